@@ -8,6 +8,13 @@ randomised start/goal/terrain as configs[4] describes). Inputs are resident in H
 region; K steps are bracketed by barrier + synchronize, the max over ranks is taken, rank 0 prints
 one JSON line. Weak scaling: B problems per GPU, no collective on the data path.
 
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, ms_per_step, ...).
+--dump-outputs DIR then writes what the last timed step left in G and V (the arrays a caller of
+eval_batch_device receives) as DIR/g.npy and DIR/jac_values.npy: float64, padding stripped, a fixed seeded
+sample of the problems when the whole batch exceeds 60 MB. The inputs depend on the arguments and SEED alone,
+so two builds can be compared output for output. --full adds everything below to the result line: each of
+them takes runs of its own after the timed region.
+
 roofline: the dominant launch's algorithmic bytes (B x its CSR values + g rows written + distinct x
 entries read, towr_gpu_kernel_info) over its average duration, measured with HIP events on the launch
 stream; the whole step's 8 (n + m + nnz) bytes per problem over the step time beside it.
@@ -237,6 +244,36 @@ def host_batch(prob, Xh, reps=3):
     return out
 
 
+DUMP_BYTES = 60 * 1000 * 1000   # --dump-outputs writes at most this much (float64) in all
+
+
+def dump_rows(B, bytes_per_row, limit=DUMP_BYTES):
+    """The problems of the batch that --dump-outputs keeps: all B when their rows fit in `limit` bytes,
+    otherwise a fixed sample (seeded by SEED alone, sorted), the same for every run and every build."""
+    keep = max(1, min(B, limit // bytes_per_row))
+    if keep == B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(SEED).choice(B, size=keep, replace=False))
+
+
+def dump_outputs(dirname, G, V, m, nnz, rank=0, limit=DUMP_BYTES):
+    """What a caller of the timed path (eval_batch_device) receives from the last timed step: g.npy, the
+    constraint values [problems, m], and jac_values.npy, the Jacobian nonzeros in CSR order [problems, nnz],
+    float64, without the leading-dimension padding, for the problems dump_rows picks. Ranks above 0 (one
+    shard of the batch each) add _rankR to the names."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = dump_rows(G.shape[0], 8 * (m + nnz), limit)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, A, cols in (("g", G, m), ("jac_values", V, nnz)):
+        if isinstance(A, np.ndarray):
+            a = A[rows]
+        else:   # device tensor: gather the kept rows on the device, copy only those
+            import torch
+            a = A[torch.from_numpy(rows).to(A.device)].cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(a[:, :cols], dtype=np.float64))
+    return len(rows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -253,6 +290,11 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the PCIe-inclusive host-buffer measurement")
     ap.add_argument("--no-gait", action="store_true", help="skip the phase-duration optimisation figure")
     ap.add_argument("--tiles-per-block", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's g and Jacobian values to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-kernel roofline, the side legs, the host-buffer and "
+                         "B = 1 latencies and the CPU baseline (--no-cpu, --no-host, --no-gait and --legs select among them)")
     ap.add_argument("--legs", default=None, help="A/B runs: comma-separated side legs to measure (objective, "
                                                  "gait_optimization, gait_torque, rotvec, pattern_watch); default all")
     args = ap.parse_args()
@@ -324,6 +366,29 @@ def main():
 
     calls = B * world * args.steps
     value = calls / wall
+    out = {
+        "metric": "full eval_g+eval_jac_g calls/sec, ANYmal trot 2.4s horizon; 1/2/4/8-GPU batch",
+        "value": value, "unit": "calls/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "warmup_settle": {"extra_untimed_steps": settle, "settle_ms": args.settle_ms},
+        "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic: randomised ANYmal trot instances (start/goal/terrain), x = x0 + seeded noise",
+        "config": {"workload": "ANYmal trot 2.4s (quadruped C1), NlpFormulation defaults, batch of independent problems",
+                   "problems_per_gpu": B, "n": prob.n, "m": prob.m, "nnz": prob.nnz,
+                   "calls_per_step": B * world, "terrains": "Flat(h~U(0,0.3)) | Stairs(randomised)",
+                   "parallelism": f"dp{world} (problem shards, no collective)"},
+    }
+    if args.dump_outputs:
+        # G and V still hold the last timed step's output (x set (K - 1) % N_X): nothing has run since
+        kept = dump_outputs(args.dump_outputs, G, V, prob.m, prob.nnz, rank)
+        out["dump_outputs"] = {"dir": args.dump_outputs, "problems": kept, "of": B, "arrays": ["g", "jac_values"]}
+    if not args.full:
+        # a plain run ends with the headline: everything below takes GPU or CPU runs of its own
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return
     bytes_call = prob.algorithmic_bytes_per_call()
     step_gbs = B * bytes_call / (kern_ms * 1e-3) / 1e9
     peak = 8000.0
@@ -351,24 +416,12 @@ def main():
         kernels[name] = {"ms": ms, "bytes_per_launch": B * by, "GB/s": B * by / (ms * 1e-3) / 1e9, "tiles_per_problem": nt}
     dom = max(step_names, key=lambda n: kernels[n]["ms"])
     achieved = kernels[dom]["GB/s"]
-    out = {
-        "metric": "full eval_g+eval_jac_g calls/sec, ANYmal trot 2.4s horizon; 1/2/4/8-GPU batch",
-        "value": value, "unit": "calls/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "warmup_settle": {"extra_untimed_steps": settle, "settle_ms": args.settle_ms},
-        "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic: randomised ANYmal trot instances (start/goal/terrain), x = x0 + seeded noise",
-        "config": {"workload": "ANYmal trot 2.4s (quadruped C1), NlpFormulation defaults, batch of independent problems",
-                   "problems_per_gpu": B, "n": prob.n, "m": prob.m, "nnz": prob.nnz,
-                   "calls_per_step": B * world, "terrains": "Flat(h~U(0,0.3)) | Stairs(randomised)",
-                   "parallelism": f"dp{world} (problem shards, no collective)"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
-                     "frac": achieved / peak, "traffic": None,
-                     "kernel": dom, "kernel_ms": kernels[dom]["ms"], "bytes_per_launch": kernels[dom]["bytes_per_launch"],
-                     "step": {"ms": kern_ms, "bytes": B * bytes_call, "GB/s": step_gbs, "frac": step_gbs / peak,
-                              "launches": step_names},
-                     "kernels": kernels},
-    }
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+                       "frac": achieved / peak, "traffic": None,
+                       "kernel": dom, "kernel_ms": kernels[dom]["ms"], "bytes_per_launch": kernels[dom]["bytes_per_launch"],
+                       "step": {"ms": kern_ms, "bytes": B * bytes_call, "GB/s": step_gbs, "frac": step_gbs / peak,
+                                "launches": step_names},
+                       "kernels": kernels}
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     if os.path.exists(pmc):
         try:

@@ -2,7 +2,7 @@
 program: its x sets, leg order and reps), 3 rounds. The default arguments are the driver's flags.
 A measurement tool, not part of the product.
 usage: python tools/ab.py TAG "name:VAR=v,VAR2=v2" "name2:TOWR_GPU_LIB=tools/build/libtowr_gpu_x.so" ...
-       [--args "--steps 20 --warmup 5 --no-cpu --no-host --legs objective,gait_optimization"] [--rounds 3]"""
+       [--args "--full --steps 20 --warmup 5 --no-cpu --no-host --legs objective,gait_optimization"] [--rounds 3]"""
 import argparse
 import json
 import os
@@ -17,7 +17,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("tag")
     ap.add_argument("cfgs", nargs="+")
-    ap.add_argument("--args", default="--steps 20 --warmup 5 --no-cpu --no-host "
+    ap.add_argument("--args", default="--full --steps 20 --warmup 5 --no-cpu --no-host "
                                       "--legs objective,gait_optimization,gait_torque,rotvec")
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()

@@ -20,7 +20,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 O=gpurun_out/${TAG}
-BENCH="--steps 20 --warmup 5"
+BENCH="--full --steps 20 --warmup 5"
 step() {   # name, seconds, command...: run it, report, stop the script on failure
   local name=$1 secs=$2; shift 2
   timeout -k 10 "$secs" "$@"
@@ -58,14 +58,14 @@ round(j['value']/1e6,3), 'M/s frac', round(j['roofline']['frac'],3), *[(k, round
     pmc)
       for C in FETCH_SIZE WRITE_SIZE; do
         step pmc_$C 200 rocprofv3 --kernel-trace --pmc $C --output-format csv -d ${O}_$C -o run -- \
-            python3 bench.py --steps 5 --warmup 2 --no-cpu --no-host --legs gait_optimization,gait_torque,objective \
+            python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-host --legs gait_optimization,gait_torque,objective \
             > ${O}_$C.log 2>&1
       done
       step pmc_summary 60 python3 tools/pmc_traffic.py ${O}_FETCH_SIZE ${O}_WRITE_SIZE ${O}_pmc_traffic.json ;;
     sq)
       step sq 200 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY \
           SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d ${O}_sq -o run -- \
-          python3 bench.py --steps 5 --warmup 2 --no-cpu --no-host --legs objective > ${O}_sq.log 2>&1
+          python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-host --legs objective > ${O}_sq.log 2>&1
       step sq_summary 60 python3 tools/pmc_summ.py ${O}_sq > ${O}_sq.txt ;;
     stamps*)
       IFS=: read -r _ ARGS <<< "$S"
