@@ -340,6 +340,44 @@ int towr_gpu_eval_batch(towr_gpu_handle h, int32_t B, const double* X, double* G
 int towr_gpu_register_host(towr_gpu_handle h, void* ptr, int64_t bytes);
 int towr_gpu_unregister_host(towr_gpu_handle h, void* ptr);
 
+/* ---- consuming a batch on the device: per-problem products with the evaluated Jacobians ---------- */
+/* The pattern by column (the transpose view of towr_gpu_jac_csr): col_ptr[n+1], row[nnz], csr_index[nnz]. The
+ * entries of column j are q in [col_ptr[j], col_ptr[j+1]); rows ascend strictly within a column; csr_index[q] is
+ * the entry's position in the CSR value array. Works on layout-only handles.                       */
+int towr_gpu_jac_csc(towr_gpu_handle h, int64_t* col_ptr /* n+1 */, int32_t* row /* nnz */, int32_t* csr_index /* nnz */);
+
+/* Y[b*ldy + i] = sum_{k in row i} V[b*ldv + k] * P[b*ldp + col[k]]           (J_b p_b, m outputs per problem)
+ * Z[b*ldz + j] (+)= sum_{k in column j} V[b*ldv + k] * LAM[b*ldl + row[k]]   (J_b^T lam_b, n outputs per problem)
+ * accumulate = 0: Z is overwritten; 1: the sum is added to what Z holds (grad f + J^T lam on top of
+ * towr_gpu_eval_cost_batch_device's GRAD). All pointers are DEVICE pointers; V holds CSR values as
+ * towr_gpu_eval_batch_device writes them; `stream` as there. ldv >= nnz, ldp, ldz >= n, ldl, ldy >= m.
+ * Bit-reproducible: Y[b] is a function of (V_b, P_b) and Z[b] of (V_b, LAM_b, and the old Z_b when accumulating)
+ * alone — the same bits for any B, any position in the batch, any stream, run to run: every output is one fixed
+ * tree of IEEE additions over exactly its own entries (no atomics, no entry skipped: a NaN or Inf term makes
+ * exactly its outputs non-finite). Rows / columns without entries give 0.0; an empty column under accumulate
+ * leaves Z_j untouched. V[b*ldv + nnz ..] is never read, Y[b*ldy + m ..] and Z[b*ldz + n ..] never written. The
+ * calls use no handle scratch (they neither wait for other calls on the handle nor drop the kept Jacobian). The
+ * first product call on a handle uploads the product tables (synchronously); later ones are asynchronous.   */
+int towr_gpu_jac_vec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv,
+                                  const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream);
+int towr_gpu_jac_tvec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv,
+                                   const double* LAM, int64_t ldl, double* Z, int64_t ldz,
+                                   int32_t accumulate, void* stream);
+
+/* Fused, chunked evaluate-and-apply: for each problem, evaluate J_b at X_b (and g_b when G != NULL), then
+ * Z_b (+)= J_b^T LAM_b when LAM != NULL (Z required) and Y_b = J_b P_b when P != NULL (Y required). The values live
+ * only in scratch owned by the handle, `chunk` problems at a time (towr_gpu_set_products_chunk; 0 = automatic:
+ * equal parts of at most 2 GiB of values each — larger chunks measured faster), so the footprint
+ * does not grow with B. Bit-identical to
+ * towr_gpu_eval_batch_device followed by the two product calls, whatever the chunk. Batch terrains as
+ * towr_gpu_eval_batch_device (exactly B entries). The scratch follows the cross-stream rule stated there; the
+ * kept Jacobian of towr_gpu_eval_g_keep_jac is not touched.                                                    */
+int towr_gpu_eval_products_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx,
+                                        double* G, int64_t ldg,
+                                        const double* LAM, int64_t ldl, double* Z, int64_t ldz, int32_t accumulate,
+                                        const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream);
+int towr_gpu_set_products_chunk(towr_gpu_handle h, int32_t problems);   /* 0 = automatic */
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

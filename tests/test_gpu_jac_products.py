@@ -1,0 +1,359 @@
+"""Batched Jacobian products on the device (towr_gpu_jac_vec_batch_device / jac_tvec / eval_products): accuracy
+against an extended-precision reference under the a-priori dot-product bound, untouched padding, bit-level
+determinism (batch size, position in the batch, stream), NaN locality, the fused chunked entry against the separate
+calls, the kept Jacobian, the C++ host driver and the argument errors.
+
+Accuracy gate: an output with k terms and S = sum |V_k| |vec_k| must satisfy |got - ref| <= 2 gamma_k S with
+gamma_k = k u / (1 - k u), u = 2^-53 — the bound of a length-k dot product in any summation order, with or without
+FMA contraction; the factor 2 covers the reference's rounding to double. Outputs without terms must be exactly 0.0.
+Under `accumulate` the pre-filled Z is one more term. Every case uses padded leading dimensions with NaN padding."""
+import functools
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests.configs import config_descs
+from towr2025_amd import TowrGpuProblem, _capi as capi
+from towr2025_amd.problem import TowrGpuError
+
+pytestmark = pytest.mark.gpu
+
+CONFIGS = config_descs()
+# the smallest shapes at which each mechanism can fail: fewer columns than lanes; short rows over several chunks;
+# long schedule columns and rows with V_b larger than LDS; the largest pattern; a fusion-free launch list
+CASES = [("monoped_procedural", 1), ("monoped_procedural", 3), ("anymal_trot_2p4s", 1), ("anymal_trot_2p4s", 37),
+         ("anymal_stairs_gaitopt", 3), ("hopper_gait_torque", 2), ("anymal_trot_rotvec", 3)]
+U = 2.0 ** -53
+EXT = np.finfo(np.longdouble).nmant > 52
+
+
+def _dev():
+    import torch
+    return torch.device("cuda:0")
+
+
+def _nan(rows, cols):
+    import torch
+    return torch.full((rows, cols), float("nan"), dtype=torch.float64, device=_dev())
+
+
+def _padded(a, ld):
+    """host (B, k) array -> device (B, ld) tensor, NaN beyond column k"""
+    import torch
+    t = _nan(a.shape[0], ld)
+    t[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
+    return t
+
+
+def _bits(t):
+    import torch
+    return t.contiguous().view(torch.int64)
+
+
+def _same_bits(a, b):
+    import torch
+    return torch.equal(_bits(a), _bits(b))
+
+
+def _lds(p):
+    return (p.nnz + 15) // 16 * 16 + 16, p.m + 5, p.n + 3   # ldv, ldy, ldz
+
+
+def _segment_sums(terms, ptr):
+    """Sums of terms[ptr[i]:ptr[i+1]]: in extended precision where long double has more than 53 bits (not yet
+    rounded to double), else math.fsum per segment; empty segments give 0."""
+    out = np.zeros(len(ptr) - 1, dtype=np.longdouble if EXT else np.float64)
+    nz = np.flatnonzero(np.diff(ptr) > 0)
+    if nz.size and EXT:
+        out[nz] = np.add.reduceat(terms, ptr[:-1][nz])
+    for i in (() if EXT else nz):
+        out[i] = math.fsum(terms[ptr[i]:ptr[i + 1]])
+    return out
+
+
+def _reference(p, V, P, LAM):
+    """Per output of host arrays V (B, nnz), P (B, n), LAM (B, m): (Y_ref, tol_Y, Z_ref before rounding, S_Z, k_Z,
+    gamma) from the engine's own V, jac_csr() and the vectors."""
+    rp, col = p.jac_csr()
+    cp, row, idx = p.jac_csc()
+    B = V.shape[0]
+    ft = np.longdouble if EXT else np.float64
+    kY, kZ = np.diff(rp).astype(np.float64), np.diff(cp).astype(np.float64)
+    Y, SY, Z, SZ = (np.zeros((B, p.m), ft), np.zeros((B, p.m), ft), np.zeros((B, p.n), ft), np.zeros((B, p.n), ft))
+    for b in range(B):
+        ty = V[b].astype(ft) * P[b][col].astype(ft)
+        tz = (V[b].astype(ft) * LAM[b][np.repeat(np.arange(p.m), np.diff(rp))].astype(ft))[idx]
+        assert np.array_equal(row, np.repeat(np.arange(p.m), np.diff(rp))[idx])
+        Y[b], SY[b] = _segment_sums(ty, rp), _segment_sums(np.abs(ty), rp)
+        Z[b], SZ[b] = _segment_sums(tz, cp), _segment_sums(np.abs(tz), cp)
+    gam = lambda k: k * U / (1 - k * U)
+    return Y.astype(np.float64), 2 * gam(kY) * SY.astype(np.float64), Z, SZ.astype(np.float64), kZ, gam
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name, B):
+    """Real Jacobians at seeded perturbations of x0, standard-normal P / LAM, the separate calls' outputs and the
+    reference, computed once per (config, B)."""
+    import torch
+    p = TowrGpuProblem(CONFIGS[name], device=0)
+    ldv, ldy, ldz = _lds(p)
+    x0 = p.initial_x()
+    rng = np.random.default_rng(20261019)
+    X = np.stack([x0 + 0.05 * np.random.default_rng(900 + b).standard_normal(p.n) for b in range(B)])
+    P, LAM, Z0 = rng.standard_normal((B, p.n)), rng.standard_normal((B, p.m)), rng.standard_normal((B, p.n))
+    Xd, Pd, LAMd = _padded(X, p.n + 1), _padded(P, p.n + 7), _padded(LAM, p.m + 9)
+    Gd, Vd = _nan(B, p.m + 2), _nan(B, ldv)
+    p.eval_batch_device(Xd, Gd, Vd)
+    Yd, Zd, Zad = _nan(B, ldy), _nan(B, ldz), _padded(Z0, ldz)
+    p.jac_vec_batch_device(Vd, Pd, Yd)
+    p.jac_tvec_batch_device(Vd, LAMd, Zd)
+    p.jac_tvec_batch_device(Vd, LAMd, Zad, accumulate=True)
+    torch.cuda.synchronize()
+    V = Vd.cpu().numpy()[:, :p.nnz]
+    assert np.isfinite(V).all()
+    return dict(p=p, X=X, P=P, LAM=LAM, Z0=Z0, Xd=Xd, Pd=Pd, LAMd=LAMd, Gd=Gd, Vd=Vd, Yd=Yd, Zd=Zd, Zad=Zad, V=V,
+                ref=_reference(p, V, P, LAM))
+
+
+def _check_products(tag, p, Yd, Zd, Zad, Z0, ref):
+    Y_ref, tolY, Z_ref, SZ, kZ, gam = ref
+    Y, Z, Za = Yd.cpu().numpy(), Zd.cpu().numpy(), Zad.cpu().numpy()
+    assert np.isnan(Y[:, p.m:]).all() and np.isnan(Z[:, p.n:]).all() and np.isnan(Za[:, p.n:]).all(), f"{tag}: padding written"
+    Y, Z, Za = Y[:, :p.m], Z[:, :p.n], Za[:, :p.n]
+    tolZ = 2 * gam(kZ) * SZ
+    tolZa = 2 * gam(kZ + 1) * (SZ + np.abs(Z0))
+    eY, eZ = np.abs(Y - Y_ref), np.abs(Z - Z_ref.astype(np.float64))
+    eZa = np.abs(Za - (Z_ref + Z0).astype(np.float64))   # (the pre-filled Z joins the sum before the one rounding)
+    worst = max(np.max(np.where(tolY > 0, eY / np.where(tolY > 0, tolY, 1), 0), initial=0.0),
+                np.max(np.where(tolZ > 0, eZ / np.where(tolZ > 0, tolZ, 1), 0), initial=0.0),
+                np.max(np.where(kZ > 0, eZa / np.where(tolZa > 0, tolZa, 1), 0), initial=0.0))
+    print(f"{tag}: largest |err| / bound {worst:.3f}")
+    assert (eY <= tolY).all() and (eZ <= tolZ).all(), f"{tag}: outside the dot-product bound ({worst:.3f})"
+    assert (eZa <= tolZa)[:, kZ > 0].all(), f"{tag}: accumulate outside the bound ({worst:.3f})"
+    rp, _ = p.jac_csr()
+    empty_r, empty_c = np.diff(rp) == 0, kZ == 0
+    assert (Y[:, empty_r] == 0.0).all() and not np.signbit(Y[:, empty_r]).any(), f"{tag}: empty rows are not 0.0"
+    assert (Z[:, empty_c] == 0.0).all(), f"{tag}: empty columns are not 0.0"
+    assert np.array_equal(Za[:, empty_c].view(np.int64), Z0[:, empty_c].view(np.int64)), f"{tag}: accumulate touched an empty column"
+
+
+@pytest.mark.parametrize("name,B", CASES)
+def test_products_within_bound_and_padding_untouched(name, B):
+    c = _case(name, B)
+    p = c["p"]
+    _check_products(f"{name} B={B}", p, c["Yd"], c["Zd"], c["Zad"], c["Z0"], c["ref"])
+    assert np.isnan(c["Vd"].cpu().numpy()[:, p.nnz:]).all()   # (never read is not observable; never written is)
+
+
+@pytest.mark.parametrize("name,B", CASES)
+def test_fused_entry_is_bit_identical_for_every_chunk(name, B):
+    import torch
+    c = _case(name, B)
+    p = c["p"]
+    ldv, ldy, ldz = _lds(p)
+    try:
+        for k in (1, 5, B, 0):
+            p.set_products_chunk(k)
+            G, Y, Z, Za = _nan(B, p.m + 2), _nan(B, ldy), _nan(B, ldz), _padded(c["Z0"], ldz)
+            p.eval_products_batch_device(c["Xd"], G=G, LAM=c["LAMd"], Z=Z, P=c["Pd"], Y=Y)
+            p.eval_products_batch_device(c["Xd"], LAM=c["LAMd"], Z=Za, accumulate=True)
+            torch.cuda.synchronize()
+            assert _same_bits(G, c["Gd"]) and _same_bits(Y, c["Yd"]), f"{name} chunk {k}: G / Y differ from the separate calls"
+            assert _same_bits(Z, c["Zd"]) and _same_bits(Za, c["Zad"]), f"{name} chunk {k}: Z differs from the separate calls"
+    finally:
+        p.set_products_chunk(0)
+
+
+def test_bits_do_not_depend_on_batch_position_or_stream():
+    import torch
+    c = _case("anymal_trot_2p4s", 37)
+    p, B = c["p"], 37
+    ldv, ldy, ldz = _lds(p)
+    for b in (0, 17, 36):   # the problem alone
+        Y, Z = _nan(1, ldy), _nan(1, ldz)
+        p.jac_vec_batch_device(c["Vd"][b:b + 1], c["Pd"][b:b + 1], Y)
+        p.jac_tvec_batch_device(c["Vd"][b:b + 1], c["LAMd"][b:b + 1], Z)
+        torch.cuda.synchronize()
+        assert _same_bits(Y, c["Yd"][b:b + 1]) and _same_bits(Z, c["Zd"][b:b + 1]), f"problem {b} alone differs from row {b} of B = 37"
+    perm = torch.from_numpy(np.random.default_rng(5).permutation(B)).to(_dev())
+    Vp, Pp, Lp = c["Vd"][perm].contiguous(), c["Pd"][perm].contiguous(), c["LAMd"][perm].contiguous()
+    Y, Z, Za = _nan(B, ldy), _nan(B, ldz), c["Zad"].clone()
+    Za[:, :p.n] = torch.from_numpy(c["Z0"]).to(_dev())[perm]
+    p.jac_vec_batch_device(Vp, Pp, Y)
+    p.jac_tvec_batch_device(Vp, Lp, Z)
+    p.jac_tvec_batch_device(Vp, Lp, Za, accumulate=True)
+    torch.cuda.synchronize()
+    assert _same_bits(Y, c["Yd"][perm]) and _same_bits(Z, c["Zd"][perm]) and _same_bits(Za, c["Zad"][perm]), "permuted batch differs"
+    s = torch.cuda.Stream(device=_dev())
+    torch.cuda.synchronize()
+    Y, Z = _nan(B, ldy), _nan(B, ldz)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        p.jac_vec_batch_device(c["Vd"], c["Pd"], Y, stream=s)
+        p.jac_tvec_batch_device(c["Vd"], c["LAMd"], Z, stream=s)
+    s.synchronize()
+    assert _same_bits(Y, c["Yd"]) and _same_bits(Z, c["Zd"]), "another stream gives other bits"
+    Y2, Z2 = _nan(B, ldy), _nan(B, ldz)   # run to run
+    p.jac_vec_batch_device(c["Vd"], c["Pd"], Y2)
+    p.jac_tvec_batch_device(c["Vd"], c["LAMd"], Z2)
+    torch.cuda.synchronize()
+    assert _same_bits(Y2, c["Yd"]) and _same_bits(Z2, c["Zd"])
+
+
+@pytest.mark.parametrize("name,B,b", [("anymal_trot_2p4s", 37, 11), ("anymal_stairs_gaitopt", 3, 1)])
+def test_nan_stays_in_its_outputs(name, B, b):
+    import torch
+    c = _case(name, B)
+    p = c["p"]
+    ldv, ldy, ldz = _lds(p)
+    rp, col = p.jac_csr()
+    row_of = np.repeat(np.arange(p.m), np.diff(rp))
+    k = int(rp[np.flatnonzero(np.diff(rp) > 3)[40]]) + 2        # an entry inside a row of several
+    Vn = c["Vd"].clone()
+    Vn[b, k] = float("nan")
+    Y, Z = _nan(B, ldy), _nan(B, ldz)
+    p.jac_vec_batch_device(Vn, c["Pd"], Y)
+    p.jac_tvec_batch_device(Vn, c["LAMd"], Z)
+    torch.cuda.synchronize()
+    nanY, nanZ = torch.isnan(Y[:, :p.m]).cpu().numpy(), torch.isnan(Z[:, :p.n]).cpu().numpy()
+    expY, expZ = np.zeros_like(nanY), np.zeros_like(nanZ)
+    expY[b, row_of[k]] = True
+    expZ[b, col[k]] = True
+    assert np.array_equal(nanY, expY) and np.array_equal(nanZ, expZ), "a NaN value reached other outputs (or missed its own)"
+    keepY, keepZ = torch.from_numpy(~expY).to(_dev()), torch.from_numpy(~expZ).to(_dev())
+    assert torch.equal(_bits(Y[:, :p.m])[keepY], _bits(c["Yd"][:, :p.m])[keepY]), "a clean Y output changed bits"
+    assert torch.equal(_bits(Z[:, :p.n])[keepZ], _bits(c["Zd"][:, :p.n])[keepZ]), "a clean Z output changed bits"
+    # one multiplier NaN: exactly the columns present in its row
+    i = int(row_of[k])
+    Ln = c["LAMd"].clone()
+    Ln[b, i] = float("nan")
+    Z = _nan(B, ldz)
+    p.jac_tvec_batch_device(c["Vd"], Ln, Z)
+    torch.cuda.synchronize()
+    nanZ = torch.isnan(Z[:, :p.n]).cpu().numpy()
+    expZ = np.zeros_like(nanZ)
+    expZ[b, col[rp[i]:rp[i + 1]]] = True
+    assert np.array_equal(nanZ, expZ), "a NaN multiplier did not turn exactly its row's columns NaN"
+    keepZ = torch.from_numpy(~expZ).to(_dev())
+    assert torch.equal(_bits(Z[:, :p.n])[keepZ], _bits(c["Zd"][:, :p.n])[keepZ])
+
+
+def test_products_of_oracle_values():
+    """The products take any values on the pattern: the oracle's Jacobian, uploaded, within the same bound."""
+    import torch
+    from oracle.oracle import Oracle
+    c = _case("anymal_trot_2p4s", 1)
+    p = c["p"]
+    ldv, ldy, ldz = _lds(p)
+    o = Oracle(CONFIGS["anymal_trot_2p4s"])
+    r, cc, v = o.eval_jac(c["X"][0])
+    pr, pc = p.jac_structure()
+    assert np.array_equal(r, pr) and np.array_equal(cc, pc)
+    V = v[None, :]
+    Vd = _padded(V, ldv)
+    Y, Z, Za = _nan(1, ldy), _nan(1, ldz), _padded(c["Z0"], ldz)
+    p.jac_vec_batch_device(Vd, c["Pd"], Y)
+    p.jac_tvec_batch_device(Vd, c["LAMd"], Z)
+    p.jac_tvec_batch_device(Vd, c["LAMd"], Za, accumulate=True)
+    torch.cuda.synchronize()
+    _check_products("oracle values", p, Y, Z, Za, c["Z0"], _reference(p, V, c["P"], c["LAM"]))
+
+
+def test_fused_entry_with_per_problem_terrain():
+    """Chunk c0 must use terrains c0 .. : flat and stairs alternate, so a chunk that starts over at terrain 0 differs."""
+    import torch
+    from towr2025_amd import formulation as F
+    p = TowrGpuProblem(F.anymal_trot().to_desc())
+    B = 33
+    rng = np.random.default_rng(7)
+    terrains = []
+    for b in range(B):
+        t = F.HeightMap.Flat(rng.uniform(0, 0.3)) if b % 2 else \
+            F.HeightMap(F.HeightMap.StairsID, (rng.uniform(0.8, 1.4), 0.4, rng.uniform(0.1, 0.25), rng.uniform(0.1, 0.25), 1.0))
+        terrains.append(F.anymal_trot(terrain=t).terrain_.to_c())
+    p.set_batch_terrain(terrains)
+    ldv, ldy, ldz = _lds(p)
+    x0 = p.initial_x()
+    X = np.stack([x0 + 0.05 * np.random.default_rng(500 + b).standard_normal(p.n) for b in range(B)])
+    Xd, Pd, Ld = _padded(X, p.n), _padded(rng.standard_normal((B, p.n)), p.n), _padded(rng.standard_normal((B, p.m)), p.m)
+    G0, V0, Y0, Z0 = _nan(B, p.m), _nan(B, ldv), _nan(B, ldy), _nan(B, ldz)
+    p.eval_batch_device(Xd, G0, V0)
+    p.jac_vec_batch_device(V0, Pd, Y0)
+    p.jac_tvec_batch_device(V0, Ld, Z0)
+    for k in (4, 33):
+        p.set_products_chunk(k)
+        G, Y, Z = _nan(B, p.m), _nan(B, ldy), _nan(B, ldz)
+        p.eval_products_batch_device(Xd, G=G, LAM=Ld, Z=Z, P=Pd, Y=Y)
+        torch.cuda.synchronize()
+        assert _same_bits(G, G0) and _same_bits(Y, Y0) and _same_bits(Z, Z0), f"chunk {k}: differs from the separate calls"
+    with pytest.raises(TowrGpuError, match="batch terrains"):   # exactly B entries, as eval_batch_device
+        p.eval_products_batch_device(Xd[:5], LAM=Ld[:5], Z=_nan(5, ldz))
+
+
+def test_fused_entry_keeps_the_kept_jacobian():
+    c = _case("anymal_trot_2p4s", 1)
+    p = TowrGpuProblem(CONFIGS["anymal_trot_2p4s"], device=0)
+    x = c["X"][0]
+    v_ref = p.eval_jac_values(x)
+    p.eval_g_keep_jac(x)
+    other = _case("anymal_trot_2p4s", 37)
+    ldv, ldy, ldz = _lds(p)
+    p.eval_products_batch_device(other["Xd"], LAM=other["LAMd"], Z=_nan(37, ldz), P=other["Pd"], Y=_nan(37, ldy))
+    v = p.eval_jac_values_kept(x)
+    assert np.array_equal(v.view(np.int64), v_ref.view(np.int64))
+
+
+def test_host_driver_products():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    host = os.path.join(root, "towr2025_amd", "host")
+    subprocess.check_call(["make", "-s", "-C", host])
+    r = subprocess.run([os.path.join(host, "build", "towr_host_check"), "anymal", "--products", "0"], capture_output=True, text=True)
+    print(r.stdout.strip(), r.stderr.strip())
+    assert r.returncode == 0 and r.stdout.startswith("products ok"), r.stdout + r.stderr
+
+
+def test_argument_errors_launch_nothing():
+    import ctypes as C
+    import torch
+    c = _case("monoped_procedural", 3)
+    p, B = c["p"], 3
+    ldv, ldy, ldz = _lds(p)
+    Y, Z, G = _nan(B, ldy), _nan(B, ldz), _nan(B, p.m)
+    short = lambda t, cols: torch.as_strided(t, (B, cols), (cols - 1, 1))   # a leading dimension one too small
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    lib, h, V, P, L, X = p._lib, p._h, c["Vd"], c["Pd"], c["LAMd"], c["Xd"]
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    INV = capi.TOWR_ERR_INVALID
+    n, m, nnz = p.sizes()
+    vec, tvec, fused = lib.towr_gpu_jac_vec_batch_device, lib.towr_gpu_jac_tvec_batch_device, lib.towr_gpu_eval_products_batch_device
+    rcs = [vec(h, B, ptr(V), nnz - 1, ptr(P), P.stride(0), ptr(Y), ldy, s), vec(h, B, ptr(V), ldv, ptr(P), n - 1, ptr(Y), ldy, s),
+           vec(h, B, ptr(V), ldv, ptr(P), P.stride(0), ptr(Y), m - 1, s), vec(h, -1, ptr(V), ldv, ptr(P), P.stride(0), ptr(Y), ldy, s),
+           vec(h, B, None, ldv, ptr(P), P.stride(0), ptr(Y), ldy, s), vec(h, B, ptr(V), ldv, None, P.stride(0), ptr(Y), ldy, s),
+           vec(h, B, ptr(V), ldv, ptr(P), P.stride(0), None, ldy, s),
+           tvec(h, B, ptr(V), nnz - 1, ptr(L), L.stride(0), ptr(Z), ldz, 0, s), tvec(h, B, ptr(V), ldv, ptr(L), m - 1, ptr(Z), ldz, 0, s),
+           tvec(h, B, ptr(V), ldv, ptr(L), L.stride(0), ptr(Z), n - 1, 0, s), tvec(h, -1, ptr(V), ldv, ptr(L), L.stride(0), ptr(Z), ldz, 0, s),
+           tvec(h, B, None, ldv, ptr(L), L.stride(0), ptr(Z), ldz, 0, s), tvec(h, B, ptr(V), ldv, None, L.stride(0), ptr(Z), ldz, 0, s),
+           tvec(h, B, ptr(V), ldv, ptr(L), L.stride(0), None, ldz, 0, s),
+           fused(h, B, ptr(X), X.stride(0), ptr(G), m, None, 0, ptr(Z), ldz, 0, ptr(P), P.stride(0), ptr(Y), ldy, s),       # Z without LAM
+           fused(h, B, ptr(X), X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), ldz, 0, None, 0, ptr(Y), ldy, s),       # Y without P
+           fused(h, B, None, X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), ldz, 0, ptr(P), P.stride(0), ptr(Y), ldy, s),
+           fused(h, -1, ptr(X), X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), ldz, 0, ptr(P), P.stride(0), ptr(Y), ldy, s),
+           fused(h, B, ptr(X), X.stride(0), ptr(G), m, ptr(L), m - 1, ptr(Z), ldz, 0, ptr(P), P.stride(0), ptr(Y), ldy, s),
+           fused(h, B, ptr(X), X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), n - 1, 0, ptr(P), P.stride(0), ptr(Y), ldy, s),
+           fused(h, B, ptr(X), X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), ldz, 0, ptr(P), n - 1, ptr(Y), ldy, s),
+           fused(h, B, ptr(X), X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), ldz, 0, ptr(P), P.stride(0), ptr(Y), m - 1, s)]
+    torch.cuda.synchronize()
+    assert rcs == [INV] * len(rcs), rcs
+    assert p._lib.towr_gpu_last_error(p._h)
+    assert torch.isnan(Y).all() and torch.isnan(Z).all() and torch.isnan(G).all(), "a refused call wrote something"
+    with pytest.raises(TowrGpuError, match="leading dimension"):     # the Python layer refuses the same before the C-ABI
+        p.jac_vec_batch_device(short(c["Vd"], nnz), P, Y)
+    # B = 0 with valid arguments, as towr_gpu_eval_batch_device: nothing to do, no error
+    assert vec(h, 0, ptr(V), ldv, ptr(P), P.stride(0), ptr(Y), ldy, s) == capi.TOWR_OK
+    assert tvec(h, 0, ptr(V), ldv, ptr(L), L.stride(0), ptr(Z), ldz, 0, s) == capi.TOWR_OK
+    assert fused(h, 0, ptr(X), X.stride(0), ptr(G), m, ptr(L), L.stride(0), ptr(Z), ldz, 0, ptr(P), P.stride(0), ptr(Y), ldy, s) == capi.TOWR_OK
+    torch.cuda.synchronize()
+    assert torch.isnan(Y).all() and torch.isnan(Z).all()

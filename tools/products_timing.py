@@ -1,0 +1,92 @@
+"""Jacobian-product timings on the GPU box (tool, not product): per call, on one box in one session,
+  (a) eval_batch_device (g + J) alone — the yardstick on that box;
+  (b) jac_vec_batch_device; (c) jac_tvec_batch_device (overwrite);
+  (d) eval_products_batch_device (g, J^T lam and J p) at the automatic chunk and at chunks of 128, 512 and B,
+for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
+rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
+warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
+printed. usage: python tools/products_timing.py [anymal|gait|all]"""
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from towr2025_amd import TowrGpuProblem, _capi as capi  # noqa: E402
+from towr2025_amd import formulation as F  # noqa: E402
+
+REPS = int(os.environ.get("REPS", "20"))
+ROUNDS = int(os.environ.get("ROUNDS", "5"))
+PEAK = 8.0e12
+
+
+def batch_x(p, B, seed=20261019):
+    """x0 + noise per variable (phase durations: +-3 % multiplicative), as bench.make_batch perturbs them."""
+    rng = np.random.default_rng(seed)
+    x0 = p.initial_x()
+    sched = np.zeros(p.n, dtype=bool)
+    for kind, _ee, c0, n in p.varset_info():
+        if kind == capi.VAR_EE_SCHEDULE:
+            sched[c0:c0 + n] = True
+    X = x0 + 0.02 * rng.standard_normal((B, p.n))
+    X[:, sched] = x0[sched] * (1.0 + 0.03 * rng.standard_normal((B, int(sched.sum()))))
+    return X
+
+
+def run(name, desc, B):
+    dev = torch.device("cuda", 0)
+    p = TowrGpuProblem(desc, device=0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    ld = lambda k: (k + 15) // 16 * 16
+    X = torch.from_numpy(batch_x(p, B)).to(dev)
+    G = torch.empty((B, ld(p.m)), dtype=torch.float64, device=dev)
+    V = torch.empty((B, ld(p.nnz)), dtype=torch.float64, device=dev)
+    P = torch.randn((B, ld(p.n)), dtype=torch.float64, device=dev)
+    LAM = torch.randn((B, ld(p.m)), dtype=torch.float64, device=dev)
+    Y, Z = torch.empty_like(LAM), torch.empty_like(P)
+
+    def fused(chunk):
+        def f():
+            p.set_products_chunk(chunk)
+            p.eval_products_batch_device(X, G=G, LAM=LAM, Z=Z, P=P, Y=Y, stream=stream)
+        return f
+    variants = [("a eval_batch_device", lambda: p.eval_batch_device(X, G, V, stream=stream)),
+                ("b jac_vec", lambda: p.jac_vec_batch_device(V, P, Y, stream=stream)),
+                ("c jac_tvec", lambda: p.jac_tvec_batch_device(V, LAM, Z, stream=stream)),
+                ("d fused chunk auto", fused(0)), ("d fused chunk 128", fused(128)), ("d fused chunk 512", fused(512)),
+                (f"d fused chunk B={B}", fused(B))]
+    for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k, _ in variants}
+    for _ in range(ROUNDS):
+        for k, fn in variants:
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            for _ in range(REPS):
+                fn()
+            z.record(stream)
+            torch.cuda.synchronize()
+            times[k].append(a.elapsed_time(z) / REPS)
+    bytes_prod = 8 * (p.nnz + p.n + p.m) * B
+    print(f"{name}: B={B} n={p.n} m={p.m} nnz={p.nnz}  product bytes {bytes_prod / 1e9:.3f} GB, V {8 * p.nnz * B / 2**30:.2f} GiB", flush=True)
+    for k, _ in variants:
+        t = times[k]
+        med = statistics.median(t)
+        rate = f"  {bytes_prod / (med * 1e-3) / 1e12:.2f} TB/s = {100 * bytes_prod / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if k[0] in "bc" else ""
+        print(f"  {k:22s} {med:.4f} ms  (min {min(t):.4f} max {max(t):.4f}){rate}", flush=True)
+    p.set_products_chunk(0)
+
+
+if __name__ == "__main__":
+    which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if which in ("anymal", "all"):
+        run("anymal_trot", F.anymal_trot().to_desc(), int(os.environ.get("B", "4096")))
+    if which in ("gait", "all"):
+        run("anymal_stairs_gaitopt", F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True).to_desc(),
+            int(os.environ.get("B_GAIT", "1024")))

@@ -140,6 +140,15 @@ SYMBOLS = {
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_int32, C.c_int32, C.c_void_p]),
     "towr_gpu_eval_batch": (C.c_int, [_HANDLE, C.c_int32, _DP, _DP, _DP]),
+    "towr_gpu_jac_csc": (C.c_int, [_HANDLE, _LP, _IP, _IP]),
+    "towr_gpu_jac_vec_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_jac_tvec_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "towr_gpu_eval_products_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_set_products_chunk": (C.c_int, [_HANDLE, C.c_int32]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -201,6 +201,22 @@ constexpr int kRvAb = 27;     // (dyn_base_ab, read by the instant's group-0 lan
 // (field-major over the whole batch put them 1.8 MB apart at B = 4096); field f of pair pr at rv_at(pr) + 64 f
 __host__ __device__ constexpr int64_t rv_at(int64_t pr) { return (pr >> 6) * (int64_t)kRvCoef * 64 + (pr & 63); }
 
+// Batched Jacobian products on the evaluated values (jprod.hip): Y_b = J_b p_b and Z_b (+)= J_b^T lam_b, one block
+// per problem over fixed chunks of kJpChunk consecutive CSR entries. A chunk's products land in an LDS tile; each
+// output that has entries in the chunk is one segment of it, summed in ascending order by one lane (short) or by one
+// wave (len >= Layout::jp_long: lane l takes entries l, l + 64, ..., then a fixed shuffle tree):
+//   J p:    a row's span of the tile (q0 = tile position). A row cut by a chunk boundary continues through a carry
+//           (flags bit 0: add the carry of the chunk before; bit 1: the row goes on, store the carry, not Y);
+//   J^T l:  a column's entries of the chunk, through the chunk-local by-column list Layout::jp_cidx (q0 = index
+//           into it, rows ascending); the chunk's partial is added to the column's running sum in LDS.
+// Chunks are visited in ascending order, so every output has one summation tree, whatever the batch.
+constexpr int kJpChunk = 2048;
+constexpr int kJpBlock = 256;
+constexpr int kJpLongDefault = 32;
+struct JpSeg { int32_t out, q0, len, flags; };
+// segments [rs0, rs0 + rns) short rows then rnl long rows (jp_rseg); likewise columns (jp_cseg)
+struct JpChunk { int32_t rs0, rns, rnl, cs0, cns, cnl, reserved[2]; };
+
 struct VarSetInfo { int kind, ee, col0, n; };
 struct ConsInfo { int kind, ee, row0, rows; };
 
@@ -297,7 +313,37 @@ struct Layout {
   // The wrapped sets are evaluated by a second layout (the handle's soft child) whose constraint
   // list is exactly these sets in this order (soft_desc).
   std::vector<std::pair<int32_t, int32_t>> soft;
+  // The pattern by column (towr_gpu_jac_csc): column j holds entries [col_ptr[j], col_ptr[j + 1]), rows ascending;
+  // csc_index = the entry's CSR position. And the product kernels' tables (JpSeg / JpChunk above): the row of every
+  // CSR entry, the chunk-local by-column lists (padded to whole chunks), the segments, the rows without entries.
+  std::vector<int64_t> col_ptr;
+  std::vector<int32_t> csc_row, csc_index;
+  std::vector<int32_t> jp_row;
+  std::vector<uint16_t> jp_cidx;
+  std::vector<JpSeg> jp_rseg, jp_cseg;
+  std::vector<JpChunk> jp_chunks;
+  std::vector<int32_t> jp_empty_rows;
+  int32_t jp_long = kJpLongDefault;   // segments of at least this many entries are summed by a wave
 };
+void build_jprod(Layout& L);   // fills the members above from row_ptr / col
+// the product kernels (jprod.hip): one block of kJpBlock threads per problem; Vec = P (ldvec >= n) and Out = Y for
+// J p, Vec = LAM (>= m) and Out = Z for J^T lam; the tables are the device copies of the members above
+struct JpArgs {
+  const double* V; int64_t ldv;
+  const double* Vec; int64_t ldvec;
+  double* Out; int64_t ldo;
+  const int32_t *col, *row;
+  const uint16_t* cidx;
+  const JpSeg *rseg, *cseg;
+  const JpChunk* chunks;
+  const int32_t *empty_rows, *col_ptr;   // col_ptr as int32 (nnz < 2^31)
+  int64_t nnz;
+  int32_t n, m, n_chunks, n_empty, accumulate, reserved;
+};
+size_t jp_vec_lds(int n, int m);    // dynamic LDS (bytes)
+size_t jp_tvec_lds(int n, int m);
+const void* jp_vec_kernel();
+const void* jp_tvec_kernel();
 
 #ifndef TOWR_COST_SLOT_MAX   // (experiment builds: -DTOWR_COST_SLOT_MAX=0, the limbs everywhere)
 #define TOWR_COST_SLOT_MAX 8192

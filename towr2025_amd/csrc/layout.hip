@@ -1018,6 +1018,72 @@ towr_problem_desc_t soft_desc(const towr_problem_desc_t& d, const Layout& L) {
   return s;
 }
 
+// The pattern by column and the product kernels' chunk tables (layout.h JpSeg): a counting sort of the CSR entries
+// by column keeps the rows ascending inside a column; the same per chunk gives its by-column lists.
+void build_jprod(Layout& L) {
+  const int64_t nnz = L.nnz;
+  L.col_ptr.assign((size_t)L.n + 1, 0);
+  for (int32_t c : L.col) ++L.col_ptr[(size_t)c + 1];
+  for (int j = 0; j < L.n; ++j) L.col_ptr[j + 1] += L.col_ptr[j];
+  L.csc_row.assign((size_t)nnz, 0);
+  L.csc_index.assign((size_t)nnz, 0);
+  L.jp_row.assign((size_t)nnz, 0);
+  L.jp_empty_rows.clear();
+  {
+    std::vector<int64_t> fill(L.col_ptr.begin(), L.col_ptr.end() - 1);
+    for (int r = 0; r < L.m; ++r) {
+      if (L.row_ptr[r] == L.row_ptr[r + 1]) L.jp_empty_rows.push_back(r);
+      for (int64_t k = L.row_ptr[r]; k < L.row_ptr[r + 1]; ++k) {
+        const int64_t q = fill[L.col[k]]++;
+        L.csc_row[q] = r;
+        L.csc_index[q] = (int32_t)k;
+        L.jp_row[k] = r;
+      }
+    }
+  }
+  const int64_t nch = (nnz + kJpChunk - 1) / kJpChunk;
+  L.jp_chunks.assign((size_t)nch, JpChunk{});
+  L.jp_cidx.assign((size_t)nch * kJpChunk, 0);
+  L.jp_rseg.clear();
+  L.jp_cseg.clear();
+  std::vector<int32_t> cnt((size_t)L.n + 1), cols;
+  std::vector<JpSeg> shortq, longq;
+  auto flush = [&](std::vector<JpSeg>& dst, int32_t* s0, int32_t* ns, int32_t* nl) {
+    *s0 = (int32_t)dst.size(); *ns = (int32_t)shortq.size(); *nl = (int32_t)longq.size();
+    dst.insert(dst.end(), shortq.begin(), shortq.end());
+    dst.insert(dst.end(), longq.begin(), longq.end());
+    shortq.clear(); longq.clear();
+  };
+  int r = 0;   // first row that may reach into the chunk
+  for (int64_t c = 0; c < nch; ++c) {
+    const int64_t k0 = c * kJpChunk, k1 = std::min<int64_t>(nnz, k0 + kJpChunk);
+    JpChunk& ch = L.jp_chunks[(size_t)c];
+    while (r < L.m && L.row_ptr[r + 1] <= k0) ++r;
+    for (int q = r; q < L.m && L.row_ptr[q] < k1; ++q) {   // rows with entries in [k0, k1)
+      const int64_t a = std::max(L.row_ptr[q], k0), b = std::min(L.row_ptr[q + 1], k1);
+      if (a >= b) continue;
+      JpSeg s{q, (int32_t)(a - k0), (int32_t)(b - a), (L.row_ptr[q] < k0 ? 1 : 0) | (L.row_ptr[q + 1] > k1 ? 2 : 0)};
+      (s.len >= L.jp_long ? longq : shortq).push_back(s);
+    }
+    flush(L.jp_rseg, &ch.rs0, &ch.rns, &ch.rnl);
+    cols.clear();   // the chunk's columns, each with its count, then its start in the chunk's list
+    for (int64_t k = k0; k < k1; ++k)
+      if (cnt[L.col[k]]++ == 0) cols.push_back(L.col[k]);
+    std::sort(cols.begin(), cols.end());
+    int32_t at = 0;
+    for (int32_t j : cols) {
+      JpSeg s{j, (int32_t)(k0 + at), cnt[j], 0};
+      (s.len >= L.jp_long ? longq : shortq).push_back(s);
+      const int32_t n = cnt[j];
+      cnt[j] = at;
+      at += n;
+    }
+    for (int64_t k = k0; k < k1; ++k) L.jp_cidx[(size_t)(k0 + cnt[L.col[k]]++)] = (uint16_t)(k - k0);   // CSR order: rows ascend
+    for (int32_t j : cols) cnt[j] = 0;
+    flush(L.jp_cseg, &ch.cs0, &ch.cns, &ch.cnl);
+  }
+}
+
 void build_misc_xspan(Layout& L);
 int build_layout(const towr_problem_desc_t& d, Layout& L, std::string& err) { return build_layout_ex(d, 0, nullptr, L, err); }
 
@@ -1692,6 +1758,7 @@ int build_layout_ex(const towr_problem_desc_t& d, int n_data, const towr_data_t*
     }
     build_misc_xspan(L);
   }
+  build_jprod(L);
   return TOWR_OK;
 }
 

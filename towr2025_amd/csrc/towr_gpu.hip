@@ -156,6 +156,15 @@ struct towr_gpu_handle_s {
   int cost_grid[3] = {1, 1, 1};     // the cost kernel's persistent grid per accumulation (launch_cost)
   double *d_sg = nullptr, *d_sv = nullptr;
   int64_t soft_cap_g = 0, soft_cap_v = 0;   // problems the scratch holds
+  // Jacobian products (jprod.hip): the tables' device copies, uploaded by the first product call on the handle
+  // (products_ready), and the fused entry's own values scratch (a chunk of problems; never d_v, so the kept
+  // Jacobian survives); products_chunk: towr_gpu_set_products_chunk (0 = automatic)
+  bool jp_ready = false;
+  JpArgs jp{};
+  void* d_jp[8] = {};
+  double* d_pv = nullptr;
+  int64_t pv_cap = 0;
+  int32_t products_chunk = 0;
 };
 
 namespace {
@@ -1420,6 +1429,10 @@ int towr_gpu_destroy(towr_gpu_handle h) {
                  h->single.d_units, h->d_gs_geo, h->d_gs_tmpl, h->d_gs_pcode, h->d_gs_blk[0], h->d_gs_blk[1], h->d_gs_blk[2],
                  h->d_gs_inst[0], h->d_gs_inst[1], h->d_gs_inst[2], h->d_gsrec, h->d_rvc, h->d_rvi, h->d_gs_segs, h->d_gs_tseg, h->d_gs_vmap, h->d_gs_ws, h->d_gs_blob};
   if (h->device >= 0) for (void* p : dev) if (p) (void)hipFree(p);
+  if (h->device >= 0) {
+    for (void* p : h->d_jp) if (p) (void)hipFree(p);
+    if (h->d_pv) (void)hipFree(h->d_pv);
+  }
   void* host[] = {h->h_x, h->h_g, h->h_v};
   for (void* p : host) if (p) (void)hipHostFree(p);
   for (const auto& r : h->pinned) (void)hipHostUnregister(const_cast<char*>(r.p));
@@ -1673,6 +1686,134 @@ int towr_gpu_eval_batch_device(towr_gpu_handle h, int32_t B, const double* X, in
   if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);   // NULL = HIP's default stream
   return launch(h, B, X, ldx, G, ldg, V, ldv, want_g, want_jac, s, ter, per, -1);
+}
+
+// ---- Jacobian products (jprod.hip) ----------------------------------------------------------------------------
+int towr_gpu_jac_csc(towr_gpu_handle h, int64_t* col_ptr, int32_t* row, int32_t* csr_index) {
+  if (!h || !col_ptr || !row || !csr_index) return fail(h, TOWR_ERR_INVALID, "null argument");
+  const Layout& L = h->L;
+  std::memcpy(col_ptr, L.col_ptr.data(), sizeof(int64_t) * L.col_ptr.size());
+  if (L.nnz) {
+    std::memcpy(row, L.csc_row.data(), sizeof(int32_t) * L.csc_row.size());
+    std::memcpy(csr_index, L.csc_index.data(), sizeof(int32_t) * L.csc_index.size());
+  }
+  return TOWR_OK;
+}
+
+// The product tables' device copies, on the first product call of the handle (towr_gpu_create and the single-problem
+// callbacks never pay for them). Synchronous copies: that first call is not asynchronous.
+static int products_ready(towr_gpu_handle h) {
+  if (h->jp_ready) return TOWR_OK;
+  const Layout& L = h->L;
+  const size_t lv = jp_vec_lds(L.n, L.m), lt = jp_tvec_lds(L.n, L.m);
+  if (std::max(lv, lt) > kLdsMax) return fail(h, TOWR_ERR_UNSUPPORTED, "problem too large for the product kernels' LDS");
+  if ((lv > 64 * 1024 && hipFuncSetAttribute(jp_vec_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lv) != hipSuccess) ||
+      (lt > 64 * 1024 && hipFuncSetAttribute(jp_tvec_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lt) != hipSuccess))
+    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  const std::vector<int32_t> cp32(L.col_ptr.begin(), L.col_ptr.end());
+  int32_t *col = nullptr, *row = nullptr, *er = nullptr, *cp = nullptr;
+  uint16_t* cidx = nullptr;
+  JpSeg *rs = nullptr, *cs = nullptr;
+  JpChunk* ch = nullptr;
+  int r = 0;
+  (void)((r = upload(h, &col, L.col)) || (r = upload(h, &row, L.jp_row)) || (r = upload(h, &cidx, L.jp_cidx)) ||
+         (r = upload(h, &rs, L.jp_rseg)) || (r = upload(h, &cs, L.jp_cseg)) || (r = upload(h, &ch, L.jp_chunks)) ||
+         (r = upload(h, &er, L.jp_empty_rows)) || (r = upload(h, &cp, cp32)));
+  void* all[8] = {col, row, cidx, rs, cs, ch, er, cp};
+  if (r) {
+    for (void* p : all) if (p) (void)hipFree(p);
+    return r;
+  }
+  std::copy(all, all + 8, h->d_jp);
+  JpArgs& a = h->jp;
+  a.col = col; a.row = row; a.cidx = cidx; a.rseg = rs; a.cseg = cs; a.chunks = ch; a.empty_rows = er; a.col_ptr = cp;
+  a.nnz = L.nnz; a.n = L.n; a.m = L.m;
+  a.n_chunks = (int32_t)L.jp_chunks.size(); a.n_empty = (int32_t)L.jp_empty_rows.size();
+  h->jp_ready = true;
+  return TOWR_OK;
+}
+
+// one product launch over B problems: Y = J p (tvec = false) or Z (+)= J^T lam
+static int launch_product(towr_gpu_handle h, bool tvec, int B, const double* V, int64_t ldv, const double* vec, int64_t ldvec,
+                          double* out, int64_t ldo, int accumulate, hipStream_t s) {
+  JpArgs a = h->jp;
+  a.V = V; a.ldv = ldv; a.Vec = vec; a.ldvec = ldvec; a.Out = out; a.ldo = ldo; a.accumulate = accumulate;
+  void* args[] = {&a};
+  const size_t lds = tvec ? jp_tvec_lds(a.n, a.m) : jp_vec_lds(a.n, a.m);
+  HIPCHK(h, launch_kernel(tvec ? jp_tvec_kernel() : jp_vec_kernel(), dim3((unsigned)B), dim3(kJpBlock), args, lds, s));
+  return TOWR_OK;
+}
+
+int towr_gpu_jac_vec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv, const double* P, int64_t ldp,
+                                  double* Y, int64_t ldy, void* stream) {
+  if (!h || B < 0 || !V || !P || !Y) return fail(h, TOWR_ERR_INVALID, "bad argument (null pointer or B < 0)");
+  const Layout& L = h->L;
+  if (ldv < L.nnz || ldp < L.n || ldy < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / n (P) / m (Y)");
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = products_ready(h)) return rc;
+  return launch_product(h, false, B, V, ldv, P, ldp, Y, ldy, 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_jac_tvec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv, const double* LAM, int64_t ldl,
+                                   double* Z, int64_t ldz, int32_t accumulate, void* stream) {
+  if (!h || B < 0 || !V || !LAM || !Z) return fail(h, TOWR_ERR_INVALID, "bad argument (null pointer or B < 0)");
+  const Layout& L = h->L;
+  if (ldv < L.nnz || ldl < L.m || ldz < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAM) / n (Z)");
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = products_ready(h)) return rc;
+  return launch_product(h, true, B, V, ldv, LAM, ldl, Z, ldz, accumulate != 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_set_products_chunk(towr_gpu_handle h, int32_t problems) {
+  if (!h || problems < 0) return fail(h, TOWR_ERR_INVALID, "bad argument");
+  h->products_chunk = problems;
+  return TOWR_OK;
+}
+
+// The values of `chunk` problems at a time in the handle's own scratch (d_pv, ordered across streams like the other
+// scratch: scratch_acquire / scratch_release), each chunk evaluated by the batch launch sequence and consumed by the
+// product kernels behind it on the caller's stream.
+int towr_gpu_eval_products_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, double* G, int64_t ldg,
+                                        const double* LAM, int64_t ldl, double* Z, int64_t ldz, int32_t accumulate,
+                                        const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream) {
+  if (!h || B < 0 || !X) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or B < 0)");
+  const Layout& L = h->L;
+  if ((Z && !LAM) || (Y && !P)) return fail(h, TOWR_ERR_INVALID, "Z given without LAM, or Y without P");
+  if ((LAM && !Z) || (P && !Y)) return fail(h, TOWR_ERR_INVALID, "LAM given without Z, or P without Y");
+  if (ldx < L.n || (G && ldg < L.m) || (LAM && (ldl < L.m || ldz < L.n)) || (P && (ldp < L.n || ldy < L.m)))
+    return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X, P, Z) / m (G, LAM, Y)");
+  if (int rc = bind(h)) return rc;
+  const towr_terrain_t* ter;
+  int per;
+  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
+  if (B == 0) return TOWR_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool want_v = LAM || P;
+  if (!want_v) return G ? launch(h, B, X, ldx, G, ldg, nullptr, 0, 1, 0, s, ter, per, -1) : TOWR_OK;
+  if (int rc = products_ready(h)) return rc;
+  // Automatic chunk: measured, a chunk sized to the Infinity Cache (128 MiB of values) gains nothing — the
+  // fused call at chunk = B costs what the three separate calls cost — and every further chunk costs its launch
+  // sequence and an underfilled chip (ANYmal gait, B = 1024: 18.8 ms in 15 chunks vs 2.6 ms in one). So the chunk is
+  // as large as a 2 GiB scratch allows (the footprint bound), cut into equal parts.
+  constexpr int64_t kAutoBytes = int64_t(2) << 30;
+  const int64_t ldv = std::max<int64_t>(16, (L.nnz + 15) & ~int64_t(15));   // rows on 128-byte boundaries
+  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ldv));
+  const int64_t parts = (B + cap - 1) / cap;
+  const int C = (int)std::min<int64_t>(B, h->products_chunk > 0 ? h->products_chunk : (B + parts - 1) / parts);
+  if (int rc = scratch_acquire(h, s)) return rc;
+  int rc = scratch_grow(h, &h->d_pv, &h->pv_cap, C, ldv);
+  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
+    const int cb = std::min(C, B - c0);
+    rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, G ? G + (int64_t)c0 * ldg : nullptr, ldg, h->d_pv, ldv, G != nullptr, 1, s,
+                per ? ter + c0 : ter, per, -1);
+    if (rc == TOWR_OK && LAM)
+      rc = launch_product(h, true, cb, h->d_pv, ldv, LAM + (int64_t)c0 * ldl, ldl, Z + (int64_t)c0 * ldz, ldz, accumulate != 0, s);
+    if (rc == TOWR_OK && P) rc = launch_product(h, false, cb, h->d_pv, ldv, P + (int64_t)c0 * ldp, ldp, Y + (int64_t)c0 * ldy, ldy, 0, s);
+  }
+  const int rr = scratch_release(h, s);   // (also after a failure: what was queued still orders the scratch)
+  return rc ? rc : rr;
 }
 
 int towr_gpu_kernel_info(towr_gpu_handle h, int32_t kernel, const char** name, int32_t* n_tiles, int64_t* bytes_per_problem) {

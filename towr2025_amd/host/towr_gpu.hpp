@@ -80,6 +80,23 @@ class Engine {
   int EvalBatchDevice(int B, const double* X, int64_t ldx, double* G, int64_t ldg, double* V, int64_t ldv, void* stream) const {
     return towr_gpu_eval_batch_device(h_, B, X, ldx, G, ldg, V, ldv, 1, 1, stream);
   }
+  // the pattern as CSR (row_ptr[m + 1], col[nnz]) and by column (col_ptr[n + 1], row[nnz], csr_index[nnz])
+  void GetJacobianCsr(int64_t* row_ptr, int32_t* col) const { Check(towr_gpu_jac_csr(h_, row_ptr, col)); }
+  void GetJacobianCsc(int64_t* col_ptr, int32_t* row, int32_t* csr_index) const { Check(towr_gpu_jac_csc(h_, col_ptr, row, csr_index)); }
+  // per-problem products with evaluated Jacobians on the device (include/towr_gpu.h): Y_b = J_b p_b, Z_b (+)= J_b^T lam_b,
+  // and the fused evaluate-and-apply whose values never leave the handle's scratch; they return the status
+  int JacVecBatchDevice(int B, const double* V, int64_t ldv, const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream) const {
+    return towr_gpu_jac_vec_batch_device(h_, B, V, ldv, P, ldp, Y, ldy, stream);
+  }
+  int JacTVecBatchDevice(int B, const double* V, int64_t ldv, const double* LAM, int64_t ldl, double* Z, int64_t ldz, bool accumulate,
+                         void* stream) const {
+    return towr_gpu_jac_tvec_batch_device(h_, B, V, ldv, LAM, ldl, Z, ldz, accumulate ? 1 : 0, stream);
+  }
+  int EvalProductsBatchDevice(int B, const double* X, int64_t ldx, double* G, int64_t ldg, const double* LAM, int64_t ldl, double* Z,
+                              int64_t ldz, bool accumulate, const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream) const {
+    return towr_gpu_eval_products_batch_device(h_, B, X, ldx, G, ldg, LAM, ldl, Z, ldz, accumulate ? 1 : 0, P, ldp, Y, ldy, stream);
+  }
+  void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // page-lock caller memory for in-place host transfers (towr_gpu_register_host); returns the status
   int RegisterHost(void* p, size_t bytes) const { return towr_gpu_register_host(h_, p, (int64_t)bytes); }
   int UnregisterHost(void* p) const { return towr_gpu_unregister_host(h_, p); }

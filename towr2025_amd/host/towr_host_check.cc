@@ -13,6 +13,10 @@
 //   between calls, and the array after finalize_solution; then per-iteration timings (eval_g + eval_jac_g through the
 //   callbacks, and eval_jac_g alone) against the cached path (one fused evaluation into the page-locked cache + the
 //   nnz-value copy into IPOPT's array). Prints one line "zerocopy ok ..." or fails with a message.
+//        towr_host_check <cfg> --products [device] [problems]
+//   evaluates a batch of the configuration on the device, applies J p and J^T lam there (separate calls and the fused
+//   entry) and compares them with a host loop over the CSR pattern; prints "products ok ... largest |err|/bound x"
+//   and exits non-zero when a bound is exceeded.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -20,6 +24,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "nlp_formulation.hpp"
 #include "towr_gpu.hpp"
@@ -110,13 +116,84 @@ int zerocopy_check(const towr_problem_desc_t& d, int device, int iters) {
   return 0;
 }
 
+// --products: a batch of B perturbations of x0 evaluated on the device, both products applied there (the separate
+// calls and the fused entry, which must agree bit for bit), compared with a host loop over towr_gpu_jac_csr in long
+// double under the a-priori bound 2 gamma_k S (k terms, S = sum |v| |vec|, gamma_k = k u / (1 - k u), u = 2^-53).
+struct DevBuf {
+  double* p = nullptr;
+  size_t n = 0;
+  explicit DevBuf(size_t doubles) : n(doubles) { if (hipMalloc(reinterpret_cast<void**>(&p), sizeof(double) * std::max<size_t>(n, 1)) != hipSuccess) p = nullptr; }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  bool put(const std::vector<double>& h) { return p && hipMemcpy(p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) == hipSuccess; }
+  bool get(std::vector<double>& h) const { h.resize(n); return p && hipMemcpy(h.data(), p, sizeof(double) * n, hipMemcpyDeviceToHost) == hipSuccess; }
+};
+
+int products_check(const towr_problem_desc_t& d, int device, int B) {
+  Engine e(d, device);
+  const int n = e.GetNumberOfOptimizationVariables(), m = e.GetNumberOfConstraints();
+  const int64_t nnz = e.GetNumberOfJacobianNonzeros();
+  std::vector<int64_t> rp((size_t)m + 1), cp((size_t)n + 1);
+  std::vector<int32_t> col((size_t)nnz), crow((size_t)nnz), cidx((size_t)nnz);
+  e.GetJacobianCsr(rp.data(), col.data());
+  e.GetJacobianCsc(cp.data(), crow.data(), cidx.data());
+  const std::vector<double> x0 = e.GetVariableValues();
+  std::vector<double> X((size_t)B * n), P((size_t)B * n), LAM((size_t)B * m);
+  for (int b = 0; b < B; ++b) {
+    for (int i = 0; i < n; ++i) { X[(size_t)b * n + i] = x0[i] + 0.01 * (b + 1) * std::sin(0.37 * i + b); P[(size_t)b * n + i] = std::cos(1.3 * i + 0.7 * b); }
+    for (int i = 0; i < m; ++i) LAM[(size_t)b * m + i] = std::sin(0.9 * i + 1.1 * b) * (1 + i % 3);
+  }
+  DevBuf dX(X.size()), dP(P.size()), dL(LAM.size()), dG((size_t)B * m), dV((size_t)B * nnz), dY((size_t)B * m), dZ((size_t)B * n),
+      dG2((size_t)B * m), dY2((size_t)B * m), dZ2((size_t)B * n);
+  if (!dX.put(X) || !dP.put(P) || !dL.put(LAM) || !dG.p || !dV.p || !dY.p || !dZ.p || !dG2.p || !dY2.p || !dZ2.p) {
+    std::fprintf(stderr, "products: device allocation failed\n");
+    return 1;
+  }
+  e.SetProductsChunk(3);
+  if (e.EvalBatchDevice(B, dX.p, n, dG.p, m, dV.p, nnz, nullptr) || e.JacVecBatchDevice(B, dV.p, nnz, dP.p, n, dY.p, m, nullptr) ||
+      e.JacTVecBatchDevice(B, dV.p, nnz, dL.p, m, dZ.p, n, false, nullptr) ||
+      e.EvalProductsBatchDevice(B, dX.p, n, dG2.p, m, dL.p, m, dZ2.p, n, false, dP.p, n, dY2.p, m, nullptr) ||
+      hipDeviceSynchronize() != hipSuccess) {
+    std::fprintf(stderr, "products: %s\n", towr_gpu_last_error(e.handle()));
+    return 1;
+  }
+  std::vector<double> G, V, Y, Z, G2, Y2, Z2;
+  if (!dG.get(G) || !dV.get(V) || !dY.get(Y) || !dZ.get(Z) || !dG2.get(G2) || !dY2.get(Y2) || !dZ2.get(Z2)) return 1;
+  auto same = [](const std::vector<double>& a, const std::vector<double>& b) { return std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0; };
+  if (!same(G, G2) || !same(Y, Y2) || !same(Z, Z2)) { std::fprintf(stderr, "products: the fused entry differs from the separate calls\n"); return 1; }
+  const long double u = std::ldexp(1.0L, -53);
+  double worst = 0.0;
+  auto judge = [&](double got, long double ref, long double S, int64_t k) {
+    if (k == 0) { if (got != 0.0) worst = INFINITY; return; }
+    const long double bound = 2 * (k * u / (1 - k * u)) * S;
+    const long double err = std::fabs((long double)got - ref);
+    worst = std::max(worst, bound > 0 ? (double)(err / bound) : (err > 0 ? (double)INFINITY : 0.0));
+  };
+  for (int b = 0; b < B; ++b) {
+    const double *v = V.data() + (size_t)b * nnz, *p = P.data() + (size_t)b * n, *l = LAM.data() + (size_t)b * m;
+    for (int r = 0; r < m; ++r) {
+      long double s = 0, S = 0;
+      for (int64_t k = rp[r]; k < rp[r + 1]; ++k) { const long double t = (long double)v[k] * p[col[k]]; s += t; S += std::fabs(t); }
+      judge(Y[(size_t)b * m + r], s, S, rp[r + 1] - rp[r]);
+    }
+    for (int j = 0; j < n; ++j) {
+      long double s = 0, S = 0;
+      for (int64_t q = cp[j]; q < cp[j + 1]; ++q) { const long double t = (long double)v[cidx[q]] * l[crow[q]]; s += t; S += std::fabs(t); }
+      judge(Z[(size_t)b * n + j], s, S, cp[j + 1] - cp[j]);
+    }
+  }
+  std::printf("products %s n=%d m=%d nnz=%lld B=%d largest |err|/bound %.3f\n", worst <= 1.0 ? "ok" : "FAILED", n, m, (long long)nnz, B, worst);
+  return worst <= 1.0 ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 3) { std::fprintf(stderr, "usage: %s <anymal|biped|hopper> <out.bin> [device]\n", argv[0]); return 2; }
   const std::string cfg = argv[1];
   const int device = argc > 3 ? std::atoi(argv[3]) : -1;
-  const bool zc = std::string(argv[2]) == "--zerocopy";
+  const bool zc = std::string(argv[2]) == "--zerocopy", pr = std::string(argv[2]) == "--products";
   NlpFormulation f = (cfg == "anymal" || cfg == "anymal_costs" || cfg == "anymal_rotvec" || cfg == "anymal_gait") ? AnymalTrot()
                      : (cfg == "biped" || cfg == "biped_next") ? BipedWalk() : MonopedHopper();
   if (cfg == "anymal_gait") {   // BASELINE configs[3]: stairs, phase-duration optimisation
@@ -142,6 +219,7 @@ int main(int argc, char** argv) {
   try {
     const towr_problem_desc_t d = f.MakeDesc();
     if (zc) return zerocopy_check(d, device < 0 ? 0 : device, argc > 4 ? std::atoi(argv[4]) : 200);
+    if (pr) return products_check(d, device < 0 ? 0 : device, argc > 4 ? std::max(1, std::atoi(argv[4])) : 7);
     Engine e(d, device);
     NlpCallbacks nlp(e);
     int n = 0, m = 0, nnz = 0;

@@ -274,6 +274,63 @@ class TowrGpuProblem:
                 if t.shape[0] < B:
                     raise TowrGpuError(f"{name}: fewer rows than X")
 
+    # -------------------------------------------------------------------- products ------------
+    def jac_csc(self):
+        """The pattern by column (the transpose view of jac_csr): col_ptr (n + 1), row (nnz), csr_index (nnz)."""
+        cp = np.zeros(self.n + 1, dtype=np.int64)
+        r = np.zeros(self.nnz, dtype=np.int32)
+        k = np.zeros(self.nnz, dtype=np.int32)
+        self._check(self._lib.towr_gpu_jac_csc(self._h, capi.lptr(cp), capi.iptr(r), capi.iptr(k)))
+        return cp, r, k
+
+    def _check_rows(self, B, *ops):
+        """(tensor, name, min columns) operands of a B-problem product call."""
+        for t, name, cols in ops:
+            _check_tensor(t, name, cols, self.device)
+            if t.dim() != 2 or t.shape[0] < B:
+                raise TowrGpuError(f"{name}: expected a 2-D tensor of >= {B} rows")
+
+    @staticmethod
+    def _stream(stream, t):
+        import torch
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream(t.device)).cuda_stream)
+
+    def jac_vec_batch_device(self, V, P, Y, stream=None):
+        """Y[b] = J_b P[b] on torch HIP tensors: V (B, ldv >= nnz) CSR values, P (B, >= n), Y (B, >= m)."""
+        B = V.shape[0]
+        self._check_rows(B, (V, "V", self.nnz), (P, "P", self.n), (Y, "Y", self.m))
+        self._check(self._lib.towr_gpu_jac_vec_batch_device(
+            self._h, B, C.c_void_p(V.data_ptr()), V.stride(0), C.c_void_p(P.data_ptr()), P.stride(0),
+            C.c_void_p(Y.data_ptr()), Y.stride(0), self._stream(stream, V)))
+
+    def jac_tvec_batch_device(self, V, LAM, Z, accumulate=False, stream=None):
+        """Z[b] (+)= J_b^T LAM[b]: V (B, ldv >= nnz), LAM (B, >= m), Z (B, >= n); accumulate adds to what Z holds."""
+        B = V.shape[0]
+        self._check_rows(B, (V, "V", self.nnz), (LAM, "LAM", self.m), (Z, "Z", self.n))
+        self._check(self._lib.towr_gpu_jac_tvec_batch_device(
+            self._h, B, C.c_void_p(V.data_ptr()), V.stride(0), C.c_void_p(LAM.data_ptr()), LAM.stride(0),
+            C.c_void_p(Z.data_ptr()), Z.stride(0), int(bool(accumulate)), self._stream(stream, V)))
+
+    def eval_products_batch_device(self, X, G=None, LAM=None, Z=None, P=None, Y=None, accumulate=False, stream=None):
+        """Evaluate J_b at X[b] (and g into G when given), then Z[b] (+)= J_b^T LAM[b] and / or Y[b] = J_b P[b]; the
+        values stay in handle scratch, set_products_chunk problems at a time."""
+        B = X.shape[0]
+        ops = [(X, "X", self.n)]
+        ops += [(t, name, cols) for t, name, cols in ((G, "G", self.m), (LAM, "LAM", self.m), (Z, "Z", self.n),
+                                                       (P, "P", self.n), (Y, "Y", self.m)) if t is not None]
+        self._check_rows(B, *ops)
+
+        def ptr(t):
+            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
+        (gp, ldg), (lp, ldl), (zp, ldz), (pp, ldp), (yp, ldy) = ptr(G), ptr(LAM), ptr(Z), ptr(P), ptr(Y)
+        self._check(self._lib.towr_gpu_eval_products_batch_device(
+            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gp, ldg, lp, ldl, zp, ldz, int(bool(accumulate)),
+            pp, ldp, yp, ldy, self._stream(stream, X)))
+
+    def set_products_chunk(self, k: int):
+        """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
+        self._check(self._lib.towr_gpu_set_products_chunk(self._h, int(k)))
+
     def step_launches(self):
         """Kernel indices (see kernels()) that one evaluation launches: fusion groups, then the unfused classes."""
         buf = (C.c_int32 * 16)()
