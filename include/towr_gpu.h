@@ -111,11 +111,11 @@ enum towr_constraint_kind {
   TOWR_C_TERRAIN_HARD     = 12, /* TerrainConstraintHard       ee; T; dt              (terrain_constraint_hard.cc:35-132)       */
   TOWR_C_EE_LINEAR        = 13, /* EELinearConstraint          T; dt; ip[0] = target (0 motion, 1 ang), ip[1] = deriv (0 pos,
                                      1 vel), ip[2] = n_terms (<= 6), ip[3 + i] = ee_i * 3 + dim_i; p[i] = coeff_i;
-                                     (ee_linear_constraint.cc:5-48; the bound tolerance is setup data, not used here)  */
+                                     (ee_linear_constraint.cc:5-48; the bound tolerance is side data TOWR_DATA_BOUNDS)  */
   TOWR_C_LINEAR_EQ        = 14  /* LinearEqualityConstraint    g = M x_set (linear_constraint.cc:35-80): ip[0] = variable set
                                      (index in AddVariableSet order), ip[1] = rows of M; M itself is side data
                                      TOWR_DATA_LINEAR_M (towr_gpu_create_ex). Jacobian = M.sparseView(): the nonzeros of M.
-                                     The offset v only enters the bounds (-v), which stay with the caller            */
+                                     The offset v only enters the bounds (-v): side data TOWR_DATA_BOUNDS            */
 };
 
 /* Role of a constraint set in the description:
@@ -205,9 +205,16 @@ typedef struct towr_gpu_handle_s* towr_gpu_handle;
 enum towr_data_kind {
   TOWR_DATA_LINEAR_M    = 0, /* index = constraint (TOWR_C_LINEAR_EQ); count = rows * n_set; data = M row-major
                                 (LinearEqualityConstraint::M_, linear_constraint.cc:35-45)                       */
-  TOWR_DATA_SOFT_BOUNDS = 1  /* index = cost term (TOWR_COST_SOFT); count = 2 * rows of the wrapped set;
+  TOWR_DATA_SOFT_BOUNDS = 1, /* index = cost term (TOWR_COST_SOFT); count = 2 * rows of the wrapped set;
                                 data = lower[0..rows-1], upper[0..rows-1] = the wrapped set's GetBounds(), from
                                 which the engine forms b = (upper + lower) / 2 as SoftConstraint's ctor does  */
+  TOWR_DATA_BOUNDS      = 2  /* OPTIONAL; index = constraint; what towr_gpu_constraint_bounds needs beyond the POD:
+                                TOWR_C_EE_LINEAR: count = 1, the tolerance (ee_linear_constraint.cc:32-35);
+                                TOWR_C_LINEAR_EQ: count = rows, the offset v (linear_constraint.cc:53-64);
+                                TOWR_C_RANGE_OF_MOTION: count = 1..3, Parameters::rom_swing_relax_dims_ as doubles
+                                (0, 1 or 2; nlp_formulation.cc:433-435); absent = no relaxation.
+                                A handle created without them evaluates as ever; only the bounds calls then fail
+                                (TOWR_ERR_INVALID) when it holds an EELinear or LinearEquality set                 */
 };
 typedef struct {
   int32_t       kind;    /* towr_data_kind                                                          */
@@ -247,6 +254,20 @@ int towr_gpu_initial_x(towr_gpu_handle h, double* x0);
 int towr_gpu_initial_x_for(towr_gpu_handle h, const towr_init_t* init, const towr_terrain_t* terrain, double* x0);
 /* Column range of variable set i (AddVariableSet order): kind, ee, first column, size.          */
 int towr_gpu_varset_info(towr_gpu_handle h, int32_t i, int32_t* kind, int32_t* ee, int32_t* col0, int32_t* n);
+
+/* Row range of constraint set i (AddConstraintSet order): kind, ee, first row, rows. The hard sets tile [0, m) in
+ * order; a TOWR_ROLE_SOFT set is not part of g and reports rows = 0.                              */
+int towr_gpu_constraint_info(towr_gpu_handle h, int32_t i, int32_t* kind, int32_t* ee, int32_t* row0, int32_t* rows);
+/* The constraint bounds in ifopt row order, lower[m] and upper[m]: every set's GetBounds() with the reference's
+ * arithmetic and literals (what IpoptAdapter::get_bounds_info reports for g). Unbounded sides are ifopt's
+ * +-1.0e20, not IEEE infinity. Only a node-based TorqueConstraint's third row, (-L, L) with L = k mu (f . n)
+ * (torque_constraint.cc:103-127), depends on x and the terrain: towr_gpu_constraint_bounds uses the description's
+ * x0 and terrain; _for those of another instance sharing the layout (as towr_gpu_initial_x_for) and differs on
+ * those rows only. TOWR_ERR_INVALID (the message names the set) when an EELinear or LinearEquality set's
+ * TOWR_DATA_BOUNDS entry was not given at creation. Host calls; they work on layout-only handles.   */
+int towr_gpu_constraint_bounds(towr_gpu_handle h, double* lower /* m */, double* upper /* m */);
+int towr_gpu_constraint_bounds_for(towr_gpu_handle h, const towr_init_t* init, const towr_terrain_t* terrain,
+                                   double* lower, double* upper);
 
 /* ---- single-problem host callbacks (what IpoptAdapter calls) -------------------------------- */
 /* g = ifopt Problem::EvalConstraints(x)          (IpoptAdapter::eval_g)                         */
@@ -377,6 +398,44 @@ int towr_gpu_eval_products_batch_device(towr_gpu_handle h, int32_t B, const doub
                                         const double* LAM, int64_t ldl, double* Z, int64_t ldz, int32_t accumulate,
                                         const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream);
 int towr_gpu_set_products_chunk(towr_gpu_handle h, int32_t problems);   /* 0 = automatic */
+
+/* ---- feasibility of a batch on the device: violation summaries and augmented-Lagrangian multipliers ---------- */
+/* Per problem b and row i, with g = G[b*ldg + i], l = GL[b*ldb + i], u = GU[b*ldb + i] (DEVICE pointers; GL = GU = NULL:
+ * the handle's description bounds, uploaded synchronously by the first such call; ldb = 0: one bounds row shared by
+ * all problems; else ldb >= m):
+ *   a side counts only if l > -1e19, respectively u < 1e19 (IPOPT's infinity threshold; IEEE infinities are safe);
+ *   violation  v_i = max(l - g, g - u, 0) over the sides that count; a NaN g gives a NaN v_i;
+ *   multiplier (LAMP != NULL, rho > 0; LAM NULL = zero multipliers): t = g + lam_i / rho, c = t clamped to the sides
+ *              that count, r_i = t - c, LAMP[b*ldlp + i] = rho r_i (Rockafellar's augmented Lagrangian for
+ *              l <= g <= u: grad_x = grad f + J^T lam+).
+ * SUM[b*lds + ...] holds 4 + n_constraints doubles (lds >= that): [0] max v_i; [1] sum v_i; [2] the lowest row
+ * attaining [0] as a double (-1.0 when [0] == 0; the first NaN row when a row is NaN); [3] phi = sum (0.5 rho r_i^2
+ * - 0.5 lam_i^2 / rho), 0.0 without LAMP; [4 + s] max v_i over constraint set s in description order (soft sets 0.0).
+ * A NaN row makes [0], [1] and its own set's entry NaN and leaves the other sets' entries untouched.
+ * One block per problem; every sum is one fixed tree (lane-strided partials, a shuffle tree, a fixed-order combine
+ * across waves; no floating-point atomics), so problem b's outputs are a function of its own operands alone: the
+ * same bits for any B, any position, any stream, run to run. Nothing beyond m (G, LAM, LAMP) or 4 + n_constraints
+ * (SUM) is read or written. No handle scratch is used and the kept Jacobian is not dropped. TOWR_ERR_INVALID before
+ * anything runs for: NULL G or SUM, lds < 4 + n_constraints, ldg / ldl / ldlp < m, 0 < ldb < m, rho <= 0 (or NaN)
+ * with LAMP, only one of GL / GU.                                                                                */
+int towr_gpu_residual_batch_device(towr_gpu_handle h, int32_t B, const double* G, int64_t ldg,
+                                   const double* GL, const double* GU, int64_t ldb,
+                                   const double* LAM, int64_t ldl, double rho,
+                                   double* LAMP, int64_t ldlp, double* SUM, int64_t lds, void* stream);
+
+/* Fused, chunked merit-and-gradient: per chunk of problems (towr_gpu_set_products_chunk, automatic as for
+ * towr_gpu_eval_products_batch_device) evaluate g and J at X into handle scratch, run the residual kernel, then
+ * Z_b (+)= J_b^T lam+_b. G and LAMP are optional outputs (NULL: they live in handle scratch only); SUM and Z are
+ * required, rho > 0. Bit-identical to towr_gpu_eval_batch_device, towr_gpu_residual_batch_device (with LAMP) and
+ * towr_gpu_jac_tvec_batch_device in sequence, whatever the chunk. With accumulate = 1 on top of
+ * towr_gpu_eval_cost_batch_device's GRAD, Z is the augmented Lagrangian's gradient and F + SUM[3] its value. Batch
+ * terrains, the cross-stream scratch rule and the kept Jacobian as for towr_gpu_eval_products_batch_device.       */
+int towr_gpu_eval_auglag_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx,
+                                      const double* GL, const double* GU, int64_t ldb,
+                                      const double* LAM, int64_t ldl, double rho,
+                                      double* G, int64_t ldg, double* LAMP, int64_t ldlp,
+                                      double* SUM, int64_t lds,
+                                      double* Z, int64_t ldz, int32_t accumulate, void* stream);
 
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the

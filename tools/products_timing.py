@@ -1,7 +1,11 @@
 """Jacobian-product timings on the GPU box (tool, not product): per call, on one box in one session,
   (a) eval_batch_device (g + J) alone — the yardstick on that box;
   (b) jac_vec_batch_device; (c) jac_tvec_batch_device (overwrite);
-  (d) eval_products_batch_device (g, J^T lam and J p) at the automatic chunk and at chunks of 128, 512 and B,
+  (d) eval_products_batch_device (g, J^T lam and J p) at the automatic chunk and at chunks of 128, 512 and B;
+  (e) residual_batch_device (summary and lam+, the handle's bounds): rate = 8 (3 m + 4 + n_constraints) B / time, the
+      bytes of G + LAM + LAMP + SUM, beside (f) a device-to-device torch copy moving the same bytes (half read, half
+      written);
+  (g) eval_auglag_batch_device (g and lam+ in scratch) beside the sum of its parts a + e + c from the same session,
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -48,6 +52,12 @@ def run(name, desc, B):
     P = torch.randn((B, ld(p.n)), dtype=torch.float64, device=dev)
     LAM = torch.randn((B, ld(p.m)), dtype=torch.float64, device=dev)
     Y, Z = torch.empty_like(LAM), torch.empty_like(P)
+    ns = p.desc.n_constraints
+    LAMP, SUM = torch.empty_like(LAM), torch.empty((B, ld(4 + ns)), dtype=torch.float64, device=dev)
+    bytes_res = 8 * (3 * p.m + 4 + ns) * B
+    src = torch.randn(bytes_res // 16, dtype=torch.float64, device=dev)
+    dst = torch.empty_like(src)
+    rho = 10.0
 
     def fused(chunk):
         def f():
@@ -58,7 +68,11 @@ def run(name, desc, B):
                 ("b jac_vec", lambda: p.jac_vec_batch_device(V, P, Y, stream=stream)),
                 ("c jac_tvec", lambda: p.jac_tvec_batch_device(V, LAM, Z, stream=stream)),
                 ("d fused chunk auto", fused(0)), ("d fused chunk 128", fused(128)), ("d fused chunk 512", fused(512)),
-                (f"d fused chunk B={B}", fused(B))]
+                (f"d fused chunk B={B}", fused(B)),
+                ("e residual", lambda: p.residual_batch_device(G, SUM, LAM=LAM, rho=rho, LAMP=LAMP, stream=stream)),
+                ("f copy, same bytes", lambda: dst.copy_(src)),
+                ("g auglag fused auto", lambda: (p.set_products_chunk(0),
+                                                 p.eval_auglag_batch_device(X, SUM, Z, LAM=LAM, rho=rho, stream=stream)))]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
         for _ in range(3):
             fn()
@@ -78,8 +92,12 @@ def run(name, desc, B):
     for k, _ in variants:
         t = times[k]
         med = statistics.median(t)
-        rate = f"  {bytes_prod / (med * 1e-3) / 1e12:.2f} TB/s = {100 * bytes_prod / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if k[0] in "bc" else ""
+        nbytes = bytes_prod if k[0] in "bc" else bytes_res if k[0] in "ef" else 0
+        rate = f"  {nbytes / (med * 1e-3) / 1e12:.2f} TB/s = {100 * nbytes / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if nbytes else ""
         print(f"  {k:22s} {med:.4f} ms  (min {min(t):.4f} max {max(t):.4f}){rate}", flush=True)
+    parts = sum(statistics.median(times[k]) for k in ("a eval_batch_device", "e residual", "c jac_tvec"))
+    print(f"  residual bytes {bytes_res / 1e9:.3f} GB; auglag parts a + e + c {parts:.4f} ms, fused / parts "
+          f"{statistics.median(times['g auglag fused auto']) / parts:.3f}", flush=True)
     p.set_products_chunk(0)
 
 

@@ -220,6 +220,30 @@ struct JpChunk { int32_t rs0, rns, rnl, cs0, cns, cnl, reserved[2]; };
 struct VarSetInfo { int kind, ee, col0, n; };
 struct ConsInfo { int kind, ee, row0, rows; };
 
+// Constraint bounds (towr_gpu_constraint_bounds). ifopt's constants: inf = 1.0e20, NoBound = (-inf, +inf),
+// BoundGreaterZero = (0, +inf), BoundSmallerZero = (-inf, 0); the literal, not IEEE infinity.
+constexpr double kBoundInf = 1.0e20;
+// A node TorqueConstraint's third row, (-L, L) with L = k mu (f . n) (torque_constraint.cc:103-127): the only bounds
+// that depend on x and the terrain. pcol = the x columns of the foot position (x, y) and fcol = of the force at the
+// start of the node's phase (-1: a constant node value, 0.0).
+struct TqBound { int32_t row, pcol[2], fcol[3]; double k; };
+
+// The residual kernel (resid.hip): per-problem violation summary of G against (GL, GU) and, with LAMP, the augmented
+// Lagrangian's multiplier update; one block of kResBlock threads per problem. set_row0[s] .. set_row0[s + 1] are the
+// rows of constraint set s (description order; a soft set's range is empty). ldb = 0: one bounds row for all problems.
+constexpr int kResBlock = 256;
+struct ResArgs {
+  const double* G; int64_t ldg;
+  const double *GL, *GU; int64_t ldb;
+  const double* LAM; int64_t ldl;
+  double* LAMP; int64_t ldlp;
+  double* SUM; int64_t lds;
+  const int32_t* set_row0;   // n_sets + 1
+  double rho;
+  int32_t m, n_sets;
+};
+const void* res_kernel();
+
 struct Layout {
   int n = 0, m = 0;
   int64_t nnz = 0;
@@ -324,8 +348,16 @@ struct Layout {
   std::vector<JpChunk> jp_chunks;
   std::vector<int32_t> jp_empty_rows;
   int32_t jp_long = kJpLongDefault;   // segments of at least this many entries are summed by a wave
+  // The constraint bounds in ifopt row order (build_bounds: every set's GetBounds restated), at the description's
+  // x0 and terrain; tq_bounds lists the rows that torque_bounds re-evaluates for another x / terrain. bounds_err is
+  // non-empty when a set's bounds need side data (TOWR_DATA_BOUNDS) that was not given: the bounds calls then fail.
+  std::vector<double> g_lower, g_upper;
+  std::vector<TqBound> tq_bounds;
+  std::string bounds_err;
 };
-void build_jprod(Layout& L);   // fills the members above from row_ptr / col
+void build_jprod(Layout& L);   // fills the jp_ / csc members above from row_ptr / col
+// the (-L, L) rows of the node TorqueConstraints at x on terrain `ter`, written into lower / upper (m doubles each)
+void torque_bounds(const Layout& L, const double* x, const towr_terrain_t& ter, double* lower, double* upper);
 // the product kernels (jprod.hip): one block of kJpBlock threads per problem; Vec = P (ldvec >= n) and Out = Y for
 // J p, Vec = LAM (>= m) and Out = Z for J^T lam; the tables are the device copies of the members above
 struct JpArgs {

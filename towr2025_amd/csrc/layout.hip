@@ -1084,6 +1084,146 @@ void build_jprod(Layout& L) {
   }
 }
 
+void torque_bounds(const Layout& L, const double* x, const towr_terrain_t& ter, double* lower, double* upper) {
+  for (const TqBound& tb : L.tq_bounds) {
+    double p[2], f[3], n[3];
+    for (int e = 0; e < 2; ++e) p[e] = tb.pcol[e] >= 0 ? x[tb.pcol[e]] : 0.0;
+    for (int e = 0; e < 3; ++e) f[e] = tb.fcol[e] >= 0 ? x[tb.fcol[e]] : 0.0;
+    ter_nbasis(ter, 0, p[0], p[1], n);
+    const double f_n = dot3(f, n);
+    const double tz_limit = tb.k * ter.friction_coeff * f_n;
+    lower[tb.row] = -tz_limit;
+    upper[tb.row] = tz_limit;
+  }
+}
+
+// The constraint bounds, every set's GetBounds / UpdateBoundsAtInstance restated over the work items (one item per
+// instant or node, in row order): the same arithmetic and literals as the reference. Side data TOWR_DATA_BOUNDS
+// (index = constraint) carries what the description does not: EELinear's tolerance, LinearEquality's offset v, and
+// RangeOfMotion's swing-relaxed dims (nlp_formulation.cc:433-435).
+int build_bounds(const towr_problem_desc_t& d, int n_data, const towr_data_t* data, const std::vector<NodeSet>& sets, Layout& L,
+                 std::string& err) {
+  L.g_lower.assign((size_t)L.m, 0.0);
+  L.g_upper.assign((size_t)L.m, 0.0);
+  L.tq_bounds.clear();
+  L.bounds_err.clear();
+  std::vector<int> row_cons((size_t)L.m, -1);
+  for (int ci = 0; ci < (int)L.cons.size(); ++ci)
+    for (int r = 0; r < L.cons[ci].rows; ++r) row_cons[(size_t)L.cons[ci].row0 + r] = ci;
+  for (int ci = 0; ci < d.n_constraints; ++ci) {   // the side data's shape
+    const towr_data_t* bd = find_data(n_data, data, TOWR_DATA_BOUNDS, ci);
+    const towr_constraint_t& c = d.constraints[ci];
+    const bool soft = c.role == TOWR_ROLE_SOFT;
+    const char* what = nullptr;
+    if (c.kind == TOWR_C_EE_LINEAR) {
+      if (bd && (bd->count != 1 || !bd->data)) what = "EELinear: side data TOWR_DATA_BOUNDS must hold 1 double (the tolerance)";
+      if (!bd && !soft && L.bounds_err.empty())
+        L.bounds_err = "constraint set " + std::to_string(ci) + " (EELinear): its bounds need the tolerance (side data TOWR_DATA_BOUNDS)";
+    } else if (c.kind == TOWR_C_LINEAR_EQ) {
+      if (bd && (bd->count != c.ip[1] || (c.ip[1] > 0 && !bd->data))) what = "LinearEquality: side data TOWR_DATA_BOUNDS must hold one offset per row";
+      if (!bd && !soft && L.bounds_err.empty())
+        L.bounds_err = "constraint set " + std::to_string(ci) + " (LinearEquality): its bounds need the offset v (side data TOWR_DATA_BOUNDS)";
+    } else if (c.kind == TOWR_C_RANGE_OF_MOTION) {
+      if (bd && (bd->count < 1 || bd->count > 3 || !bd->data)) what = "RangeOfMotion: side data TOWR_DATA_BOUNDS must hold 1..3 relaxed dims";
+      for (int64_t q = 0; bd && !what && q < bd->count; ++q)
+        if (!(bd->data[q] == 0.0 || bd->data[q] == 1.0 || bd->data[q] == 2.0)) what = "RangeOfMotion: a relaxed dim must be 0, 1 or 2";
+    } else if (bd) {
+      what = "side data TOWR_DATA_BOUNDS given for a constraint kind that takes none";
+    }
+    if (what) { err = what; return TOWR_ERR_INVALID; }
+  }
+  auto set = [&](int row, double lo, double up) { L.g_lower[(size_t)row] = lo; L.g_upper[(size_t)row] = up; };
+  for (const ItemDesc& it : L.items) {
+    const int r0 = it.row0;
+    const int ci = row_cons[(size_t)r0];
+    const towr_constraint_t& c = d.constraints[ci];
+    const towr_data_t* bd = find_data(n_data, data, TOWR_DATA_BOUNDS, ci);
+    switch (it.type) {
+      case IT_DYN:     // dynamic_constraint.cc:71-75
+        for (int r = 0; r < 6; ++r) set(r0 + r, 0.0, 0.0);
+        break;
+      case IT_ROM: {   // range_of_motion_constraint.cc:86-103
+        double tl;
+        const int ph = seg_lookup(d.phase_durations[it.ee], d.n_phases[it.ee], it.t, &tl);   // PhaseDurations::IsContactPhase
+        const bool contact = ph % 2 == 0 ? d.contact_at_start[it.ee] != 0 : d.contact_at_start[it.ee] == 0;
+        for (int dim = 0; dim < 3; ++dim) {
+          bool relax = false;
+          for (int64_t q = 0; bd && q < bd->count; ++q) relax = relax || (int)bd->data[q] == dim;
+          if (relax && !contact) { set(r0 + dim, -kBoundInf, kBoundInf); continue; }
+          const double nom = 0.0 + d.robot.nominal_stance[it.ee][dim];   // Bounds b; b += nominal
+          set(r0 + dim, nom + d.robot.min_dev[it.ee][dim], nom + d.robot.max_dev[it.ee][dim]);
+        }
+        break;
+      }
+      case IT_FDISC: case IT_FNODE:   // force_constraint.cc:91-105, force_constraint_discretized.cc:120-129
+        set(r0, 0.0, c.p[0]);
+        set(r0 + 1, -kBoundInf, 0.0);
+        set(r0 + 2, 0.0, kBoundInf);
+        set(r0 + 3, -kBoundInf, 0.0);
+        set(r0 + 4, 0.0, kBoundInf);
+        break;
+      case IT_TERR:    // terrain_constraint.cc:76-91
+        if (sets[2 + 4 * it.ee].is_constant_node(it.a0)) set(r0, 0.0, 0.0);
+        else set(r0, c.p[0], c.p[1]);
+        break;
+      case IT_THARD: case IT_BHGT:   // terrain_constraint_hard.cc:76-83, base_height_constraint.cc:73-88
+        set(r0, 0.0, 1e20);
+        break;
+      case IT_BMOT:    // base_motion_constraint.cc:38-73: rows AX AY AZ LX LY LZ
+        for (int r = 0; r < 6; ++r) set(r0 + r, -kBoundInf, kBoundInf);
+        set(r0 + 0, c.p[0], c.p[1]);
+        set(r0 + 1, c.p[2], c.p[3]);
+        set(r0 + 5, c.p[4], c.p[5]);
+        break;
+      case IT_SACC:
+        for (int r = 0; r < 3; ++r) set(r0 + r, 0.0, 0.0);
+        break;
+      case IT_SWING:
+        for (int r = 0; r < 4; ++r) set(r0 + r, 0.0, 0.0);
+        break;
+      case IT_TDUR:    // total_duration_constraint.cc:57-64
+        set(r0, 0.1, c.T - 0.2);
+        break;
+      case IT_TQDISC:  // torque_constraint_discretized.cc:129-136
+        set(r0, c.p[0], c.p[1]);
+        set(r0 + 1, c.p[2], c.p[3]);
+        set(r0 + 2, -kBoundInf, 0.0);
+        set(r0 + 3, -kBoundInf, 0.0);
+        break;
+      case IT_TQNODE: {   // torque_constraint.cc:103-127: the third row follows x (torque_bounds)
+        set(r0, c.p[0], c.p[1]);
+        set(r0 + 1, c.p[2], c.p[3]);
+        const NodeSet& tv = sets[5 + 4 * it.ee];
+        const NodeSet& fv = sets[4 + 4 * it.ee];
+        const int fn = fv.node_at_start_of_phase(tv.phase_of(it.a0));
+        if (fn < 0) { err = "torque node phase has no force node"; return TOWR_ERR_INVALID; }
+        TqBound tb{};
+        tb.row = r0 + 2;
+        tb.k = c.p[4];
+        const int ms = 2 + 4 * it.ee, fs = 4 + 4 * it.ee;
+        for (int e = 0; e < 2; ++e) tb.pcol[e] = L.nodecol[(size_t)(L.spl[ms].node_off + it.a1) * 6 + kPos * 3 + e];
+        for (int e = 0; e < 3; ++e) tb.fcol[e] = L.nodecol[(size_t)(L.spl[fs].node_off + fn) * 6 + kPos * 3 + e];
+        L.tq_bounds.push_back(tb);
+        break;
+      }
+      case IT_EELIN: {   // ee_linear_constraint.cc:32-35
+        const double tol = bd ? bd->data[0] : 0.0;
+        set(r0, -tol, tol);
+        break;
+      }
+      case IT_LINEQ: {   // linear_constraint.cc:53-64
+        const double v = bd ? bd->data[it.k] : 0.0;
+        set(r0, -v, -v);
+        break;
+      }
+      case IT_NONE: break;
+      default: err = "internal: work item without bounds"; return TOWR_ERR_INVALID;
+    }
+  }
+  torque_bounds(L, L.x0.data(), L.terrain, L.g_lower.data(), L.g_upper.data());
+  return TOWR_OK;
+}
+
 void build_misc_xspan(Layout& L);
 int build_layout(const towr_problem_desc_t& d, Layout& L, std::string& err) { return build_layout_ex(d, 0, nullptr, L, err); }
 
@@ -1376,6 +1516,7 @@ int build_layout_ex(const towr_problem_desc_t& d, int n_data, const towr_data_t*
     L.cons.push_back(info);
   }
   L.m = row;
+  if (int rc = build_bounds(d, n_data, data, sets, L, err)) return rc;
 
   // ---- segment table: the reference's GetLocalTime scan for every (timed instance, spline)
   {

@@ -165,6 +165,13 @@ struct towr_gpu_handle_s {
   double* d_pv = nullptr;
   int64_t pv_cap = 0;
   int32_t products_chunk = 0;
+  // Residuals (resid.hip): the device copies of the constraint sets' row ranges and of the description bounds,
+  // uploaded by the first residual call on the handle, and the fused entry's g / lam+ scratch (a chunk of problems)
+  bool res_ready = false;
+  int32_t* d_set_row0 = nullptr;
+  double *d_blo = nullptr, *d_bup = nullptr;
+  double *d_rg = nullptr, *d_rl = nullptr;
+  int64_t rg_cap = 0, rl_cap = 0;
 };
 
 namespace {
@@ -1432,6 +1439,8 @@ int towr_gpu_destroy(towr_gpu_handle h) {
   if (h->device >= 0) {
     for (void* p : h->d_jp) if (p) (void)hipFree(p);
     if (h->d_pv) (void)hipFree(h->d_pv);
+    void* res[] = {h->d_set_row0, h->d_blo, h->d_bup, h->d_rg, h->d_rl};
+    for (void* p : res) if (p) (void)hipFree(p);
   }
   void* host[] = {h->h_x, h->h_g, h->h_v};
   for (void* p : host) if (p) (void)hipHostFree(p);
@@ -1486,6 +1495,39 @@ int towr_gpu_initial_x_for(towr_gpu_handle h, const towr_init_t* init, const tow
   std::string err;
   if (int rc = initial_x_for(h->L.desc, *init, *terrain, v, err)) return fail(h, rc, err);
   std::memcpy(x0, v.data(), sizeof(double) * v.size());
+  return TOWR_OK;
+}
+
+int towr_gpu_constraint_info(towr_gpu_handle h, int32_t i, int32_t* kind, int32_t* ee, int32_t* row0, int32_t* rows) {
+  if (!h || i < 0 || i >= (int32_t)h->L.cons.size()) return fail(h, TOWR_ERR_INVALID, "bad constraint set index");
+  const ConsInfo& c = h->L.cons[i];
+  if (kind) *kind = h->L.desc.constraints[i].kind;   // (a soft set's ConsInfo holds no kind)
+  if (ee) *ee = c.ee;
+  if (row0) *row0 = c.row0;
+  if (rows) *rows = c.rows;
+  return TOWR_OK;
+}
+
+int towr_gpu_constraint_bounds(towr_gpu_handle h, double* lower, double* upper) {
+  if (!h || !lower || !upper) return fail(h, TOWR_ERR_INVALID, "null argument");
+  const Layout& L = h->L;
+  if (!L.bounds_err.empty()) return fail(h, TOWR_ERR_INVALID, L.bounds_err);
+  if (L.m) {
+    std::memcpy(lower, L.g_lower.data(), sizeof(double) * L.g_lower.size());
+    std::memcpy(upper, L.g_upper.data(), sizeof(double) * L.g_upper.size());
+  }
+  return TOWR_OK;
+}
+
+int towr_gpu_constraint_bounds_for(towr_gpu_handle h, const towr_init_t* init, const towr_terrain_t* terrain, double* lower,
+                                   double* upper) {
+  if (!h || !init || !terrain) return fail(h, TOWR_ERR_INVALID, "null argument");
+  if (int rc = towr_gpu_constraint_bounds(h, lower, upper)) return rc;
+  if (h->L.tq_bounds.empty()) return TOWR_OK;
+  std::vector<double> x;
+  std::string err;
+  if (int rc = initial_x_for(h->L.desc, *init, *terrain, x, err)) return fail(h, rc, err);
+  torque_bounds(h->L, x.data(), *terrain, lower, upper);
   return TOWR_OK;
 }
 
@@ -1813,6 +1855,114 @@ int towr_gpu_eval_products_batch_device(towr_gpu_handle h, int32_t B, const doub
     if (rc == TOWR_OK && P) rc = launch_product(h, false, cb, h->d_pv, ldv, P + (int64_t)c0 * ldp, ldp, Y + (int64_t)c0 * ldy, ldy, 0, s);
   }
   const int rr = scratch_release(h, s);   // (also after a failure: what was queued still orders the scratch)
+  return rc ? rc : rr;
+}
+
+// ---- residuals (resid.hip) ---------------------------------------------------------------------------------------
+// The residual kernel's tables, on the first residual call of the handle (synchronous copies, as products_ready): the
+// sets' row ranges and, when every set's bounds are known, the description bounds.
+static int residual_ready(towr_gpu_handle h) {
+  if (h->res_ready) return TOWR_OK;
+  const Layout& L = h->L;
+  std::vector<int32_t> row0;
+  for (const ConsInfo& c : L.cons) row0.push_back(c.row0);
+  row0.push_back(L.m);
+  int32_t* d_row0 = nullptr;
+  double *lo = nullptr, *up = nullptr;
+  int r = upload(h, &d_row0, row0);
+  if (!r && L.bounds_err.empty()) (void)((r = upload(h, &lo, L.g_lower)) || (r = upload(h, &up, L.g_upper)));
+  if (r) {
+    void* all[] = {d_row0, lo, up};
+    for (void* p : all) if (p) (void)hipFree(p);
+    return r;
+  }
+  h->d_set_row0 = d_row0; h->d_blo = lo; h->d_bup = up;
+  h->res_ready = true;
+  return TOWR_OK;
+}
+
+// the argument checks the residual entry and the fused entry share (before anything runs)
+static int residual_args(towr_gpu_handle h, const double* GL, const double* GU, int64_t ldb, const double* LAM, int64_t ldl,
+                         double rho, bool lamp, int64_t ldlp, const double* SUM, int64_t lds) {
+  const Layout& L = h->L;
+  if (!SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
+  if (lds < 4 + (int64_t)L.cons.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 4 + n_constraints");
+  if ((GL == nullptr) != (GU == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of GL / GU given");
+  if (GL && ldb != 0 && ldb < L.m) return fail(h, TOWR_ERR_INVALID, "ldb must be 0 (shared bounds) or >= m");
+  if (!GL && !L.bounds_err.empty()) return fail(h, TOWR_ERR_INVALID, L.bounds_err);
+  if (lamp && !(rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 with LAMP");
+  if (lamp && ldlp < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAMP smaller than m");
+  if (lamp && LAM && ldl < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAM smaller than m");
+  return TOWR_OK;
+}
+
+static int launch_residual(towr_gpu_handle h, int B, const double* G, int64_t ldg, const double* GL, const double* GU, int64_t ldb,
+                           const double* LAM, int64_t ldl, double rho, double* LAMP, int64_t ldlp, double* SUM, int64_t lds,
+                           hipStream_t s) {
+  ResArgs a{};
+  a.G = G; a.ldg = ldg;
+  a.GL = GL ? GL : h->d_blo; a.GU = GL ? GU : h->d_bup; a.ldb = GL ? ldb : 0;
+  a.LAM = LAMP ? LAM : nullptr; a.ldl = ldl; a.LAMP = LAMP; a.ldlp = ldlp; a.SUM = SUM; a.lds = lds;
+  a.set_row0 = h->d_set_row0; a.rho = LAMP ? rho : 1.0; a.m = h->L.m; a.n_sets = (int32_t)h->L.cons.size();
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(res_kernel(), dim3((unsigned)B), dim3(kResBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+int towr_gpu_residual_batch_device(towr_gpu_handle h, int32_t B, const double* G, int64_t ldg, const double* GL, const double* GU,
+                                   int64_t ldb, const double* LAM, int64_t ldl, double rho, double* LAMP, int64_t ldlp,
+                                   double* SUM, int64_t lds, void* stream) {
+  if (!h || B < 0 || !G) return fail(h, TOWR_ERR_INVALID, "bad argument (null G or B < 0)");
+  if (ldg < h->L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of G smaller than m");
+  if (int rc = residual_args(h, GL, GU, ldb, LAM, ldl, rho, LAMP != nullptr, ldlp, SUM, lds)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = residual_ready(h)) return rc;
+  return launch_residual(h, B, G, ldg, GL, GU, ldb, LAM, ldl, rho, LAMP, ldlp, SUM, lds, reinterpret_cast<hipStream_t>(stream));
+}
+
+// As towr_gpu_eval_products_batch_device: a chunk of problems at a time through the handle's scratch (the values in
+// d_pv; g and lam+ in d_rg / d_rl when the caller does not want them), the three launches of a chunk back to back on
+// the caller's stream.
+int towr_gpu_eval_auglag_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* GL, const double* GU,
+                                      int64_t ldb, const double* LAM, int64_t ldl, double rho, double* G, int64_t ldg,
+                                      double* LAMP, int64_t ldlp, double* SUM, int64_t lds, double* Z, int64_t ldz,
+                                      int32_t accumulate, void* stream) {
+  if (!h || B < 0 || !X || !Z) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or Z, or B < 0)");
+  const Layout& L = h->L;
+  if (ldx < L.n || ldz < L.n || (G && ldg < L.m)) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X, Z) / m (G)");
+  if (int rc = residual_args(h, GL, GU, ldb, LAM, ldl, rho, true, LAMP ? ldlp : L.m, SUM, lds)) return rc;
+  if (int rc = bind(h)) return rc;
+  const towr_terrain_t* ter;
+  int per;
+  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
+  if (B == 0) return TOWR_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = products_ready(h)) return rc;
+  if (int rc = residual_ready(h)) return rc;
+  constexpr int64_t kAutoBytes = int64_t(2) << 30;   // the automatic chunk of towr_gpu_eval_products_batch_device
+  const int64_t ldv = std::max<int64_t>(16, (L.nnz + 15) & ~int64_t(15));
+  const int64_t ldr = std::max<int64_t>(16, ((int64_t)L.m + 15) & ~int64_t(15));
+  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ldv));
+  const int64_t parts = (B + cap - 1) / cap;
+  const int C = (int)std::min<int64_t>(B, h->products_chunk > 0 ? h->products_chunk : (B + parts - 1) / parts);
+  if (int rc = scratch_acquire(h, s)) return rc;
+  int rc = scratch_grow(h, &h->d_pv, &h->pv_cap, C, ldv);
+  if (rc == TOWR_OK && !G) rc = scratch_grow(h, &h->d_rg, &h->rg_cap, C, ldr);
+  if (rc == TOWR_OK && !LAMP) rc = scratch_grow(h, &h->d_rl, &h->rl_cap, C, ldr);
+  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
+    const int cb = std::min(C, B - c0);
+    double* g = G ? G + (int64_t)c0 * ldg : h->d_rg;
+    const int64_t lg = G ? ldg : ldr;
+    double* lp = LAMP ? LAMP + (int64_t)c0 * ldlp : h->d_rl;
+    const int64_t llp = LAMP ? ldlp : ldr;
+    rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, g, lg, h->d_pv, ldv, 1, 1, s, per ? ter + c0 : ter, per, -1);
+    if (rc == TOWR_OK)
+      rc = launch_residual(h, cb, g, lg, GL ? GL + (int64_t)c0 * ldb : nullptr, GL ? GU + (int64_t)c0 * ldb : nullptr, ldb,
+                           LAM ? LAM + (int64_t)c0 * ldl : nullptr, ldl, rho, lp, llp, SUM + (int64_t)c0 * lds, lds, s);
+    if (rc == TOWR_OK) rc = launch_product(h, true, cb, h->d_pv, ldv, lp, llp, Z + (int64_t)c0 * ldz, ldz, accumulate != 0, s);
+  }
+  const int rr = scratch_release(h, s);
   return rc ? rc : rr;
 }
 

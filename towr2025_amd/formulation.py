@@ -381,6 +381,8 @@ class Parameters:
         self.torque_ty_min_, self.torque_ty_max_ = -100.0, 100.0
         self.torque_k_friction_ = 2.0 / 3.0
         self.ee_linear_constraints_: List["EELinearConstraintDef"] = []
+        # dims (0..2) whose RangeOfMotion bounds are lifted while the foot swings (parameters.h:331)
+        self.rom_swing_relax_dims_: List[int] = []
         # costs (parameters.h:157-247): (CostName, weight) pairs; none by default (parameters.cc:90)
         self.costs_: List[Tuple[int, float]] = []
         self.energy_cost_torque_weight_ = 1.0
@@ -539,6 +541,20 @@ class NlpFormulation:
                 raise ValueError("EELinear: 1..6 terms supported")
             out.append(dict(kind=capi.C_EE_LINEAR, ee=0, T=T, dt=dfn.dt, p=[c for _, _, c in dfn.terms],
                             ip=[dfn.target, dfn.deriv, len(dfn.terms)] + [e * 3 + d for e, d, _ in dfn.terms]))
+        return out
+
+    def bounds_data(self, constraints=None) -> List[Tuple[int, int, List[float]]]:
+        """Side data TOWR_DATA_BOUNDS for the constraint list (default: constraint_sets()), as (kind, constraint index,
+        doubles): each EELinear set's tolerance (the k-th EELinear set is ee_linear_constraints_[k]) and, with
+        rom_swing_relax_dims_, the relaxed dims of every RangeOfMotion set (nlp_formulation.cc:433-435)."""
+        P = self.params_
+        out, k = [], 0
+        for i, c in enumerate(self.constraint_sets() if constraints is None else constraints):
+            if c["kind"] == capi.C_EE_LINEAR:
+                out.append((capi.DATA_BOUNDS, i, [float(P.ee_linear_constraints_[k].tolerance)]))
+                k += 1
+            elif c["kind"] == capi.C_RANGE_OF_MOTION and P.rom_swing_relax_dims_:
+                out.append((capi.DATA_BOUNDS, i, [float(d) for d in P.rom_swing_relax_dims_]))
         return out
 
     # cost terms in NlpFormulation::GetCosts order (nlp_formulation.cc:604-680)

@@ -330,6 +330,19 @@ std::vector<ConstraintSpec> NlpFormulation::GetConstraints() const {
   return out;
 }
 
+std::vector<BoundsEntry> NlpFormulation::BoundsData() const {
+  const Parameters& P = params_;
+  const std::vector<ConstraintSpec> cs = GetConstraints();
+  std::vector<BoundsEntry> out;
+  size_t k = 0;   // the k-th EELinear set is ee_linear_constraints_[k]
+  for (size_t i = 0; i < cs.size(); ++i) {
+    if (cs[i].kind == TOWR_C_EE_LINEAR) out.push_back({(int)i, {P.ee_linear_constraints_.at(k++).tolerance}});
+    else if (cs[i].kind == TOWR_C_RANGE_OF_MOTION && !P.rom_swing_relax_dims_.empty())
+      out.push_back({(int)i, std::vector<double>(P.rom_swing_relax_dims_.begin(), P.rom_swing_relax_dims_.end())});
+  }
+  return out;
+}
+
 // NlpFormulation::GetCosts (nlp_formulation.cc:604-680): MakeForcesCost (:646-664) and
 // MakeEEMotionCost (:666-678) expand into NodeCosts; the swing ee-base tracking terms (:613-626) follow
 std::vector<CostSpec> NlpFormulation::GetCosts() const {

@@ -96,6 +96,8 @@ struct Parameters {
     double dt = 0.1;
   };
   std::vector<EELinearConstraintDef> ee_linear_constraints_;
+  // dims (0..2) whose RangeOfMotion bounds are lifted while the foot swings (parameters.h:331)
+  std::vector<int> rom_swing_relax_dims_;
   // costs (parameters.h:157-247): (CostName, weight) pairs, none by default (parameters.cc:90)
   enum CostName { ForcesCostID, EEMotionCostID, EnergyCostID, AngMomCostID };
   std::vector<std::pair<CostName, double>> costs_;
@@ -125,6 +127,8 @@ struct BaseState {
 struct VarSet { int kind, ee; };
 struct CostSpec { int kind, ee; double weight, dt; std::array<double, 4> p{}; std::array<int32_t, 4> ip{}; };
 struct ConstraintSpec { int kind, ee; double T, dt; std::array<double, 6> p{}; std::array<int32_t, 9> ip{}; };
+// one TOWR_DATA_BOUNDS entry of towr_gpu_create_ex: the constraint's index and its doubles
+struct BoundsEntry { int index; std::vector<double> values; };
 
 class NlpFormulation {
  public:
@@ -137,6 +141,9 @@ class NlpFormulation {
   std::vector<VarSet> GetVariableSets() const;          // nlp_formulation.cc:76-119 order
   std::vector<ConstraintSpec> GetConstraints() const;   // nlp_formulation.cc:365-398 expansion
   std::vector<CostSpec> GetCosts() const;               // nlp_formulation.cc:604-680 expansion
+  // side data TOWR_DATA_BOUNDS for GetConstraints(): each EELinear set's tolerance and, with rom_swing_relax_dims_,
+  // every RangeOfMotion set's relaxed dims (nlp_formulation.cc:433-435); the same entries as formulation.py's
+  std::vector<BoundsEntry> BoundsData() const;
   // the engine's problem description (optionally with an explicit variable / constraint list as
   // towr/test/procedural_example.cc builds, a procedural initial guess and goal footholds)
   towr_problem_desc_t MakeDesc() const;

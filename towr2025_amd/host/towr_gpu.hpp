@@ -96,6 +96,26 @@ class Engine {
                               int64_t ldz, bool accumulate, const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream) const {
     return towr_gpu_eval_products_batch_device(h_, B, X, ldx, G, ldg, LAM, ldl, Z, ldz, accumulate ? 1 : 0, P, ldp, Y, ldy, stream);
   }
+  // constraint set i's row range, and the constraint bounds in row order (ifopt's GetBounds of every set; +-1e20 = no bound)
+  void GetConstraintInfo(int i, int32_t* kind, int32_t* ee, int32_t* row0, int32_t* rows) const {
+    Check(towr_gpu_constraint_info(h_, i, kind, ee, row0, rows));
+  }
+  void GetConstraintBounds(double* lower, double* upper) const { Check(towr_gpu_constraint_bounds(h_, lower, upper)); }
+  void GetConstraintBoundsFor(const towr_init_t& init, const towr_terrain_t& terrain, double* lower, double* upper) const {
+    Check(towr_gpu_constraint_bounds_for(h_, &init, &terrain, lower, upper));
+  }
+  // per-problem violation summaries and augmented-Lagrangian multipliers of a batch of g on the device, and the fused
+  // evaluate / residual / J^T lam+ entry (include/towr_gpu.h); they return the status
+  int ResidualBatchDevice(int B, const double* G, int64_t ldg, const double* GL, const double* GU, int64_t ldb, const double* LAM,
+                          int64_t ldl, double rho, double* LAMP, int64_t ldlp, double* SUM, int64_t lds, void* stream) const {
+    return towr_gpu_residual_batch_device(h_, B, G, ldg, GL, GU, ldb, LAM, ldl, rho, LAMP, ldlp, SUM, lds, stream);
+  }
+  int EvalAuglagBatchDevice(int B, const double* X, int64_t ldx, const double* GL, const double* GU, int64_t ldb, const double* LAM,
+                            int64_t ldl, double rho, double* G, int64_t ldg, double* LAMP, int64_t ldlp, double* SUM, int64_t lds,
+                            double* Z, int64_t ldz, bool accumulate, void* stream) const {
+    return towr_gpu_eval_auglag_batch_device(h_, B, X, ldx, GL, GU, ldb, LAM, ldl, rho, G, ldg, LAMP, ldlp, SUM, lds, Z, ldz,
+                                             accumulate ? 1 : 0, stream);
+  }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // page-lock caller memory for in-place host transfers (towr_gpu_register_host); returns the status
   int RegisterHost(void* p, size_t bytes) const { return towr_gpu_register_host(h_, p, (int64_t)bytes); }

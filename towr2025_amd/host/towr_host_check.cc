@@ -17,6 +17,13 @@
 //   evaluates a batch of the configuration on the device, applies J p and J^T lam there (separate calls and the fused
 //   entry) and compares them with a host loop over the CSR pattern; prints "products ok ... largest |err|/bound x"
 //   and exits non-zero when a bound is exceeded.
+//        towr_host_check <cfg> --bounds [relaxed dims, e.g. 2 or 0,2]
+//   prints the C++ mirror's TOWR_DATA_BOUNDS entries ("data <constraint> <count> <values...>") and, from a layout-only
+//   engine created with them, the constraint bounds ("row <i> <lower> <upper>"), every double as %.17g.
+//        towr_host_check <cfg> --residual [device] [problems]
+//   evaluates a batch on the device, runs the residual kernel (the handle's bounds, random multipliers) and the fused
+//   merit-and-gradient entry, and compares them with a host loop over the bounds; prints "residual ok ..." and exits
+//   non-zero on a mismatch.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -187,6 +194,106 @@ int products_check(const towr_problem_desc_t& d, int device, int B) {
   return worst <= 1.0 ? 0 : 1;
 }
 
+std::vector<towr_data_t> as_side_data(const std::vector<BoundsEntry>& bd) {
+  std::vector<towr_data_t> out;
+  for (const BoundsEntry& e : bd) out.push_back(towr_data_t{TOWR_DATA_BOUNDS, e.index, (int64_t)e.values.size(), e.values.data()});
+  return out;
+}
+
+int bounds_dump(const NlpFormulation& f) {
+  const std::vector<BoundsEntry> bd = f.BoundsData();
+  for (const BoundsEntry& e : bd) {
+    std::printf("data %d %zu", e.index, e.values.size());
+    for (double v : e.values) std::printf(" %.17g", v);
+    std::printf("\n");
+  }
+  Engine e(f.MakeDesc(), -1, as_side_data(bd));
+  const int m = e.GetNumberOfConstraints();
+  std::vector<double> lo(m), up(m);
+  e.GetConstraintBounds(lo.data(), up.data());
+  for (int i = 0; i < m; ++i) std::printf("row %d %.17g %.17g\n", i, lo[i], up[i]);
+  return 0;
+}
+
+// --residual: B perturbations of x0; the residual kernel's outputs against a host loop: the maxima, the arg max and the
+// per-set maxima bit for bit, the two sums under 2 gamma_m S (+ 8 u S for phi's per-term roundings), lam+ within
+// 8 u rho (|g| + |lam| / rho + |c|); then the fused entry against the separate calls, bit for bit.
+int residual_check(const NlpFormulation& f, int device, int B) {
+  const std::vector<BoundsEntry> bd = f.BoundsData();
+  const towr_problem_desc_t d = f.MakeDesc();
+  Engine e(d, device, as_side_data(bd));
+  const int n = e.GetNumberOfOptimizationVariables(), m = e.GetNumberOfConstraints(), ns = d.n_constraints, lds = 4 + ns;
+  const int64_t nnz = e.GetNumberOfJacobianNonzeros();
+  std::vector<double> lo(m), up(m);
+  e.GetConstraintBounds(lo.data(), up.data());
+  std::vector<int32_t> row0(ns + 1, m);
+  for (int s = 0; s < ns; ++s) { int32_t k, ee, rows; e.GetConstraintInfo(s, &k, &ee, &row0[s], &rows); }
+  const std::vector<double> x0 = e.GetVariableValues();
+  const double rho = 10.0;
+  std::vector<double> X((size_t)B * n), LAM((size_t)B * m);
+  for (int b = 0; b < B; ++b) {
+    for (int i = 0; i < n; ++i) X[(size_t)b * n + i] = x0[i] + 0.01 * b * std::sin(0.37 * i + b);
+    for (int i = 0; i < m; ++i) LAM[(size_t)b * m + i] = std::sin(0.9 * i + 1.1 * b) * (1 + i % 3);
+  }
+  DevBuf dX(X.size()), dL(LAM.size()), dG((size_t)B * m), dV((size_t)B * nnz), dLP((size_t)B * m), dS((size_t)B * lds), dZ((size_t)B * n),
+      dG2((size_t)B * m), dLP2((size_t)B * m), dS2((size_t)B * lds), dZ2((size_t)B * n);
+  if (!dX.put(X) || !dL.put(LAM) || !dG.p || !dV.p || !dLP.p || !dS.p || !dZ.p || !dG2.p || !dLP2.p || !dS2.p || !dZ2.p) {
+    std::fprintf(stderr, "residual: device allocation failed\n");
+    return 1;
+  }
+  e.SetProductsChunk(3);
+  if (e.EvalBatchDevice(B, dX.p, n, dG.p, m, dV.p, nnz, nullptr) ||
+      e.ResidualBatchDevice(B, dG.p, m, nullptr, nullptr, 0, dL.p, m, rho, dLP.p, m, dS.p, lds, nullptr) ||
+      e.JacTVecBatchDevice(B, dV.p, nnz, dLP.p, m, dZ.p, n, false, nullptr) ||
+      e.EvalAuglagBatchDevice(B, dX.p, n, nullptr, nullptr, 0, dL.p, m, rho, dG2.p, m, dLP2.p, m, dS2.p, lds, dZ2.p, n, false, nullptr) ||
+      hipDeviceSynchronize() != hipSuccess) {
+    std::fprintf(stderr, "residual: %s\n", towr_gpu_last_error(e.handle()));
+    return 1;
+  }
+  std::vector<double> G, LP, S, Z, G2, LP2, S2, Z2;
+  if (!dG.get(G) || !dLP.get(LP) || !dS.get(S) || !dZ.get(Z) || !dG2.get(G2) || !dLP2.get(LP2) || !dS2.get(S2) || !dZ2.get(Z2)) return 1;
+  auto same = [](const std::vector<double>& a, const std::vector<double>& b) { return std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0; };
+  if (!same(G, G2) || !same(LP, LP2) || !same(S, S2) || !same(Z, Z2)) { std::fprintf(stderr, "residual: the fused entry differs from the separate calls\n"); return 1; }
+  const long double u = std::ldexp(1.0L, -53), gam = 2 * (m * u / (1 - m * u));
+  int bad = 0;
+  double worst = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const double *g = G.data() + (size_t)b * m, *lam = LAM.data() + (size_t)b * m, *lp = LP.data() + (size_t)b * m, *sm = S.data() + (size_t)b * lds;
+    std::vector<double> smax(ns, 0.0);
+    double vmax = 0.0, arg = -1.0;
+    long double sv = 0, phi = 0, aphi = 0;
+    int set = 0;
+    for (int i = 0; i < m; ++i) {
+      while (i >= row0[set + 1]) ++set;
+      const bool hl = lo[i] > -1e19, hu = up[i] < 1e19;
+      double v = 0.0;
+      if (hl && lo[i] - g[i] > v) v = lo[i] - g[i];
+      if (hu && g[i] - up[i] > v) v = g[i] - up[i];
+      if (v > vmax) { vmax = v; arg = i; }
+      smax[set] = std::max(smax[set], v);
+      sv += v;
+      const double t = g[i] + lam[i] / rho;
+      double c = t;
+      if (hl && c < lo[i]) c = lo[i];
+      if (hu && c > up[i]) c = up[i];
+      const double r = t - c;
+      const long double term = 0.5L * rho * r * r - 0.5L * lam[i] * lam[i] / rho;
+      phi += term; aphi += std::fabs(term);
+      const double tol = 8 * (double)u * rho * (std::fabs(g[i]) + std::fabs(lam[i]) / rho + std::fabs(c));
+      if (!(std::fabs(lp[i] - rho * r) <= tol)) ++bad;
+    }
+    if (std::memcmp(&sm[0], &vmax, 8) || sm[2] != arg) ++bad;
+    for (int s = 0; s < ns; ++s) if (std::memcmp(&sm[4 + s], &smax[s], 8)) ++bad;
+    const long double e1 = std::fabs((long double)sm[1] - sv), b1 = gam * sv;
+    const long double e3 = std::fabs((long double)sm[3] - phi), b3 = (gam + 8 * u) * aphi;
+    if (!(e1 <= b1) || !(e3 <= b3)) ++bad;
+    if (b1 > 0) worst = std::max(worst, (double)(e1 / b1));
+    if (b3 > 0) worst = std::max(worst, (double)(e3 / b3));
+  }
+  std::printf("residual %s n=%d m=%d sets=%d B=%d mismatches %d largest sum |err|/bound %.3f\n", bad ? "FAILED" : "ok", n, m, ns, B, bad, worst);
+  return bad ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -194,6 +301,7 @@ int main(int argc, char** argv) {
   const std::string cfg = argv[1];
   const int device = argc > 3 ? std::atoi(argv[3]) : -1;
   const bool zc = std::string(argv[2]) == "--zerocopy", pr = std::string(argv[2]) == "--products";
+  const bool bo = std::string(argv[2]) == "--bounds", rs = std::string(argv[2]) == "--residual";
   NlpFormulation f = (cfg == "anymal" || cfg == "anymal_costs" || cfg == "anymal_rotvec" || cfg == "anymal_gait") ? AnymalTrot()
                      : (cfg == "biped" || cfg == "biped_next") ? BipedWalk() : MonopedHopper();
   if (cfg == "anymal_gait") {   // BASELINE configs[3]: stairs, phase-duration optimisation
@@ -217,6 +325,12 @@ int main(int argc, char** argv) {
     f.params_.enable_swing_ee_base_pos_tracking = true;
   }
   try {
+    if (bo) {
+      for (const char* q = argc > 3 ? argv[3] : ""; *q; ++q)
+        if (*q >= '0' && *q <= '2') f.params_.rom_swing_relax_dims_.push_back(*q - '0');
+      return bounds_dump(f);
+    }
+    if (rs) return residual_check(f, device < 0 ? 0 : device, argc > 4 ? std::max(1, std::atoi(argv[4])) : 5);
     const towr_problem_desc_t d = f.MakeDesc();
     if (zc) return zerocopy_check(d, device < 0 ? 0 : device, argc > 4 ? std::atoi(argv[4]) : 200);
     if (pr) return products_check(d, device < 0 ? 0 : device, argc > 4 ? std::max(1, std::atoi(argv[4])) : 7);

@@ -107,6 +107,30 @@ class TowrGpuProblem:
             out.append((k.value, e.value, c0.value, n.value))
         return out
 
+    def constraint_info(self):
+        """[(kind, ee, row0, rows)] of the constraint sets in description order; the hard sets tile [0, m), a soft
+        set has rows = 0."""
+        out = []
+        for i in range(self.desc.n_constraints):
+            k, e, r0, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+            self._check(self._lib.towr_gpu_constraint_info(self._h, i, C.byref(k), C.byref(e), C.byref(r0), C.byref(n)))
+            out.append((k.value, e.value, r0.value, n.value))
+        return out
+
+    def constraint_bounds(self):
+        """(lower, upper), m doubles each: every constraint set's GetBounds() in row order, at the description's x0
+        and terrain (IpoptAdapter::get_bounds_info for g). Unbounded sides are +-1e20."""
+        lo, up = np.zeros(self.m), np.zeros(self.m)
+        self._check(self._lib.towr_gpu_constraint_bounds(self._h, capi.dptr(lo), capi.dptr(up)))
+        return lo, up
+
+    def constraint_bounds_for(self, init: capi.InitDesc, terrain: capi.Terrain):
+        """The bounds of another start/goal/terrain instance on this layout (they differ on node-Torque rows only)."""
+        lo, up = np.zeros(self.m), np.zeros(self.m)
+        self._check(self._lib.towr_gpu_constraint_bounds_for(self._h, C.byref(init), C.byref(terrain),
+                                                             capi.dptr(lo), capi.dptr(up)))
+        return lo, up
+
     def jac_structure(self):
         r = np.zeros(self.nnz, dtype=np.int32)
         c = np.zeros(self.nnz, dtype=np.int32)
@@ -326,6 +350,62 @@ class TowrGpuProblem:
         self._check(self._lib.towr_gpu_eval_products_batch_device(
             self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gp, ldg, lp, ldl, zp, ldz, int(bool(accumulate)),
             pp, ldp, yp, ldy, self._stream(stream, X)))
+
+    # -------------------------------------------------------------------- residuals -----------
+    def _bounds_operands(self, B, GL, GU):
+        """(GL pointer, GU pointer, ldb) of a residual call: both None (the handle's bounds), both 1-D of >= m entries
+        (one row shared by all problems, ldb = 0) or both 2-D (B, >= m)."""
+        if GL is None and GU is None:
+            return C.c_void_p(None), C.c_void_p(None), 0
+        if GL is None or GU is None:
+            raise TowrGpuError("GL and GU: give both or neither")
+        if GL.dim() != GU.dim():
+            raise TowrGpuError("GL and GU: one is shared (1-D), the other per problem (2-D)")
+        if GL.dim() == 1:
+            for t, name in ((GL, "GL"), (GU, "GU")):
+                _check_tensor(t, name, self.m, self.device)
+                if t.shape[0] < self.m or (t.shape[0] > 1 and t.stride(0) != 1):
+                    raise TowrGpuError(f"{name}: expected >= {self.m} contiguous entries")
+            return C.c_void_p(GL.data_ptr()), C.c_void_p(GU.data_ptr()), 0
+        self._check_rows(B, (GL, "GL", self.m), (GU, "GU", self.m))
+        if GL.stride(0) != GU.stride(0) or GL.stride(0) < self.m:
+            raise TowrGpuError("GL and GU: they share one leading dimension (>= m)")
+        return C.c_void_p(GL.data_ptr()), C.c_void_p(GU.data_ptr()), GL.stride(0)
+
+    def residual_batch_device(self, G, SUM, GL=None, GU=None, LAM=None, rho=1.0, LAMP=None, stream=None):
+        """Per-problem violation summary of G (B, >= m) against the bounds into SUM (B, >= 4 + n_constraints): max,
+        sum, arg max, phi, per-set maxima (towr_gpu.h). GL / GU: None (the handle's bounds), 1-D (shared) or (B, >= m).
+        With LAMP (B, >= m): the augmented Lagrangian's multipliers for LAM (None = zero) and rho."""
+        B = G.shape[0]
+        ops = [(G, "G", self.m), (SUM, "SUM", 4 + self.desc.n_constraints)]
+        ops += [(t, name, self.m) for t, name in ((LAM, "LAM"), (LAMP, "LAMP")) if t is not None]
+        self._check_rows(B, *ops)
+        gl, gu, ldb = self._bounds_operands(B, GL, GU)
+
+        def ptr(t):
+            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
+        (lp, ldl), (pp, ldlp) = ptr(LAM), ptr(LAMP)
+        self._check(self._lib.towr_gpu_residual_batch_device(
+            self._h, B, C.c_void_p(G.data_ptr()), G.stride(0), gl, gu, ldb, lp, ldl, float(rho), pp, ldlp,
+            C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, G)))
+
+    def eval_auglag_batch_device(self, X, SUM, Z, GL=None, GU=None, LAM=None, rho=1.0, G=None, LAMP=None,
+                                 accumulate=False, stream=None):
+        """Evaluate g_b, J_b at X[b], then SUM[b] and lam+_b as residual_batch_device, then Z[b] (+)= J_b^T lam+_b; g and
+        lam+ are written to G / LAMP when given. The values stay in handle scratch, set_products_chunk problems at a time."""
+        B = X.shape[0]
+        ops = [(X, "X", self.n), (SUM, "SUM", 4 + self.desc.n_constraints), (Z, "Z", self.n)]
+        ops += [(t, name, self.m) for t, name in ((LAM, "LAM"), (G, "G"), (LAMP, "LAMP")) if t is not None]
+        self._check_rows(B, *ops)
+        gl, gu, ldb = self._bounds_operands(B, GL, GU)
+
+        def ptr(t):
+            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
+        (lp, ldl), (gp, ldg), (pp, ldlp) = ptr(LAM), ptr(G), ptr(LAMP)
+        self._check(self._lib.towr_gpu_eval_auglag_batch_device(
+            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gl, gu, ldb, lp, ldl, float(rho), gp, ldg, pp, ldlp,
+            C.c_void_p(SUM.data_ptr()), SUM.stride(0), C.c_void_p(Z.data_ptr()), Z.stride(0), int(bool(accumulate)),
+            self._stream(stream, X)))
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
