@@ -208,17 +208,25 @@ enum towr_data_kind {
   TOWR_DATA_SOFT_BOUNDS = 1, /* index = cost term (TOWR_COST_SOFT); count = 2 * rows of the wrapped set;
                                 data = lower[0..rows-1], upper[0..rows-1] = the wrapped set's GetBounds(), from
                                 which the engine forms b = (upper + lower) / 2 as SoftConstraint's ctor does  */
-  TOWR_DATA_BOUNDS      = 2  /* OPTIONAL; index = constraint; what towr_gpu_constraint_bounds needs beyond the POD:
+  TOWR_DATA_BOUNDS      = 2, /* OPTIONAL; index = constraint; what towr_gpu_constraint_bounds needs beyond the POD:
                                 TOWR_C_EE_LINEAR: count = 1, the tolerance (ee_linear_constraint.cc:32-35);
                                 TOWR_C_LINEAR_EQ: count = rows, the offset v (linear_constraint.cc:53-64);
                                 TOWR_C_RANGE_OF_MOTION: count = 1..3, Parameters::rom_swing_relax_dims_ as doubles
                                 (0, 1 or 2; nlp_formulation.cc:433-435); absent = no relaxation.
                                 A handle created without them evaluates as ever; only the bounds calls then fail
                                 (TOWR_ERR_INVALID) when it holds an EELinear or LinearEquality set                 */
+  TOWR_DATA_VAR_BOUNDS  = 3  /* OPTIONAL; index = variable set (AddVariableSet order, a node set); count = 5 * records;
+                                data = records (node_id, deriv, dim, lower, upper), each one call of
+                                NodesVariables::AddBound(NodeValueInfo(node, deriv, dim), lower, upper)
+                                (nodes_variables.cc:234-241; AddBounds / AddStartBound / AddFinalBound reduce to it),
+                                applied in order: what the driver bounds on the variables (nlp_formulation.cc:121-346).
+                                A record naming a value that is not optimised (deriv 2, a swing node of a force set,
+                                a swing z velocity) is a no-op, as in the reference. A set without an entry is
+                                unbounded (towr_gpu_variable_bounds)                                                */
 };
 typedef struct {
   int32_t       kind;    /* towr_data_kind                                                          */
-  int32_t       index;   /* constraint or cost index in the description                             */
+  int32_t       index;   /* constraint, cost or variable-set index in the description               */
   int64_t       count;   /* doubles at `data`                                                       */
   const double* data;    /* host memory, copied at creation                                         */
 } towr_data_t;
@@ -268,6 +276,19 @@ int towr_gpu_constraint_info(towr_gpu_handle h, int32_t i, int32_t* kind, int32_
 int towr_gpu_constraint_bounds(towr_gpu_handle h, double* lower /* m */, double* upper /* m */);
 int towr_gpu_constraint_bounds_for(towr_gpu_handle h, const towr_init_t* init, const towr_terrain_t* terrain,
                                    double* lower, double* upper);
+/* The variable bounds in ifopt column order, lower[n] and upper[n] (what IpoptAdapter::get_bounds_info reports for
+ * x): every node set starts as ifopt's NoBound (-1.0e20, +1.0e20) and takes its TOWR_DATA_VAR_BOUNDS records in
+ * order, later ones overwriting earlier ones; a record bounds the one column its node value maps to (two stance
+ * nodes that share a variable share the bound). Every variable of a schedule set gets bound_phase_duration
+ * (phase_durations.cc:51,103-110). Unbounded sides are +-1.0e20, never IEEE infinity. towr_gpu_variable_bounds
+ * answers for the entries given at creation; _with rebuilds the bounds on this layout from the TOWR_DATA_VAR_BOUNDS
+ * entries of `data` instead (another instance of the randomised batch, whose start and goal differ) and changes
+ * nothing in the handle. Creation and _with refuse (TOWR_ERR_INVALID, the message names the variable set) a count
+ * that is no multiple of 5, a non-integral or out-of-range node, deriv (0..2) or dim (0..2), a NaN, lower > upper,
+ * and an index that is not a node set. Host calls; they work on layout-only handles.                           */
+int towr_gpu_variable_bounds(towr_gpu_handle h, double* lower /* n */, double* upper /* n */);
+int towr_gpu_variable_bounds_with(towr_gpu_handle h, int32_t n_data, const towr_data_t* data,
+                                  double* lower, double* upper);
 
 /* ---- single-problem host callbacks (what IpoptAdapter calls) -------------------------------- */
 /* g = ifopt Problem::EvalConstraints(x)          (IpoptAdapter::eval_g)                         */
@@ -436,6 +457,49 @@ int towr_gpu_eval_auglag_batch_device(towr_gpu_handle h, int32_t B, const double
                                       double* G, int64_t ldg, double* LAMP, int64_t ldlp,
                                       double* SUM, int64_t lds,
                                       double* Z, int64_t ldz, int32_t accumulate, void* stream);
+
+/* ---- taking a step on the device: the projected step and its summary ------------------------------------------ */
+/* Per problem b and column j, with x = X[b*ldx + j], d = D[b*ldd + j], l = XL[b*ldb + j], u = XU[b*ldb + j] and the
+ * step length a = ALPHA[b] (ALPHA NULL: the scalar alpha). All pointers are DEVICE pointers. XL = XU = NULL: the
+ * handle's description bounds (towr_gpu_variable_bounds), uploaded synchronously by the first such call; ldb = 0:
+ * one bounds row shared by all problems; else ldb >= n (per-problem rows, towr_gpu_variable_bounds_with):
+ *   a side counts only if l > -1e19, respectively u < 1e19 (as towr_gpu_residual_batch_device);
+ *   t  = x - a d, a rounded product then a rounded subtraction (never a fused multiply-add);
+ *   xp = t clamped to the sides that count, XP[b*ldxp + j] (XP NULL: summary only); a fixed variable (l == u) lands
+ *        exactly on l;
+ *   s  = xp - x, the projected step.
+ * SUM[b*lds + ...] holds 5 + n_varsets doubles (lds >= that): [0] max |s_j| (with a = 1 and d = grad L the
+ * projected-gradient stationarity measure); [1] sum s_j^2; [2] sum d_j s_j (the slope of an Armijo test); [3] the
+ * number of columns whose xp lies on a side that counts, as a double; [4] max(l - x, x - u, 0) over the sides that
+ * count (how far X itself is outside its box); [5 + s] max |s_j| over variable set s (AddVariableSet order).
+ * A NaN x, d or a makes [0], [1], [2] and its own set's entry NaN and leaves the other sets' entries untouched.
+ * One block per problem; the sums are one fixed tree each (lane-strided partials, a shuffle tree, the waves in
+ * order; no floating-point atomics) and the maxima are integer maxima of the bit patterns, so problem b's outputs
+ * are a function of its own operands alone: the same bits for any B, any position, any stream, run to run. Nothing
+ * beyond n (X, D, XP, XL, XU) or 5 + n_varsets (SUM) is read or written. No handle scratch is used and the kept
+ * Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for: NULL X, D or SUM, lds < 5 + n_varsets,
+ * ldx / ldd / ldxp < n, 0 < ldb < n, only one of XL / XU, a NaN scalar alpha with ALPHA NULL.                     */
+int towr_gpu_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx,
+                               const double* D, int64_t ldd, const double* ALPHA, double alpha,
+                               const double* XL, const double* XU, int64_t ldb,
+                               double* XP, int64_t ldxp, double* SUM, int64_t lds, void* stream);
+
+/* One call per iteration of a projected first-order method on the augmented Lagrangian: on `stream`,
+ *   1. towr_gpu_eval_cost_batch_device with GRAD into handle scratch (F NULL: f into handle scratch as well);
+ *   2. towr_gpu_eval_auglag_batch_device with accumulate = 1 onto that gradient (G, LAMP optional, RSUM its SUM);
+ *   3. towr_gpu_step_batch_device with D = that gradient (XP and SSUM required).
+ * Bit-identical to the three calls in sequence, whatever the products chunk. It exists for the footprint (the
+ * gradient, like the values, g and lam+, never leaves handle scratch) and the single call, not for speed: it
+ * launches what the three calls launch. Batch terrains, the cross-stream scratch rule and the kept Jacobian as for
+ * towr_gpu_eval_products_batch_device. Argument checks as the three calls'.                                      */
+int towr_gpu_auglag_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx,
+                                      const double* GL, const double* GU, int64_t ldgb,
+                                      const double* LAM, int64_t ldl, double rho,
+                                      const double* ALPHA, double alpha,
+                                      const double* XL, const double* XU, int64_t ldxb,
+                                      double* F, double* G, int64_t ldg, double* LAMP, int64_t ldlp,
+                                      double* RSUM, int64_t ldrs,
+                                      double* XP, int64_t ldxp, double* SSUM, int64_t ldss, void* stream);
 
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the

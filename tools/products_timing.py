@@ -5,7 +5,9 @@
   (e) residual_batch_device (summary and lam+, the handle's bounds): rate = 8 (3 m + 4 + n_constraints) B / time, the
       bytes of G + LAM + LAMP + SUM, beside (f) a device-to-device torch copy moving the same bytes (half read, half
       written);
-  (g) eval_auglag_batch_device (g and lam+ in scratch) beside the sum of its parts a + e + c from the same session,
+  (g) eval_auglag_batch_device (g and lam+ in scratch) beside the sum of its parts a + e + c from the same session;
+  (h) step_batch_device (XP and the summary, the handle's bounds, scalar step length): rate = 8 (3 n + 5 + n_varsets)
+      B / time, the bytes of X + D + XP + SUM, beside (i) a device-to-device torch copy moving the same bytes,
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -40,9 +42,10 @@ def batch_x(p, B, seed=20261019):
     return X
 
 
-def run(name, desc, B):
+def run(name, f, B):
     dev = torch.device("cuda", 0)
-    p = TowrGpuProblem(desc, device=0)
+    f.params_.enable_stance_tracking = False   # the start / goal variable bounds (the step kernel's box)
+    p = TowrGpuProblem(f.to_desc(), device=0, data=f.var_bounds_data())
     stream = torch.cuda.Stream(dev)
     torch.cuda.set_stream(stream)
     ld = lambda k: (k + 15) // 16 * 16
@@ -58,6 +61,13 @@ def run(name, desc, B):
     src = torch.randn(bytes_res // 16, dtype=torch.float64, device=dev)
     dst = torch.empty_like(src)
     rho = 10.0
+    nv = p.desc.n_varsets
+    XP, SSUM = torch.empty_like(P), torch.empty((B, ld(5 + nv)), dtype=torch.float64, device=dev)
+    Xs = torch.zeros_like(P)
+    Xs[:, :p.n] = X
+    bytes_step = 8 * (3 * p.n + 5 + nv) * B
+    src_s = torch.randn(bytes_step // 16, dtype=torch.float64, device=dev)
+    dst_s = torch.empty_like(src_s)
 
     def fused(chunk):
         def f():
@@ -72,7 +82,9 @@ def run(name, desc, B):
                 ("e residual", lambda: p.residual_batch_device(G, SUM, LAM=LAM, rho=rho, LAMP=LAMP, stream=stream)),
                 ("f copy, same bytes", lambda: dst.copy_(src)),
                 ("g auglag fused auto", lambda: (p.set_products_chunk(0),
-                                                 p.eval_auglag_batch_device(X, SUM, Z, LAM=LAM, rho=rho, stream=stream)))]
+                                                 p.eval_auglag_batch_device(X, SUM, Z, LAM=LAM, rho=rho, stream=stream))),
+                ("h step", lambda: p.step_batch_device(Xs, P, SSUM, XP=XP, alpha=0.01, stream=stream)),
+                ("i copy, step's bytes", lambda: dst_s.copy_(src_s))]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
         for _ in range(3):
             fn()
@@ -92,7 +104,7 @@ def run(name, desc, B):
     for k, _ in variants:
         t = times[k]
         med = statistics.median(t)
-        nbytes = bytes_prod if k[0] in "bc" else bytes_res if k[0] in "ef" else 0
+        nbytes = bytes_prod if k[0] in "bc" else bytes_res if k[0] in "ef" else bytes_step if k[0] in "hi" else 0
         rate = f"  {nbytes / (med * 1e-3) / 1e12:.2f} TB/s = {100 * nbytes / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if nbytes else ""
         print(f"  {k:22s} {med:.4f} ms  (min {min(t):.4f} max {max(t):.4f}){rate}", flush=True)
     parts = sum(statistics.median(times[k]) for k in ("a eval_batch_device", "e residual", "c jac_tvec"))
@@ -104,7 +116,7 @@ def run(name, desc, B):
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("anymal", "all"):
-        run("anymal_trot", F.anymal_trot().to_desc(), int(os.environ.get("B", "4096")))
+        run("anymal_trot", F.anymal_trot(), int(os.environ.get("B", "4096")))
     if which in ("gait", "all"):
-        run("anymal_stairs_gaitopt", F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True).to_desc(),
+        run("anymal_stairs_gaitopt", F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True),
             int(os.environ.get("B_GAIT", "1024")))

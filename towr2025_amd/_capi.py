@@ -71,7 +71,7 @@ class InitDesc(C.Structure):
 # towr_cost_kind
 COST_NODE, COST_ENERGY, COST_ANG_MOMENTUM, COST_EE_BASE_POS, COST_BASE_HEIGHT, COST_SOFT = range(6)
 # towr_data_kind (side data of towr_gpu_create_ex)
-DATA_LINEAR_M, DATA_SOFT_BOUNDS, DATA_BOUNDS = 0, 1, 2
+DATA_LINEAR_M, DATA_SOFT_BOUNDS, DATA_BOUNDS, DATA_VAR_BOUNDS = 0, 1, 2, 3
 MAX_COSTS = 128
 
 
@@ -125,6 +125,8 @@ SYMBOLS = {
     "towr_gpu_constraint_info": (C.c_int, [_HANDLE, C.c_int32, _IP, _IP, _IP, _IP]),
     "towr_gpu_constraint_bounds": (C.c_int, [_HANDLE, _DP, _DP]),
     "towr_gpu_constraint_bounds_for": (C.c_int, [_HANDLE, C.POINTER(InitDesc), C.POINTER(Terrain), _DP, _DP]),
+    "towr_gpu_variable_bounds": (C.c_int, [_HANDLE, _DP, _DP]),
+    "towr_gpu_variable_bounds_with": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(SideData), _DP, _DP]),
     "towr_gpu_eval_g": (C.c_int, [_HANDLE, _DP, _DP]),
     "towr_gpu_eval_jac_values": (C.c_int, [_HANDLE, _DP, _DP]),
     "towr_gpu_eval_g_jac": (C.c_int, [_HANDLE, _DP, _DP, _DP]),
@@ -159,6 +161,15 @@ SYMBOLS = {
                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "towr_gpu_step_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_auglag_step_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
+                                                     C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                     C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

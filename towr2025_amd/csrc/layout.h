@@ -244,6 +244,22 @@ struct ResArgs {
 };
 const void* res_kernel();
 
+// The step kernel (step.hip): per problem XP = P_[XL, XU](X - a D) and the summary of the projected step s = XP - X
+// (towr_gpu.h); one block of kStepBlock threads per problem. set_col0[s] .. set_col0[s + 1] are the columns of
+// variable set s (AddVariableSet order). ldb = 0: one bounds row for all problems. ALPHA NULL: the scalar alpha.
+constexpr int kStepBlock = 256;
+struct StepArgs {
+  const double* X; int64_t ldx;
+  const double* D; int64_t ldd;
+  const double* ALPHA; double alpha;
+  const double *XL, *XU; int64_t ldb;
+  double* XP; int64_t ldxp;
+  double* SUM; int64_t lds;
+  const int32_t* set_col0;   // n_sets + 1
+  int32_t n, n_sets;
+};
+const void* step_kernel();
+
 struct Layout {
   int n = 0, m = 0;
   int64_t nnz = 0;
@@ -354,7 +370,12 @@ struct Layout {
   std::vector<double> g_lower, g_upper;
   std::vector<TqBound> tq_bounds;
   std::string bounds_err;
+  // The variable bounds in ifopt column order (build_var_bounds: the driver's AddBound calls, side data
+  // TOWR_DATA_VAR_BOUNDS, replayed on the node sets; the schedule sets' duration box)
+  std::vector<double> x_lower, x_upper;
 };
+// the variable bounds of the layout for the TOWR_DATA_VAR_BOUNDS entries of `data` (lower / upper: n doubles each)
+int build_var_bounds(const Layout& L, int n_data, const towr_data_t* data, double* lower, double* upper, std::string& err);
 void build_jprod(Layout& L);   // fills the jp_ / csc members above from row_ptr / col
 // the (-L, L) rows of the node TorqueConstraints at x on terrain `ter`, written into lower / upper (m doubles each)
 void torque_bounds(const Layout& L, const double* x, const towr_terrain_t& ter, double* lower, double* upper);

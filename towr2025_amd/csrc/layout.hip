@@ -1224,6 +1224,62 @@ int build_bounds(const towr_problem_desc_t& d, int n_data, const towr_data_t* da
   return TOWR_OK;
 }
 
+// The variable bounds: NodesVariables::AddBound (nodes_variables.cc:234-241) replayed per record (node, deriv, dim,
+// lower, upper) of a node set's TOWR_DATA_VAR_BOUNDS entry, in the order given, on bounds that start as NoBound
+// (nodes_variables_all.cc:41, nodes_variables_phase_based.cc:197). The reference bounds every optimisation index whose
+// node-value infos contain the record's: exactly the column nodecol names (two stance nodes share one), and none for a
+// value that is not optimised (an acceleration, a swing node of a force set, a swing z velocity). PhaseDurations:
+// every variable gets bound_phase_duration (phase_durations.cc:51,103-110).
+int build_var_bounds(const Layout& L, int n_data, const towr_data_t* data, double* lower, double* upper, std::string& err) {
+  const towr_problem_desc_t& d = L.desc;
+  for (int j = 0; j < L.n; ++j) { lower[j] = -kBoundInf; upper[j] = kBoundInf; }
+  for (int i = 0; i < n_data; ++i)
+    if (data[i].kind == TOWR_DATA_VAR_BOUNDS) {
+      const int vi = data[i].index;
+      if (vi < 0 || vi >= (int)L.varsets.size() || L.varsets[(size_t)vi].kind == TOWR_VAR_EE_SCHEDULE) {
+        err = "variable set " + std::to_string(vi) + ": side data TOWR_DATA_VAR_BOUNDS needs a node variable set";
+        return TOWR_ERR_INVALID;
+      }
+    }
+  for (int vi = 0; vi < (int)L.varsets.size(); ++vi) {
+    const VarSetInfo& vs = L.varsets[(size_t)vi];
+    if (vs.kind == TOWR_VAR_EE_SCHEDULE) {   // vs.n = PhaseDurations::GetRows
+      for (int k = 0; k < vs.n; ++k) {
+        lower[vs.col0 + k] = d.bound_phase_duration[0];
+        upper[vs.col0 + k] = d.bound_phase_duration[1];
+      }
+      continue;
+    }
+    const towr_data_t* bd = find_data(n_data, data, TOWR_DATA_VAR_BOUNDS, vi);
+    if (!bd) continue;
+    const std::string who = "variable set " + std::to_string(vi) + ": side data TOWR_DATA_VAR_BOUNDS ";
+    if (bd->count < 0 || bd->count % 5 != 0 || (bd->count > 0 && !bd->data)) {
+      err = who + "must hold records of 5 doubles (node, deriv, dim, lower, upper)";
+      return TOWR_ERR_INVALID;
+    }
+    const int si = vs.kind == TOWR_VAR_BASE_LIN ? 0 : vs.kind == TOWR_VAR_BASE_ANG ? 1 : 2 + 4 * vs.ee + (vs.kind - TOWR_VAR_EE_MOTION);
+    const SplineMeta& sp = L.spl[(size_t)si];
+    const int n_nodes = sp.n_polys + 1;
+    for (int64_t q = 0; q < bd->count; q += 5) {
+      const double* r = bd->data + q;
+      for (int k = 0; k < 5; ++k)
+        if (r[k] != r[k]) { err = who + "holds a NaN"; return TOWR_ERR_INVALID; }
+      if (!(r[0] >= 0 && r[0] < n_nodes && r[0] == std::floor(r[0])) || !(r[1] == 0.0 || r[1] == 1.0 || r[1] == 2.0) ||
+          !(r[2] == 0.0 || r[2] == 1.0 || r[2] == 2.0)) {
+        err = who + "names a node, deriv (0..2) or dim (0..2) that is not an integer in range";
+        return TOWR_ERR_INVALID;
+      }
+      if (r[3] > r[4]) { err = who + "holds lower > upper"; return TOWR_ERR_INVALID; }
+      if (r[1] == 2.0) continue;   // AddStartBound(kAcc, ...): no node value is an acceleration
+      const int col = L.nodecol[(size_t)(sp.node_off + (int)r[0]) * 6 + (size_t)((int)r[1] * 3 + (int)r[2])];
+      if (col < 0) continue;
+      lower[col] = r[3];
+      upper[col] = r[4];
+    }
+  }
+  return TOWR_OK;
+}
+
 void build_misc_xspan(Layout& L);
 int build_layout(const towr_problem_desc_t& d, Layout& L, std::string& err) { return build_layout_ex(d, 0, nullptr, L, err); }
 
@@ -1517,6 +1573,9 @@ int build_layout_ex(const towr_problem_desc_t& d, int n_data, const towr_data_t*
   }
   L.m = row;
   if (int rc = build_bounds(d, n_data, data, sets, L, err)) return rc;
+  L.x_lower.assign((size_t)L.n, 0.0);
+  L.x_upper.assign((size_t)L.n, 0.0);
+  if (int rc = build_var_bounds(L, n_data, data, L.x_lower.data(), L.x_upper.data(), err)) return rc;
 
   // ---- segment table: the reference's GetLocalTime scan for every (timed instance, spline)
   {

@@ -172,6 +172,13 @@ struct towr_gpu_handle_s {
   double *d_blo = nullptr, *d_bup = nullptr;
   double *d_rg = nullptr, *d_rl = nullptr;
   int64_t rg_cap = 0, rl_cap = 0;
+  // Steps (step.hip): the device copies of the variable sets' column ranges and of the description's variable
+  // bounds, uploaded by the first step call on the handle, and the fused entry's gradient / f scratch (the batch)
+  bool step_ready = false;
+  int32_t* d_set_col0 = nullptr;
+  double *d_xlo = nullptr, *d_xup = nullptr;
+  double *d_sd = nullptr, *d_sf = nullptr;
+  int64_t sd_cap = 0, sf_cap = 0;
 };
 
 namespace {
@@ -1439,7 +1446,7 @@ int towr_gpu_destroy(towr_gpu_handle h) {
   if (h->device >= 0) {
     for (void* p : h->d_jp) if (p) (void)hipFree(p);
     if (h->d_pv) (void)hipFree(h->d_pv);
-    void* res[] = {h->d_set_row0, h->d_blo, h->d_bup, h->d_rg, h->d_rl};
+    void* res[] = {h->d_set_row0, h->d_blo, h->d_bup, h->d_rg, h->d_rl, h->d_set_col0, h->d_xlo, h->d_xup, h->d_sd, h->d_sf};
     for (void* p : res) if (p) (void)hipFree(p);
   }
   void* host[] = {h->h_x, h->h_g, h->h_v};
@@ -1528,6 +1535,28 @@ int towr_gpu_constraint_bounds_for(towr_gpu_handle h, const towr_init_t* init, c
   std::string err;
   if (int rc = initial_x_for(h->L.desc, *init, *terrain, x, err)) return fail(h, rc, err);
   torque_bounds(h->L, x.data(), *terrain, lower, upper);
+  return TOWR_OK;
+}
+
+int towr_gpu_variable_bounds(towr_gpu_handle h, double* lower, double* upper) {
+  if (!h || !lower || !upper) return fail(h, TOWR_ERR_INVALID, "null argument");
+  const Layout& L = h->L;
+  if (L.n) {
+    std::memcpy(lower, L.x_lower.data(), sizeof(double) * L.x_lower.size());
+    std::memcpy(upper, L.x_upper.data(), sizeof(double) * L.x_upper.size());
+  }
+  return TOWR_OK;
+}
+
+int towr_gpu_variable_bounds_with(towr_gpu_handle h, int32_t n_data, const towr_data_t* data, double* lower, double* upper) {
+  if (!h || !lower || !upper || n_data < 0 || (n_data > 0 && !data)) return fail(h, TOWR_ERR_INVALID, "null argument or bad side data");
+  std::vector<double> lo((size_t)h->L.n), up((size_t)h->L.n);   // (a refused entry leaves the caller's arrays alone)
+  std::string err;
+  if (int rc = build_var_bounds(h->L, n_data, data, lo.data(), up.data(), err)) return fail(h, rc, err);
+  if (h->L.n) {
+    std::memcpy(lower, lo.data(), sizeof(double) * lo.size());
+    std::memcpy(upper, up.data(), sizeof(double) * up.size());
+  }
   return TOWR_OK;
 }
 
@@ -1921,6 +1950,37 @@ int towr_gpu_residual_batch_device(towr_gpu_handle h, int32_t B, const double* G
   return launch_residual(h, B, G, ldg, GL, GU, ldb, LAM, ldl, rho, LAMP, ldlp, SUM, lds, reinterpret_cast<hipStream_t>(stream));
 }
 
+// The chunks of towr_gpu_eval_auglag_batch_device, shared with towr_gpu_auglag_step_batch_device (the caller holds the
+// scratch: scratch_acquire / scratch_release)
+static int auglag_chunks(towr_gpu_handle h, int B, const double* X, int64_t ldx, const double* GL, const double* GU, int64_t ldb,
+                         const double* LAM, int64_t ldl, double rho, double* G, int64_t ldg, double* LAMP, int64_t ldlp,
+                         double* SUM, int64_t lds, double* Z, int64_t ldz, int32_t accumulate, hipStream_t s,
+                         const towr_terrain_t* ter, int per) {
+  const Layout& L = h->L;
+  constexpr int64_t kAutoBytes = int64_t(2) << 30;   // the automatic chunk of towr_gpu_eval_products_batch_device
+  const int64_t ldv = std::max<int64_t>(16, (L.nnz + 15) & ~int64_t(15));
+  const int64_t ldr = std::max<int64_t>(16, ((int64_t)L.m + 15) & ~int64_t(15));
+  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ldv));
+  const int64_t parts = (B + cap - 1) / cap;
+  const int C = (int)std::min<int64_t>(B, h->products_chunk > 0 ? h->products_chunk : (B + parts - 1) / parts);
+  int rc = scratch_grow(h, &h->d_pv, &h->pv_cap, C, ldv);
+  if (rc == TOWR_OK && !G) rc = scratch_grow(h, &h->d_rg, &h->rg_cap, C, ldr);
+  if (rc == TOWR_OK && !LAMP) rc = scratch_grow(h, &h->d_rl, &h->rl_cap, C, ldr);
+  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
+    const int cb = std::min(C, B - c0);
+    double* g = G ? G + (int64_t)c0 * ldg : h->d_rg;
+    const int64_t lg = G ? ldg : ldr;
+    double* lp = LAMP ? LAMP + (int64_t)c0 * ldlp : h->d_rl;
+    const int64_t llp = LAMP ? ldlp : ldr;
+    rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, g, lg, h->d_pv, ldv, 1, 1, s, per ? ter + c0 : ter, per, -1);
+    if (rc == TOWR_OK)
+      rc = launch_residual(h, cb, g, lg, GL ? GL + (int64_t)c0 * ldb : nullptr, GL ? GU + (int64_t)c0 * ldb : nullptr, ldb,
+                           LAM ? LAM + (int64_t)c0 * ldl : nullptr, ldl, rho, lp, llp, SUM + (int64_t)c0 * lds, lds, s);
+    if (rc == TOWR_OK) rc = launch_product(h, true, cb, h->d_pv, ldv, lp, llp, Z + (int64_t)c0 * ldz, ldz, accumulate != 0, s);
+  }
+  return rc;
+}
+
 // As towr_gpu_eval_products_batch_device: a chunk of problems at a time through the handle's scratch (the values in
 // d_pv; g and lam+ in d_rg / d_rl when the caller does not want them), the three launches of a chunk back to back on
 // the caller's stream.
@@ -1940,28 +2000,102 @@ int towr_gpu_eval_auglag_batch_device(towr_gpu_handle h, int32_t B, const double
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (int rc = products_ready(h)) return rc;
   if (int rc = residual_ready(h)) return rc;
-  constexpr int64_t kAutoBytes = int64_t(2) << 30;   // the automatic chunk of towr_gpu_eval_products_batch_device
-  const int64_t ldv = std::max<int64_t>(16, (L.nnz + 15) & ~int64_t(15));
-  const int64_t ldr = std::max<int64_t>(16, ((int64_t)L.m + 15) & ~int64_t(15));
-  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ldv));
-  const int64_t parts = (B + cap - 1) / cap;
-  const int C = (int)std::min<int64_t>(B, h->products_chunk > 0 ? h->products_chunk : (B + parts - 1) / parts);
   if (int rc = scratch_acquire(h, s)) return rc;
-  int rc = scratch_grow(h, &h->d_pv, &h->pv_cap, C, ldv);
-  if (rc == TOWR_OK && !G) rc = scratch_grow(h, &h->d_rg, &h->rg_cap, C, ldr);
-  if (rc == TOWR_OK && !LAMP) rc = scratch_grow(h, &h->d_rl, &h->rl_cap, C, ldr);
-  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
-    const int cb = std::min(C, B - c0);
-    double* g = G ? G + (int64_t)c0 * ldg : h->d_rg;
-    const int64_t lg = G ? ldg : ldr;
-    double* lp = LAMP ? LAMP + (int64_t)c0 * ldlp : h->d_rl;
-    const int64_t llp = LAMP ? ldlp : ldr;
-    rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, g, lg, h->d_pv, ldv, 1, 1, s, per ? ter + c0 : ter, per, -1);
-    if (rc == TOWR_OK)
-      rc = launch_residual(h, cb, g, lg, GL ? GL + (int64_t)c0 * ldb : nullptr, GL ? GU + (int64_t)c0 * ldb : nullptr, ldb,
-                           LAM ? LAM + (int64_t)c0 * ldl : nullptr, ldl, rho, lp, llp, SUM + (int64_t)c0 * lds, lds, s);
-    if (rc == TOWR_OK) rc = launch_product(h, true, cb, h->d_pv, ldv, lp, llp, Z + (int64_t)c0 * ldz, ldz, accumulate != 0, s);
+  const int rc = auglag_chunks(h, B, X, ldx, GL, GU, ldb, LAM, ldl, rho, G, ldg, LAMP, ldlp, SUM, lds, Z, ldz, accumulate, s, ter, per);
+  const int rr = scratch_release(h, s);
+  return rc ? rc : rr;
+}
+
+// ---- steps (step.hip) ----------------------------------------------------------------------------------------------
+// The step kernel's tables, on the first step call of the handle (synchronous copies, as residual_ready): the variable
+// sets' column ranges and the description's variable bounds.
+static int step_ready(towr_gpu_handle h) {
+  if (h->step_ready) return TOWR_OK;
+  const Layout& L = h->L;
+  std::vector<int32_t> col0;
+  for (const VarSetInfo& v : L.varsets) col0.push_back(v.col0);
+  col0.push_back(L.n);
+  int32_t* d_col0 = nullptr;
+  double *lo = nullptr, *up = nullptr;
+  int r = 0;
+  (void)((r = upload(h, &d_col0, col0)) || (r = upload(h, &lo, L.x_lower)) || (r = upload(h, &up, L.x_upper)));
+  if (r) {
+    void* all[] = {d_col0, lo, up};
+    for (void* p : all) if (p) (void)hipFree(p);
+    return r;
   }
+  h->d_set_col0 = d_col0; h->d_xlo = lo; h->d_xup = up;
+  h->step_ready = true;
+  return TOWR_OK;
+}
+
+// the argument checks the step entry and the fused entry share (before anything runs)
+static int step_args(towr_gpu_handle h, const double* ALPHA, double alpha, const double* XL, const double* XU, int64_t ldb,
+                     int64_t ldxp, bool xp, const double* SUM, int64_t lds) {
+  const Layout& L = h->L;
+  if (!SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
+  if (lds < 5 + (int64_t)L.varsets.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 5 + n_varsets");
+  if ((XL == nullptr) != (XU == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XL / XU given");
+  if (XL && ldb != 0 && ldb < L.n) return fail(h, TOWR_ERR_INVALID, "ldb must be 0 (shared bounds) or >= n");
+  if (!ALPHA && alpha != alpha) return fail(h, TOWR_ERR_INVALID, "alpha is NaN");
+  if (xp && ldxp < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of XP smaller than n");
+  return TOWR_OK;
+}
+
+static int launch_step(towr_gpu_handle h, int B, const double* X, int64_t ldx, const double* D, int64_t ldd, const double* ALPHA,
+                       double alpha, const double* XL, const double* XU, int64_t ldb, double* XP, int64_t ldxp, double* SUM,
+                       int64_t lds, hipStream_t s) {
+  StepArgs a{};
+  a.X = X; a.ldx = ldx; a.D = D; a.ldd = ldd; a.ALPHA = ALPHA; a.alpha = alpha;
+  a.XL = XL ? XL : h->d_xlo; a.XU = XL ? XU : h->d_xup; a.ldb = XL ? ldb : 0;
+  a.XP = XP; a.ldxp = ldxp; a.SUM = SUM; a.lds = lds;
+  a.set_col0 = h->d_set_col0; a.n = h->L.n; a.n_sets = (int32_t)h->L.varsets.size();
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(step_kernel(), dim3((unsigned)B), dim3(kStepBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+int towr_gpu_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* D, int64_t ldd,
+                               const double* ALPHA, double alpha, const double* XL, const double* XU, int64_t ldb,
+                               double* XP, int64_t ldxp, double* SUM, int64_t lds, void* stream) {
+  if (!h || B < 0 || !X || !D) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or D, or B < 0)");
+  if (ldx < h->L.n || ldd < h->L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X or D smaller than n");
+  if (int rc = step_args(h, ALPHA, alpha, XL, XU, ldb, ldxp, XP != nullptr, SUM, lds)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = step_ready(h)) return rc;
+  return launch_step(h, B, X, ldx, D, ldd, ALPHA, alpha, XL, XU, ldb, XP, ldxp, SUM, lds, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The gradient of the whole batch in handle scratch (d_sd: grad f from the cost launch, then + J^T lam+ per chunk of
+// the auglag sequence), the step kernel behind it: what the three public calls launch, on the caller's stream.
+int towr_gpu_auglag_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* GL, const double* GU,
+                                      int64_t ldgb, const double* LAM, int64_t ldl, double rho, const double* ALPHA, double alpha,
+                                      const double* XL, const double* XU, int64_t ldxb, double* F, double* G, int64_t ldg,
+                                      double* LAMP, int64_t ldlp, double* RSUM, int64_t ldrs, double* XP, int64_t ldxp,
+                                      double* SSUM, int64_t ldss, void* stream) {
+  if (!h || B < 0 || !X || !XP) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or XP, or B < 0)");
+  const Layout& L = h->L;
+  if (ldx < L.n || (G && ldg < L.m)) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X) / m (G)");
+  if (int rc = residual_args(h, GL, GU, ldgb, LAM, ldl, rho, true, LAMP ? ldlp : L.m, RSUM, ldrs)) return rc;
+  if (int rc = step_args(h, ALPHA, alpha, XL, XU, ldxb, ldxp, true, SSUM, ldss)) return rc;
+  if (int rc = bind(h)) return rc;
+  const towr_terrain_t* ter;
+  int per;
+  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
+  if (B == 0) return TOWR_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = products_ready(h)) return rc;
+  if (int rc = residual_ready(h)) return rc;
+  if (int rc = step_ready(h)) return rc;
+  const int64_t ldn = std::max<int64_t>(16, ((int64_t)L.n + 15) & ~int64_t(15));   // rows on 128-byte boundaries
+  if (int rc = scratch_acquire(h, s)) return rc;
+  int rc = scratch_grow(h, &h->d_sd, &h->sd_cap, B, ldn);
+  if (rc == TOWR_OK && !F) rc = scratch_grow(h, &h->d_sf, &h->sf_cap, B, 1);
+  if (rc == TOWR_OK) rc = launch_cost(h, B, X, ldx, F ? F : h->d_sf, h->d_sd, ldn, s, ter, per);
+  if (rc == TOWR_OK)
+    rc = auglag_chunks(h, B, X, ldx, GL, GU, ldgb, LAM, ldl, rho, G, ldg, LAMP, ldlp, RSUM, ldrs, h->d_sd, ldn, 1, s, ter, per);
+  if (rc == TOWR_OK) rc = launch_step(h, B, X, ldx, h->d_sd, ldn, ALPHA, alpha, XL, XU, ldxb, XP, ldxp, SSUM, ldss, s);
   const int rr = scratch_release(h, s);
   return rc ? rc : rr;
 }

@@ -404,6 +404,19 @@ class Parameters:
         self.base_rom_ay = (-1e20, 1e20)
         self.base_rom_lz = (-1e20, 1e20)
         self.angular_rep_ = 0  # EulerZYX
+        # what only the variable bounds use (parameters.h:179-313, parameters.cc:65-96; var_bounds_data)
+        self.bounds_final_lin_pos_: List[int] = [0, 1, 2]
+        self.bounds_final_lin_vel_: List[int] = [0, 1, 2]
+        self.bounds_final_ang_pos_: List[int] = [0, 1, 2]
+        self.bounds_final_ang_vel_: List[int] = [0, 1, 2]
+        self.constrain_base_pitch_ = False
+        self.base_pitch_target_ = 0.0
+        self.base_lin_waypoints_: List["BaseWaypoint"] = []
+        self.base_ang_waypoints_: List["BaseWaypoint"] = []
+        self.enable_stance_tracking = True
+        self.ee_stance_position_: List[List[Tuple[float, float, float]]] = []   # [ee][k-th stance phase]
+        self.enable_stance_rpy_tracking = True
+        self.ee_stance_rpy_: List[List[Tuple[float, float, float]]] = []
 
     def OptimizePhaseDurations(self):
         self.constraints_.append(Parameters.TotalTime)
@@ -453,6 +466,36 @@ class EELinearConstraintDef:
     deriv: int = 0
     tolerance: float = 0.0
     dt: float = 0.1
+
+
+@dataclass
+class BaseWaypoint:
+    """Parameters::BaseWaypoint (parameters.h:301-307): a bound on a base node value at time t; tolerance all zero
+    is an equality, else [value - tolerance, value + tolerance] per axis."""
+    t: float
+    deriv: int
+    dims: List[int]
+    value: Tuple[float, float, float]
+    tolerance: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+
+
+def _phase_polys(phase_count, first_constant, n_changing):
+    """NodesVariablesPhaseBased's polynomials as (phase, is_constant) (nodes_variables_phase_based.cc:39-73)."""
+    polys, const = [], first_constant
+    for ph in range(phase_count):
+        polys += [(ph, True)] if const else [(ph, False)] * n_changing
+        const = not const
+    return polys
+
+
+def _is_constant_node(polys, node):
+    """IsConstantNode (nodes_variables_phase_based.cc:101-113)"""
+    last = len(polys)
+    if node == 0:
+        return polys[0][1]
+    if node == last:
+        return polys[last - 1][1]
+    return polys[node - 1][1] or polys[node][1]
 
 
 @dataclass
@@ -557,6 +600,160 @@ class NlpFormulation:
                 out.append((capi.DATA_BOUNDS, i, [float(d) for d in P.rom_swing_relax_dims_]))
         return out
 
+    def init_desc(self, init_mode=capi.INIT_FORMULATION, ee_goal=None) -> capi.InitDesc:
+        """The start / goal states as the description carries them (to_desc's `init`)."""
+        it = capi.InitDesc()
+        it.mode = init_mode
+        b0, b1 = self.initial_base_, self.final_base_
+        for k in range(3):
+            it.base_lin_p0[k], it.base_lin_v0[k] = b0.lin_p[k], b0.lin_v[k]
+            it.base_ang_p0[k], it.base_ang_v0[k] = b0.ang_p[k], b0.ang_v[k]
+            it.base_lin_p1[k], it.base_lin_v1[k] = b1.lin_p[k], b1.lin_v[k]
+            it.base_ang_p1[k], it.base_ang_v1[k] = b1.ang_p[k], b1.ang_v[k]
+        for ee in range(min(self.params_.GetEECount(), len(self.initial_ee_W_))):
+            for k in range(3):
+                it.ee_p0[ee][k] = self.initial_ee_W_[ee][k]
+                if ee_goal is not None:
+                    it.ee_p1[ee][k] = ee_goal[ee][k]
+        return it
+
+    def var_bounds_data(self, varsets=None, init=None, terrain=None, init_mode=capi.INIT_FORMULATION, ee_goal=None,
+                        total_time=None) -> List[Tuple[int, int, List[float]]]:
+        """Side data TOWR_DATA_VAR_BOUNDS for the variable-set list (default: variable_sets()), as (kind, variable set
+        index, doubles): the bound calls of MakeBaseVariables .. MakeTorqueVariables (nlp_formulation.cc:121-346)
+        restated as records (node, deriv, dim, lower, upper), one per NodesVariables::AddBound call, in call order.
+        `init` (a capi.InitDesc) / `terrain` (a capi.Terrain or HeightMap): another instance's start / goal states and
+        terrain on the same layout (default: this formulation's, with init_mode / ee_goal as to_desc). A procedural
+        init (capi.INIT_PROCEDURAL) gives the records of towr/test/procedural_example.cc:136-158."""
+        P, E = self.params_, self.params_.GetEECount()
+        it = init if init is not None else self.init_desc(init_mode, ee_goal)
+        ter = self.terrain_ if terrain is None else terrain
+        if isinstance(ter, capi.Terrain):
+            ter = HeightMap(ter.id, list(ter.p), ter.friction_coeff)
+        T = P.GetTotalTime() if total_time is None else total_time
+        n_base, left = 1, T                                  # GetBasePolyDurations().size() + 1 (parameters.cc:114-130)
+        while left > 1e-10:
+            n_base += 1
+            left -= P.duration_base_polynomial_
+        km, dm = self.model_.kinematic_model, self.model_.dynamic_model
+        XYZ, zero3 = [0, 1, 2], (0.0, 0.0, 0.0)
+        kPos, kVel, kAcc = 0, 1, 2
+        lin_p0, lin_v0, lin_p1, lin_v1 = list(it.base_lin_p0), list(it.base_lin_v0), list(it.base_lin_p1), list(it.base_lin_v1)
+        ang_p0, ang_v0, ang_p1, ang_v1 = list(it.base_ang_p0), list(it.base_ang_v0), list(it.base_ang_p1), list(it.base_ang_v1)
+
+        def add(rec, node, deriv, dims, lower, upper=None):   # AddBounds (nodes_variables.cc:219-250)
+            for dim in dims:
+                rec += [float(node), float(deriv), float(dim), float(lower[dim]),
+                        float((lower if upper is None else upper)[dim])]
+
+        def waypoints(rec, wps):                              # apply_waypoints (nlp_formulation.cc:166-179)
+            for wp in wps:
+                q = wp.t / P.duration_base_polynomial_
+                nid = int(math.copysign(math.floor(abs(q) + 0.5), q))   # std::round
+                nid = max(0, min(nid, n_base - 1))
+                if all(v == 0.0 for v in wp.tolerance):
+                    add(rec, nid, wp.deriv, wp.dims, wp.value)
+                else:
+                    add(rec, nid, wp.deriv, wp.dims, [wp.value[k] - wp.tolerance[k] for k in range(3)],
+                        [wp.value[k] + wp.tolerance[k] for k in range(3)])
+
+        def stance_nodes(ee):
+            """The node at the start of every stance phase of an ee-motion / ee-angle set: the loops of
+            nlp_formulation.cc:222-230 / :267-275, which skip the phase after a hit."""
+            polys = _phase_polys(len(P.ee_phase_durations_[ee]), bool(P.ee_in_contact_at_start_[ee]),
+                                 P.ee_polynomials_per_swing_phase_)
+            out, phase = [], 0
+            while phase < len(P.ee_phase_durations_[ee]):
+                node = [i for i, (ph, _) in enumerate(polys) if ph == phase][0]   # GetNodeIDAtStartOfPhase
+                if _is_constant_node(polys, node):
+                    out.append(node)
+                    phase += 1
+                phase += 1
+            return out
+
+        def last_node(ee, first_constant, n_changing):
+            return len(_phase_polys(len(P.ee_phase_durations_[ee]), first_constant, n_changing))
+
+        out = []
+        for i, (kind, ee) in enumerate(self.variable_sets() if varsets is None else varsets):
+            rec: List[float] = []
+            cs = bool(P.ee_in_contact_at_start_[ee]) if kind not in (capi.VAR_BASE_LIN, capi.VAR_BASE_ANG) else False
+            if kind == capi.VAR_EE_SCHEDULE:
+                continue                                      # PhaseDurations: bound_phase_duration, in the description
+            if it.mode == capi.INIT_PROCEDURAL:               # procedural_example.cc:136-158
+                if kind == capi.VAR_BASE_LIN:
+                    add(rec, 0, kPos, XYZ, lin_p0)
+                    add(rec, 0, kVel, XYZ, zero3)
+                    add(rec, n_base - 1, kPos, XYZ, lin_p1)
+                    add(rec, n_base - 1, kVel, XYZ, zero3)
+                elif kind == capi.VAR_BASE_ANG:
+                    add(rec, 0, kPos, XYZ, ang_p0)
+                    add(rec, 0, kVel, XYZ, zero3)
+                    add(rec, n_base - 1, kPos, XYZ, ang_p1)
+                    add(rec, n_base - 1, kVel, XYZ, zero3)
+                elif kind == capi.VAR_EE_MOTION:
+                    add(rec, 0, kPos, XYZ, list(it.ee_p0[ee]))
+                    add(rec, last_node(ee, cs, P.ee_polynomials_per_swing_phase_), kPos, XYZ, list(it.ee_p1[ee]))
+                elif kind == capi.VAR_EE_ANG:
+                    add(rec, 0, kPos, XYZ, ang_p0)
+                    add(rec, last_node(ee, cs, P.ee_polynomials_per_swing_phase_), kPos, XYZ, ang_p1)
+            elif kind == capi.VAR_BASE_LIN:                   # MakeBaseVariables (:136-141, :180)
+                add(rec, 0, kPos, XYZ, lin_p0)
+                add(rec, 0, kVel, XYZ, lin_v0)
+                add(rec, 0, kAcc, XYZ, zero3)
+                add(rec, n_base - 1, kPos, P.bounds_final_lin_pos_, lin_p1)
+                add(rec, n_base - 1, kVel, P.bounds_final_lin_vel_, lin_v1)
+                add(rec, n_base - 1, kAcc, XYZ, zero3)
+                waypoints(rec, P.base_lin_waypoints_)
+            elif kind == capi.VAR_BASE_ANG:                   # (:146-162, :181)
+                add(rec, 0, kPos, XYZ, ang_p0)
+                add(rec, 0, kVel, XYZ, ang_v0)
+                add(rec, 0, kAcc, XYZ, zero3)
+                add(rec, n_base - 1, kPos, P.bounds_final_ang_pos_, ang_p1)
+                add(rec, n_base - 1, kVel, P.bounds_final_ang_vel_, ang_v1)
+                add(rec, n_base - 1, kAcc, XYZ, zero3)
+                if P.constrain_base_pitch_:
+                    for node in range(n_base):
+                        add(rec, node, kPos, [1], (0.0, P.base_pitch_target_, 0.0))
+                        add(rec, node, kVel, [1], zero3)
+                waypoints(rec, P.base_ang_waypoints_)
+            elif kind == capi.VAR_EE_MOTION:                  # MakeEndeffectorVariables (:203-236)
+                if P.enable_stance_tracking:
+                    if ee >= len(P.ee_stance_position_):
+                        raise ValueError("enable_stance_tracking needs ee_stance_position_ of every endeffector")
+                    for k, node in enumerate(stance_nodes(ee)):
+                        if k >= len(P.ee_stance_position_[ee]):
+                            raise ValueError("ee_stance_position_ holds fewer positions than the endeffector has stance phases")
+                        pos = P.ee_stance_position_[ee][k]
+                        add(rec, node, kPos, [0, 1], (pos[0], pos[1], 0.0))
+                else:
+                    R = _euler_zyx((0.0, 0.0, ang_p1[2]))
+                    ns = km.nominal_stance[ee]
+                    fx, fy = [lin_p1[q] + (R[q][0] * ns[0] + R[q][1] * ns[1] + R[q][2] * ns[2]) for q in range(2)]
+                    add(rec, 0, kPos, XYZ, list(it.ee_p0[ee]))
+                    add(rec, last_node(ee, cs, P.ee_polynomials_per_swing_phase_), kPos, XYZ, (fx, fy, ter.GetHeight(fx, fy)))
+            elif kind == capi.VAR_EE_ANG:                     # MakeEndeffectorAngVariables (:261-281)
+                if P.enable_stance_rpy_tracking and ee < len(P.ee_stance_rpy_) and P.ee_stance_rpy_[ee]:
+                    for k, node in enumerate(stance_nodes(ee)):
+                        if k >= len(P.ee_stance_rpy_[ee]):
+                            raise ValueError("ee_stance_rpy_ holds fewer angles than the endeffector has stance phases")
+                        add(rec, node, kPos, XYZ, P.ee_stance_rpy_[ee][k])
+                else:
+                    add(rec, 0, kPos, XYZ, ang_p0)
+                    add(rec, last_node(ee, cs, P.ee_polynomials_per_swing_phase_), kPos, XYZ, ang_p1)
+            elif kind in (capi.VAR_EE_FORCE, capi.VAR_EE_TORQUE):   # MakeForceVariables / MakeTorqueVariables (:309-340)
+                force = kind == capi.VAR_EE_FORCE
+                stance = (0.0, 0.0, dm.mass * dm.g / E) if force else zero3
+                last = last_node(ee, not cs, P.force_polynomials_per_stance_phase_ if force
+                                 else P.torque_polynomials_per_stance_phase_)
+                add(rec, 0, kPos, XYZ, stance)
+                add(rec, last, kPos, XYZ, stance)
+                add(rec, 0, kVel, XYZ, zero3)
+                add(rec, last, kVel, XYZ, zero3)
+            if rec:
+                out.append((capi.DATA_VAR_BOUNDS, i, rec))
+        return out
+
     # cost terms in NlpFormulation::GetCosts order (nlp_formulation.cc:604-680)
     def cost_terms(self) -> List[dict]:
         P, E = self.params_, self.params_.GetEECount()
@@ -655,19 +852,7 @@ class NlpFormulation:
                 d.costs[i].p[j] = v
             for j, v in enumerate(c.get("ip", [])):
                 d.costs[i].ip[j] = v
-        it = d.init
-        it.mode = init_mode
-        b0, b1 = self.initial_base_, self.final_base_
-        for k in range(3):
-            it.base_lin_p0[k], it.base_lin_v0[k] = b0.lin_p[k], b0.lin_v[k]
-            it.base_ang_p0[k], it.base_ang_v0[k] = b0.ang_p[k], b0.ang_v[k]
-            it.base_lin_p1[k], it.base_lin_v1[k] = b1.lin_p[k], b1.lin_v[k]
-            it.base_ang_p1[k], it.base_ang_v1[k] = b1.ang_p[k], b1.ang_v[k]
-        for ee in range(min(E, len(self.initial_ee_W_))):
-            for k in range(3):
-                it.ee_p0[ee][k] = self.initial_ee_W_[ee][k]
-                if ee_goal is not None:
-                    it.ee_p1[ee][k] = ee_goal[ee][k]
+        d.init = self.init_desc(init_mode, ee_goal)
         return d
 
 

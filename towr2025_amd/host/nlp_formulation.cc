@@ -1,6 +1,7 @@
 // nlp_formulation.cc — see nlp_formulation.hpp. Reference file:line per function.
 #include "nlp_formulation.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -339,6 +340,165 @@ std::vector<BoundsEntry> NlpFormulation::BoundsData() const {
     if (cs[i].kind == TOWR_C_EE_LINEAR) out.push_back({(int)i, {P.ee_linear_constraints_.at(k++).tolerance}});
     else if (cs[i].kind == TOWR_C_RANGE_OF_MOTION && !P.rom_swing_relax_dims_.empty())
       out.push_back({(int)i, std::vector<double>(P.rom_swing_relax_dims_.begin(), P.rom_swing_relax_dims_.end())});
+  }
+  return out;
+}
+
+std::vector<BoundsEntry> NlpFormulation::VarBoundsData() const {
+  return VarBoundsData(GetVariableSets(), MakeDesc().init, terrain_, params_.GetTotalTime());
+}
+
+// MakeBaseVariables .. MakeTorqueVariables (nlp_formulation.cc:121-346): every AddBound call as one record
+std::vector<BoundsEntry> NlpFormulation::VarBoundsData(const std::vector<VarSet>& vs, const towr_init_t& it, const HeightMap& ter,
+                                                       double total_time) const {
+  const Parameters& P = params_;
+  const int E = P.GetEECount();
+  int n_base = 1;   // GetBasePolyDurations().size() + 1 (parameters.cc:114-130)
+  for (double left = total_time; left > 1e-10; left -= P.duration_base_polynomial_) ++n_base;
+  const std::vector<int> XYZ{0, 1, 2};
+  const double zero3[3] = {0.0, 0.0, 0.0};
+  enum { kPos = 0, kVel = 1, kAcc = 2 };
+  using Rec = std::vector<double>;
+  auto add2 = [](Rec& rec, int node, int deriv, const std::vector<int>& dims, const double* lower, const double* upper) {
+    for (int dim : dims) {   // AddBounds (nodes_variables.cc:219-250)
+      const double r[5] = {(double)node, (double)deriv, (double)dim, lower[dim], upper[dim]};
+      rec.insert(rec.end(), r, r + 5);
+    }
+  };
+  auto add = [&](Rec& rec, int node, int deriv, const std::vector<int>& dims, const double* val) { add2(rec, node, deriv, dims, val, val); };
+  auto waypoints = [&](Rec& rec, const std::vector<Parameters::BaseWaypoint>& wps) {   // apply_waypoints (:166-179)
+    for (const auto& wp : wps) {
+      int nid = (int)std::round(wp.t / P.duration_base_polynomial_);
+      nid = std::max(0, std::min(nid, n_base - 1));
+      if (wp.tolerance[0] == 0.0 && wp.tolerance[1] == 0.0 && wp.tolerance[2] == 0.0) {
+        add(rec, nid, wp.deriv, wp.dims, wp.value.data());
+      } else {
+        double lo[3], up[3];
+        for (int k = 0; k < 3; ++k) { lo[k] = wp.value[k] - wp.tolerance[k]; up[k] = wp.value[k] + wp.tolerance[k]; }
+        add2(rec, nid, wp.deriv, wp.dims, lo, up);
+      }
+    }
+  };
+  // NodesVariablesPhaseBased's polynomials as (phase, is_constant) (nodes_variables_phase_based.cc:39-73)
+  using Polys = std::vector<std::pair<int, bool>>;
+  auto phase_polys = [&](int ee, bool first_constant, int n_changing) {
+    Polys polys;
+    bool c = first_constant;
+    for (int ph = 0; ph < (int)P.ee_phase_durations_.at(ee).size(); ++ph, c = !c)
+      for (int j = 0; j < (c ? 1 : n_changing); ++j) polys.push_back({ph, c});
+    return polys;
+  };
+  auto is_constant_node = [](const Polys& polys, int node) {   // :101-113
+    const int last = (int)polys.size();
+    if (node == 0) return polys[0].second;
+    if (node == last) return polys[last - 1].second;
+    return polys[node - 1].second || polys[node].second;
+  };
+  // the node at the start of every stance phase of an ee-motion / ee-angle set: the loops of :222-230 / :267-275,
+  // which skip the phase after a hit
+  auto stance_nodes = [&](int ee) {
+    const Polys polys = phase_polys(ee, P.ee_in_contact_at_start_.at(ee), P.ee_polynomials_per_swing_phase_);
+    std::vector<int> out;
+    for (int phase = 0; phase < (int)P.ee_phase_durations_.at(ee).size(); ++phase) {
+      int node = 0;
+      while (polys[node].first != phase) ++node;   // GetNodeIDAtStartOfPhase
+      if (!is_constant_node(polys, node)) continue;
+      out.push_back(node);
+      ++phase;
+    }
+    return out;
+  };
+  std::vector<BoundsEntry> out;
+  for (size_t i = 0; i < vs.size(); ++i) {
+    const int kind = vs[i].kind, ee = vs[i].ee;
+    if (kind == TOWR_VAR_EE_SCHEDULE) continue;   // PhaseDurations: bound_phase_duration, in the description
+    const bool base = kind == TOWR_VAR_BASE_LIN || kind == TOWR_VAR_BASE_ANG;
+    const bool cs = base ? false : (bool)P.ee_in_contact_at_start_.at(ee);
+    const int last_swing = base ? 0 : (int)phase_polys(ee, cs, P.ee_polynomials_per_swing_phase_).size();
+    Rec rec;
+    if (it.mode == TOWR_INIT_PROCEDURAL) {   // procedural_example.cc:136-158
+      if (kind == TOWR_VAR_BASE_LIN) {
+        add(rec, 0, kPos, XYZ, it.base_lin_p0);
+        add(rec, 0, kVel, XYZ, zero3);
+        add(rec, n_base - 1, kPos, XYZ, it.base_lin_p1);
+        add(rec, n_base - 1, kVel, XYZ, zero3);
+      } else if (kind == TOWR_VAR_BASE_ANG) {
+        add(rec, 0, kPos, XYZ, it.base_ang_p0);
+        add(rec, 0, kVel, XYZ, zero3);
+        add(rec, n_base - 1, kPos, XYZ, it.base_ang_p1);
+        add(rec, n_base - 1, kVel, XYZ, zero3);
+      } else if (kind == TOWR_VAR_EE_MOTION) {
+        add(rec, 0, kPos, XYZ, it.ee_p0[ee]);
+        add(rec, last_swing, kPos, XYZ, it.ee_p1[ee]);
+      } else if (kind == TOWR_VAR_EE_ANG) {
+        add(rec, 0, kPos, XYZ, it.base_ang_p0);
+        add(rec, last_swing, kPos, XYZ, it.base_ang_p1);
+      }
+    } else if (kind == TOWR_VAR_BASE_LIN) {   // MakeBaseVariables (:136-141, :180)
+      add(rec, 0, kPos, XYZ, it.base_lin_p0);
+      add(rec, 0, kVel, XYZ, it.base_lin_v0);
+      add(rec, 0, kAcc, XYZ, zero3);
+      add(rec, n_base - 1, kPos, P.bounds_final_lin_pos_, it.base_lin_p1);
+      add(rec, n_base - 1, kVel, P.bounds_final_lin_vel_, it.base_lin_v1);
+      add(rec, n_base - 1, kAcc, XYZ, zero3);
+      waypoints(rec, P.base_lin_waypoints_);
+    } else if (kind == TOWR_VAR_BASE_ANG) {   // (:146-162, :181)
+      add(rec, 0, kPos, XYZ, it.base_ang_p0);
+      add(rec, 0, kVel, XYZ, it.base_ang_v0);
+      add(rec, 0, kAcc, XYZ, zero3);
+      add(rec, n_base - 1, kPos, P.bounds_final_ang_pos_, it.base_ang_p1);
+      add(rec, n_base - 1, kVel, P.bounds_final_ang_vel_, it.base_ang_v1);
+      add(rec, n_base - 1, kAcc, XYZ, zero3);
+      if (P.constrain_base_pitch_) {
+        const double target[3] = {0.0, P.base_pitch_target_, 0.0};
+        for (int node = 0; node < n_base; ++node) {
+          add(rec, node, kPos, {1}, target);
+          add(rec, node, kVel, {1}, zero3);
+        }
+      }
+      waypoints(rec, P.base_ang_waypoints_);
+    } else if (kind == TOWR_VAR_EE_MOTION) {   // MakeEndeffectorVariables (:203-236)
+      if (P.enable_stance_tracking) {
+        if (ee >= (int)P.ee_stance_position_.size()) throw std::out_of_range("enable_stance_tracking needs ee_stance_position_ of every endeffector");
+        const std::vector<int> nodes = stance_nodes(ee);
+        for (size_t k = 0; k < nodes.size(); ++k) {
+          if (k >= P.ee_stance_position_[ee].size()) throw std::out_of_range("ee_stance_position_ holds fewer positions than the endeffector has stance phases");
+          const double pos[3] = {P.ee_stance_position_[ee][k][0], P.ee_stance_position_[ee][k][1], 0.0};
+          add(rec, nodes[k], kPos, {0, 1}, pos);
+        }
+      } else {
+        const double yaw = it.base_ang_p1[2], sz = std::sin(yaw), cz = std::cos(yaw);
+        // EulerConverter::GetRotationMatrixBaseToWorld of (0, 0, yaw) (euler_converter.cc:207-221), rows 0 and 1
+        const double sx = std::sin(0.0), cx = std::cos(0.0), sy = std::sin(0.0), cy = std::cos(0.0);
+        const double R[2][3] = {{cy * cz, cz * sx * sy - cx * sz, sx * sz + cx * cz * sy}, {cy * sz, cx * cz + sx * sy * sz, cx * sy * sz - cz * sx}};
+        const Vector3d& ns = model_.kinematic_model.nominal_stance.at(ee);
+        double fin[3];
+        for (int q = 0; q < 2; ++q) fin[q] = it.base_lin_p1[q] + (R[q][0] * ns[0] + R[q][1] * ns[1] + R[q][2] * ns[2]);
+        fin[2] = ter.GetHeight(fin[0], fin[1]);
+        add(rec, 0, kPos, XYZ, it.ee_p0[ee]);
+        add(rec, last_swing, kPos, XYZ, fin);
+      }
+    } else if (kind == TOWR_VAR_EE_ANG) {   // MakeEndeffectorAngVariables (:261-281)
+      if (P.enable_stance_rpy_tracking && ee < (int)P.ee_stance_rpy_.size() && !P.ee_stance_rpy_[ee].empty()) {
+        const std::vector<int> nodes = stance_nodes(ee);
+        for (size_t k = 0; k < nodes.size(); ++k) {
+          if (k >= P.ee_stance_rpy_[ee].size()) throw std::out_of_range("ee_stance_rpy_ holds fewer angles than the endeffector has stance phases");
+          add(rec, nodes[k], kPos, XYZ, P.ee_stance_rpy_[ee][k].data());
+        }
+      } else {
+        add(rec, 0, kPos, XYZ, it.base_ang_p0);
+        add(rec, last_swing, kPos, XYZ, it.base_ang_p1);
+      }
+    } else if (kind == TOWR_VAR_EE_FORCE || kind == TOWR_VAR_EE_TORQUE) {   // MakeForceVariables / MakeTorqueVariables (:309-340)
+      const bool force = kind == TOWR_VAR_EE_FORCE;
+      const double stance[3] = {0.0, 0.0, force ? model_.dynamic_model.m * model_.dynamic_model.g / E : 0.0};
+      const int last = (int)phase_polys(ee, !cs, force ? P.force_polynomials_per_stance_phase_ : P.torque_polynomials_per_stance_phase_).size();
+      add(rec, 0, kPos, XYZ, stance);
+      add(rec, last, kPos, XYZ, stance);
+      add(rec, 0, kVel, XYZ, zero3);
+      add(rec, last, kVel, XYZ, zero3);
+    }
+    if (!rec.empty()) out.push_back({(int)i, rec});
   }
   return out;
 }

@@ -114,6 +114,23 @@ struct Parameters {
   std::vector<bool> ee_in_contact_at_start_;
   std::vector<double> ee_swing_height_min_, ee_swing_height_max_;
   std::array<double, 6> base_rom_{-1e20, 1e20, -1e20, 1e20, -1e20, 1e20};   // ax, ay, lz bounds
+  // what only the variable bounds use (parameters.h:179-313, parameters.cc:65-96; NlpFormulation::VarBoundsData)
+  std::vector<int> bounds_final_lin_pos_{0, 1, 2}, bounds_final_lin_vel_{0, 1, 2}, bounds_final_ang_pos_{0, 1, 2},
+      bounds_final_ang_vel_{0, 1, 2};
+  bool constrain_base_pitch_ = false;
+  double base_pitch_target_ = 0.0;
+  struct BaseWaypoint {   // parameters.h:301-307: tolerance all zero is an equality, else value -+ tolerance per axis
+    double t;
+    int deriv;
+    std::vector<int> dims;
+    std::array<double, 3> value;
+    std::array<double, 3> tolerance{};
+  };
+  std::vector<BaseWaypoint> base_lin_waypoints_, base_ang_waypoints_;
+  bool enable_stance_tracking = true;
+  std::vector<std::vector<std::array<double, 3>>> ee_stance_position_;   // [ee][k-th stance phase]
+  bool enable_stance_rpy_tracking = true;
+  std::vector<std::vector<std::array<double, 3>>> ee_stance_rpy_;
   void OptimizePhaseDurations() { constraints_.push_back(TotalTime); }
   bool IsOptimizeTimings() const;
   int GetEECount() const { return (int)ee_in_contact_at_start_.size(); }
@@ -144,6 +161,14 @@ class NlpFormulation {
   // side data TOWR_DATA_BOUNDS for GetConstraints(): each EELinear set's tolerance and, with rom_swing_relax_dims_,
   // every RangeOfMotion set's relaxed dims (nlp_formulation.cc:433-435); the same entries as formulation.py's
   std::vector<BoundsEntry> BoundsData() const;
+  // side data TOWR_DATA_VAR_BOUNDS for GetVariableSets() (or `vs`): the bound calls of MakeBaseVariables ..
+  // MakeTorqueVariables (nlp_formulation.cc:121-346) as records (node, deriv, dim, lower, upper), one per
+  // NodesVariables::AddBound call in call order; index = the variable set. `init` / `terrain`: another instance's
+  // start / goal states and terrain on the same layout (default: this formulation's). A TOWR_INIT_PROCEDURAL init
+  // gives the records of procedural_example.cc:136-158. The same entries as formulation.py's var_bounds_data.
+  std::vector<BoundsEntry> VarBoundsData() const;
+  std::vector<BoundsEntry> VarBoundsData(const std::vector<VarSet>& vs, const towr_init_t& init, const HeightMap& terrain,
+                                         double total_time) const;
   // the engine's problem description (optionally with an explicit variable / constraint list as
   // towr/test/procedural_example.cc builds, a procedural initial guess and goal footholds)
   towr_problem_desc_t MakeDesc() const;

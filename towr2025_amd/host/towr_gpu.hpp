@@ -116,6 +116,30 @@ class Engine {
     return towr_gpu_eval_auglag_batch_device(h_, B, X, ldx, GL, GU, ldb, LAM, ldl, rho, G, ldg, LAMP, ldlp, SUM, lds, Z, ldz,
                                              accumulate ? 1 : 0, stream);
   }
+  // the bounds on x in column order (ifopt's GetBounds of every variable set; +-1e20 = no bound): from the
+  // TOWR_DATA_VAR_BOUNDS entries given at creation, from those of `data` instead (another instance on this layout),
+  // and of a list of instances as row-major B x n arrays (the per-problem rows of StepBatchDevice)
+  void GetVariableBounds(double* lower, double* upper) const { Check(towr_gpu_variable_bounds(h_, lower, upper)); }
+  void GetVariableBoundsWith(const std::vector<towr_data_t>& data, double* lower, double* upper) const {
+    Check(towr_gpu_variable_bounds_with(h_, (int32_t)data.size(), data.data(), lower, upper));
+  }
+  void GetVariableBoundsBatch(const std::vector<std::vector<towr_data_t>>& datas, double* lower, double* upper) const {
+    for (size_t b = 0; b < datas.size(); ++b) GetVariableBoundsWith(datas[b], lower + b * (size_t)n_, upper + b * (size_t)n_);
+  }
+  // the projected step XP = P_[XL, XU](X - a D) with its summary, and one augmented-Lagrangian iteration in one call
+  // (cost gradient, merit-and-gradient, step; include/towr_gpu.h); they return the status
+  int StepBatchDevice(int B, const double* X, int64_t ldx, const double* D, int64_t ldd, const double* ALPHA, double alpha,
+                      const double* XL, const double* XU, int64_t ldb, double* XP, int64_t ldxp, double* SUM, int64_t lds,
+                      void* stream) const {
+    return towr_gpu_step_batch_device(h_, B, X, ldx, D, ldd, ALPHA, alpha, XL, XU, ldb, XP, ldxp, SUM, lds, stream);
+  }
+  int AuglagStepBatchDevice(int B, const double* X, int64_t ldx, const double* GL, const double* GU, int64_t ldgb, const double* LAM,
+                            int64_t ldl, double rho, const double* ALPHA, double alpha, const double* XL, const double* XU,
+                            int64_t ldxb, double* F, double* G, int64_t ldg, double* LAMP, int64_t ldlp, double* RSUM, int64_t ldrs,
+                            double* XP, int64_t ldxp, double* SSUM, int64_t ldss, void* stream) const {
+    return towr_gpu_auglag_step_batch_device(h_, B, X, ldx, GL, GU, ldgb, LAM, ldl, rho, ALPHA, alpha, XL, XU, ldxb, F, G, ldg,
+                                             LAMP, ldlp, RSUM, ldrs, XP, ldxp, SSUM, ldss, stream);
+  }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // page-lock caller memory for in-place host transfers (towr_gpu_register_host); returns the status
   int RegisterHost(void* p, size_t bytes) const { return towr_gpu_register_host(h_, p, (int64_t)bytes); }

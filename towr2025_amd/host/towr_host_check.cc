@@ -20,6 +20,9 @@
 //        towr_host_check <cfg> --bounds [relaxed dims, e.g. 2 or 0,2]
 //   prints the C++ mirror's TOWR_DATA_BOUNDS entries ("data <constraint> <count> <values...>") and, from a layout-only
 //   engine created with them, the constraint bounds ("row <i> <lower> <upper>"), every double as %.17g.
+//        towr_host_check <cfg> --varbounds [plain|rich] [device (default -1: layout only)]
+//   prints the C++ mirror's TOWR_DATA_VAR_BOUNDS entries ("data <variable set> <count> <values...>") and, from an
+//   engine created with them, the variable bounds ("col <j> <lower> <upper>"), every double as %.17g.
 //        towr_host_check <cfg> --residual [device] [problems]
 //   evaluates a batch on the device, runs the residual kernel (the handle's bounds, random multipliers) and the fused
 //   merit-and-gradient entry, and compares them with a host loop over the bounds; prints "residual ok ..." and exits
@@ -215,6 +218,46 @@ int bounds_dump(const NlpFormulation& f) {
   return 0;
 }
 
+// --varbounds: the variable-bound knobs of the variant set on `f` (the same values as tests/test_var_bounds.py):
+//   plain  stance tracking off: the start / goal bounds of nlp_formulation.cc:136-151, 234-235, 279-280, 309-340;
+//   rich   stance-position tracking on every foot, stance-rpy tracking on foot 0, the base pitch pinned, the final
+//          base z free, an exact base-linear waypoint and a toleranced base-angular one.
+int varbounds_dump(NlpFormulation f, const std::string& variant, int device) {
+  Parameters& P = f.params_;
+  if (variant == "rich") {
+    P.constrain_base_pitch_ = true;
+    P.base_pitch_target_ = 0.05;
+    P.bounds_final_lin_pos_ = {0, 1};
+    P.base_lin_waypoints_.push_back({0.52, 0, {2}, {0.0, 0.0, 0.5}, {0.0, 0.0, 0.0}});
+    P.base_ang_waypoints_.push_back({0.25, 1, {0, 2}, {0.1, 0.0, -0.1}, {0.05, 0.0, 0.025}});
+    for (int ee = 0; ee < P.GetEECount(); ++ee) {
+      std::vector<std::array<double, 3>> pos;
+      for (int k = 0; k < (int)P.ee_phase_durations_[ee].size(); ++k) pos.push_back({0.125 * k + 0.0625 * ee, -0.25 * ee, 0.0});
+      P.ee_stance_position_.push_back(pos);
+    }
+    P.ee_stance_rpy_.push_back({});
+    for (int k = 0; k < (int)P.ee_phase_durations_[0].size(); ++k) P.ee_stance_rpy_[0].push_back({0.0, 0.03125 * k, 0.5});
+  } else {
+    P.enable_stance_tracking = false;
+  }
+  const std::vector<BoundsEntry> vb = f.VarBoundsData();
+  std::vector<towr_data_t> data;
+  for (const BoundsEntry& e : vb) {
+    std::printf("data %d %zu", e.index, e.values.size());
+    for (double v : e.values) std::printf(" %.17g", v);
+    std::printf("\n");
+    data.push_back(towr_data_t{TOWR_DATA_VAR_BOUNDS, e.index, (int64_t)e.values.size(), e.values.data()});
+  }
+  Engine e(f.MakeDesc(), device, data);
+  const int n = e.GetNumberOfOptimizationVariables();
+  std::vector<double> lo(n), up(n), lo2(n), up2(n);
+  e.GetVariableBounds(lo.data(), up.data());
+  e.GetVariableBoundsWith(data, lo2.data(), up2.data());
+  if (lo != lo2 || up != up2) { std::fprintf(stderr, "varbounds: GetVariableBoundsWith differs from GetVariableBounds\n"); return 1; }
+  for (int j = 0; j < n; ++j) std::printf("col %d %.17g %.17g\n", j, lo[j], up[j]);
+  return 0;
+}
+
 // --residual: B perturbations of x0; the residual kernel's outputs against a host loop: the maxima, the arg max and the
 // per-set maxima bit for bit, the two sums under 2 gamma_m S (+ 8 u S for phi's per-term roundings), lam+ within
 // 8 u rho (|g| + |lam| / rho + |c|); then the fused entry against the separate calls, bit for bit.
@@ -330,6 +373,7 @@ int main(int argc, char** argv) {
         if (*q >= '0' && *q <= '2') f.params_.rom_swing_relax_dims_.push_back(*q - '0');
       return bounds_dump(f);
     }
+    if (std::string(argv[2]) == "--varbounds") return varbounds_dump(f, argc > 3 ? argv[3] : "plain", argc > 4 ? std::atoi(argv[4]) : -1);
     if (rs) return residual_check(f, device < 0 ? 0 : device, argc > 4 ? std::max(1, std::atoi(argv[4])) : 5);
     const towr_problem_desc_t d = f.MakeDesc();
     if (zc) return zerocopy_check(d, device < 0 ? 0 : device, argc > 4 ? std::atoi(argv[4]) : 200);

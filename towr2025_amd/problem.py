@@ -51,7 +51,9 @@ def _check_tensor(t, what, min_cols, device=None):
 class TowrGpuProblem:
     """`data`: side data of towr_gpu_create_ex, [(towr_data_kind, index, float64 array)]: the matrix M of
     each LinearEqualityConstraint (capi.DATA_LINEAR_M, constraint index, rows x n_set row-major) and the
-    wrapped set's bounds of each SoftConstraint term (capi.DATA_SOFT_BOUNDS, cost index, [lower, upper])."""
+    wrapped set's bounds of each SoftConstraint term (capi.DATA_SOFT_BOUNDS, cost index, [lower, upper]); optionally
+    what the bounds calls need (capi.DATA_BOUNDS, NlpFormulation.bounds_data(); capi.DATA_VAR_BOUNDS, variable set
+    index, records (node, deriv, dim, lower, upper), NlpFormulation.var_bounds_data())."""
 
     def __init__(self, desc: capi.ProblemDesc, device: int = 0, data=None):
         self._lib = capi.load_library()
@@ -129,6 +131,31 @@ class TowrGpuProblem:
         lo, up = np.zeros(self.m), np.zeros(self.m)
         self._check(self._lib.towr_gpu_constraint_bounds_for(self._h, C.byref(init), C.byref(terrain),
                                                              capi.dptr(lo), capi.dptr(up)))
+        return lo, up
+
+    def variable_bounds(self):
+        """(lower, upper), n doubles each: the bounds on x in ifopt column order (IpoptAdapter::get_bounds_info for x),
+        from the TOWR_DATA_VAR_BOUNDS entries given at creation and, for the schedule sets, bound_phase_duration.
+        Unbounded sides are +-1e20."""
+        lo, up = np.zeros(self.n), np.zeros(self.n)
+        self._check(self._lib.towr_gpu_variable_bounds(self._h, capi.dptr(lo), capi.dptr(up)))
+        return lo, up
+
+    def variable_bounds_with(self, data):
+        """The bounds of another instance on this layout: `data` as the constructor's, its DATA_VAR_BOUNDS entries used
+        instead of the creation's (NlpFormulation.var_bounds_data with that instance's init / terrain)."""
+        lo, up = np.zeros(self.n), np.zeros(self.n)
+        arr, keep = capi.side_data(data)
+        self._check(self._lib.towr_gpu_variable_bounds_with(self._h, len(data or []), arr, capi.dptr(lo), capi.dptr(up)))
+        del keep
+        return lo, up
+
+    def variable_bounds_batch(self, datas):
+        """variable_bounds_with of every entry of `datas`: (lower, upper), (B, n) arrays (the per-problem rows of
+        step_batch_device)."""
+        lo, up = np.zeros((len(datas), self.n)), np.zeros((len(datas), self.n))
+        for b, data in enumerate(datas):
+            lo[b], up[b] = self.variable_bounds_with(data)
         return lo, up
 
     def jac_structure(self):
@@ -406,6 +433,80 @@ class TowrGpuProblem:
             self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gl, gu, ldb, lp, ldl, float(rho), gp, ldg, pp, ldlp,
             C.c_void_p(SUM.data_ptr()), SUM.stride(0), C.c_void_p(Z.data_ptr()), Z.stride(0), int(bool(accumulate)),
             self._stream(stream, X)))
+
+    # -------------------------------------------------------------------- steps ---------------
+    def _var_bounds_operands(self, B, XL, XU):
+        """(XL pointer, XU pointer, ldb) of a step call: both None (the handle's bounds), both 1-D of >= n entries (one
+        row shared by all problems, ldb = 0) or both 2-D (B, >= n)."""
+        if XL is None and XU is None:
+            return C.c_void_p(None), C.c_void_p(None), 0
+        if XL is None or XU is None:
+            raise TowrGpuError("XL and XU: give both or neither")
+        if XL.dim() != XU.dim():
+            raise TowrGpuError("XL and XU: one is shared (1-D), the other per problem (2-D)")
+        if XL.dim() == 1:
+            for t, name in ((XL, "XL"), (XU, "XU")):
+                _check_tensor(t, name, self.n, self.device)
+                if t.shape[0] < self.n or (t.shape[0] > 1 and t.stride(0) != 1):
+                    raise TowrGpuError(f"{name}: expected >= {self.n} contiguous entries")
+            return C.c_void_p(XL.data_ptr()), C.c_void_p(XU.data_ptr()), 0
+        self._check_rows(B, (XL, "XL", self.n), (XU, "XU", self.n))
+        if XL.stride(0) != XU.stride(0) or XL.stride(0) < self.n:
+            raise TowrGpuError("XL and XU: they share one leading dimension (>= n)")
+        return C.c_void_p(XL.data_ptr()), C.c_void_p(XU.data_ptr()), XL.stride(0)
+
+    def _alpha_operand(self, B, alpha):
+        """(ALPHA pointer, scalar) of a step call: a float, or a contiguous 1-D device tensor of >= B step lengths."""
+        if isinstance(alpha, (int, float)):
+            return C.c_void_p(None), float(alpha)
+        _check_tensor(alpha, "ALPHA", 1, self.device)
+        if alpha.dim() != 1 or alpha.shape[0] < B or (alpha.shape[0] > 1 and alpha.stride(0) != 1):
+            raise TowrGpuError("ALPHA: expected a contiguous 1-D tensor of >= B entries")
+        return C.c_void_p(alpha.data_ptr()), 0.0
+
+    def step_batch_device(self, X, D, SUM, XP=None, alpha=1.0, XL=None, XU=None, stream=None):
+        """XP[b] = P_[XL, XU](X[b] - alpha_b D[b]) and the projected step's summary into SUM (B, >= 5 + n_varsets): max
+        |s|, sum s^2, sum d s, columns on a bound, how far X is outside its box, per-set max |s| (towr_gpu.h). alpha: a
+        float or a 1-D tensor of B step lengths. XL / XU: None (the handle's bounds), 1-D (shared) or (B, >= n). XP
+        None: the summary only."""
+        B = X.shape[0]
+        ops = [(X, "X", self.n), (D, "D", self.n), (SUM, "SUM", 5 + self.desc.n_varsets)]
+        if XP is not None:
+            ops.append((XP, "XP", self.n))
+        self._check_rows(B, *ops)
+        xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        ap, a = self._alpha_operand(B, alpha)
+        xp, ldxp = (C.c_void_p(None), 0) if XP is None else (C.c_void_p(XP.data_ptr()), XP.stride(0))
+        self._check(self._lib.towr_gpu_step_batch_device(
+            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(D.data_ptr()), D.stride(0), ap, a, xl, xu, ldb,
+            xp, ldxp, C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, X)))
+
+    def auglag_step_batch_device(self, X, XP, SSUM, RSUM, GL=None, GU=None, LAM=None, rho=1.0, alpha=1.0, XL=None, XU=None,
+                                 F=None, G=None, LAMP=None, stream=None):
+        """One iteration in one call: eval_cost_batch_device's gradient, eval_auglag_batch_device accumulated onto it
+        (RSUM its summary; F, G, LAMP optional outputs) and step_batch_device with D = that gradient (XP, SSUM); the
+        gradient stays in handle scratch. Bit-identical to the three calls in sequence."""
+        B = X.shape[0]
+        ops = [(X, "X", self.n), (XP, "XP", self.n), (SSUM, "SSUM", 5 + self.desc.n_varsets),
+               (RSUM, "RSUM", 4 + self.desc.n_constraints)]
+        ops += [(t, name, self.m) for t, name in ((LAM, "LAM"), (G, "G"), (LAMP, "LAMP")) if t is not None]
+        self._check_rows(B, *ops)
+        if F is not None:
+            _check_tensor(F, "F", 1, self.device)
+            if F.dim() != 1 or F.shape[0] < B or (B > 1 and F.stride(0) != 1):
+                raise TowrGpuError("F: expected a contiguous 1-D tensor of >= B entries")
+        gl, gu, ldgb = self._bounds_operands(B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(B, XL, XU)
+        ap, a = self._alpha_operand(B, alpha)
+
+        def ptr(t):
+            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
+        (lp, ldl), (gp, ldg), (pp, ldlp) = ptr(LAM), ptr(G), ptr(LAMP)
+        self._check(self._lib.towr_gpu_auglag_step_batch_device(
+            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gl, gu, ldgb, lp, ldl, float(rho), ap, a, xl, xu, ldxb,
+            C.c_void_p(F.data_ptr() if F is not None else None), gp, ldg, pp, ldlp,
+            C.c_void_p(RSUM.data_ptr()), RSUM.stride(0), C.c_void_p(XP.data_ptr()), XP.stride(0),
+            C.c_void_p(SSUM.data_ptr()), SSUM.stride(0), self._stream(stream, X)))
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
