@@ -501,6 +501,82 @@ int towr_gpu_auglag_step_batch_device(towr_gpu_handle h, int32_t B, const double
                                       double* RSUM, int64_t ldrs,
                                       double* XP, int64_t ldxp, double* SSUM, int64_t ldss, void* stream);
 
+/* ---- a quasi-Newton direction on the device: the L-BFGS history and the two-loop recursion --------------------- */
+/* The history is caller-owned DEVICE memory for B problems and `mem` pairs, 1 <= mem <= TOWR_LBFGS_MAX_MEM: pair k
+ * of problem b starts at HS + (b*mem + k)*ldh (s) and HY + (b*mem + k)*ldh (y), ldh >= n; HMETA is int32_t[2*B],
+ * {count, next} per problem: the number of pairs held (0..mem) and the slot the next accepted pair goes to
+ * (0..mem-1). A zeroed HMETA is an empty history — also the way to reset it when lam or rho change (the pairs
+ * describe another function then). A problem whose count or next is out of range is treated as empty ({0, 0}); the
+ * kernels never index from such a value. All pointers are DEVICE pointers; `stream` as everywhere else.            */
+#define TOWR_LBFGS_MAX_MEM 16
+
+/* Per problem: s_j = XN_j - X_j, y_j = GRN_j - GR_j (one rounded subtraction each); sy = sum s y, ss = sum s s,
+ * yy = sum y y. The pair is accepted iff sy > curv_eps * yy (L-BFGS-B's curvature test: gamma = sy / yy stays above
+ * curv_eps; a NaN anywhere makes the comparison false). Accepted: s and y are written to slot `next`, then
+ * next = (next + 1) % mem and count = min(count + 1, mem). Rejected: not one byte of HS, HY or HMETA of that problem
+ * changes. SUM[b*lds + ..] holds 6 doubles (lds >= 6): [0] sy; [1] ss; [2] yy; [3] 1.0 accepted / 0.0 rejected;
+ * [4] count after the call; [5] the slot written (-1.0 when rejected). Nothing beyond n is read or written in any
+ * row, nothing beyond 6 in SUM. The sums are one fixed tree each (as towr_gpu_step_batch_device) and the decision is
+ * taken on them: problem b's outputs are a function of its own operands alone. No handle scratch is used and the
+ * kept Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for: a NULL pointer, mem outside
+ * 1..TOWR_LBFGS_MAX_MEM, ldx / ldxn / ldgr / ldgrn / ldh < n, lds < 6, curv_eps negative or NaN.
+ * TOWR_ERR_UNSUPPORTED at the call when n is too large for the kernels' LDS (16 n bytes of 60 KiB).                */
+int towr_gpu_lbfgs_update_batch_device(towr_gpu_handle h, int32_t B, int32_t mem,
+                                       const double* X, int64_t ldx, const double* XN, int64_t ldxn,
+                                       const double* GR, int64_t ldgr, const double* GRN, int64_t ldgrn,
+                                       double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA,
+                                       double* SUM, int64_t lds, void* stream);
+
+/* The two-loop recursion on the free columns: D_b ~ H_b g_b, g = GR[b*ldgr + ..]. The bounds as for
+ * towr_gpu_step_batch_device (XL = XU = NULL: the handle's; ldb = 0: one shared row; a side counts only within
+ * +-1e19); X = NULL: every column is free and the bounds are not read. Column j is held iff its lower side counts,
+ * x_j <= l_j and g_j > 0, or its upper side counts, x_j >= u_j and g_j < 0, or both sides count and l_j == u_j (exact
+ * comparisons: the step kernel lands a clamped variable exactly on its bound). Every other column is free (a NaN g_j
+ * is free). Held entries count as zero in every sum and are never updated:
+ *   q = g; for i = 1..count (newest to oldest), slot = (next - i) mod mem: c_i = sum_free s y; the pair is used iff
+ *   c_i > 0 (a NaN in a pair makes it unused); if used a_i = (sum_free s q) / c_i, q -= a_i y;
+ *   gamma = c / sum_free y y of the newest used pair (1 when none is used); r = gamma q;
+ *   for the used pairs, oldest to newest: beta = (sum_free y r) / c_i, r += (a_i - beta) s;
+ *   D_j = r_j on free columns, D_j = g_j bit for bit on held ones (the projected step keeps them on their bound).
+ * With count == 0, D equals GR bit for bit. A NaN g_j on a free column makes the free columns of that problem's D
+ * NaN (when a pair is used) and touches no other problem. SUM[b*lds + ..] holds 5 doubles (lds >= 5): [0] pairs
+ * used; [1] gamma; [2] sum_j g_j D_j over all columns (the slope: backtrack through ALPHA or fall back to D = GR
+ * when it is not positive); [3] the number of held columns; [4] sum_free g^2. Fixed-tree sums, the used decisions on
+ * them: problem b's outputs are a function of its own operands alone. Nothing beyond n (rows) or 5 (SUM) is read
+ * or written. No handle scratch, the kept Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for: NULL
+ * GR, D, HS, HY, HMETA or SUM, mem outside 1..TOWR_LBFGS_MAX_MEM, ldx / ldgr / ldd / ldh < n, lds < 5, only one
+ * of XL / XU, 0 < ldb < n. TOWR_ERR_UNSUPPORTED as for the update.                                                 */
+int towr_gpu_lbfgs_direction_batch_device(towr_gpu_handle h, int32_t B, int32_t mem,
+                                          const double* X, int64_t ldx, const double* GR, int64_t ldgr,
+                                          const double* XL, const double* XU, int64_t ldb,
+                                          const double* HS, const double* HY, int64_t ldh, const int32_t* HMETA,
+                                          double* D, int64_t ldd, double* SUM, int64_t lds, void* stream);
+
+/* One call per inner iteration of a bound-projected L-BFGS method on the augmented Lagrangian: on `stream`,
+ *   1. towr_gpu_eval_cost_batch_device with GRAD = GR (F NULL: f into handle scratch), then
+ *      towr_gpu_eval_auglag_batch_device with accumulate = 1 onto GR (g and lam+ in handle scratch, RSUM its SUM).
+ *      GR (required, ldgr >= n) must persist: it is the next call's GRPREV;
+ *   2. towr_gpu_lbfgs_update_batch_device with (X, XN) = (XPREV, X) and (GR, GRN) = (GRPREV, GR), USUM its SUM, when
+ *      XPREV and GRPREV are given; both NULL (the first iteration): no update, USUM is not written;
+ *   3. towr_gpu_lbfgs_direction_batch_device at (X, GR) into handle scratch, DSUM its SUM;
+ *   4. towr_gpu_step_batch_device with that direction (XP and SSUM required).
+ * Bit-identical to those calls in sequence, whatever the products chunk. Batch terrains, the cross-stream scratch
+ * rule and the kept Jacobian as for towr_gpu_eval_products_batch_device. Argument checks as those calls', and only
+ * one of XPREV / GRPREV is TOWR_ERR_INVALID. Three X buffers and two GR buffers rotate in the caller's loop
+ * (INTEGRATION.md).                                                                                              */
+int towr_gpu_auglag_lbfgs_step_batch_device(towr_gpu_handle h, int32_t B, int32_t mem,
+                                            const double* X, int64_t ldx,
+                                            const double* XPREV, int64_t ldxprev,
+                                            const double* GRPREV, int64_t ldgrprev,
+                                            const double* GL, const double* GU, int64_t ldgb,
+                                            const double* LAM, int64_t ldl, double rho,
+                                            const double* ALPHA, double alpha,
+                                            const double* XL, const double* XU, int64_t ldxb,
+                                            double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA,
+                                            double* F, double* GR, int64_t ldgr, double* RSUM, int64_t ldrs,
+                                            double* USUM, int64_t ldus, double* DSUM, int64_t ldds,
+                                            double* XP, int64_t ldxp, double* SSUM, int64_t ldss, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

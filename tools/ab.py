@@ -39,7 +39,7 @@ def main():
                 sys.exit(rc)
             line = [l for l in open(log) if l.startswith("{")][-1]
             j = json.loads(line)
-            ks = j["roofline"]["kernels"]
+            ks = j.get("roofline", {}).get("kernels", {})   # (a plain run has no roofline section)
             legs = {k: j[k]["ms_per_batch"] for k in LEGS if k in j}
             res.setdefault(name, []).append((j["ms_per_step"], {k: v["ms"] for k, v in ks.items()}, legs))
             print(f"{name:12s} r{r} step {j['ms_per_step']:.4f} ms  " +

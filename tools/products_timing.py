@@ -7,7 +7,15 @@
       written);
   (g) eval_auglag_batch_device (g and lam+ in scratch) beside the sum of its parts a + e + c from the same session;
   (h) step_batch_device (XP and the summary, the handle's bounds, scalar step length): rate = 8 (3 n + 5 + n_varsets)
-      B / time, the bytes of X + D + XP + SUM, beside (i) a device-to-device torch copy moving the same bytes,
+      B / time, the bytes of X + D + XP + SUM, beside (i) a device-to-device torch copy moving the same bytes;
+  (j) lbfgs_update_batch_device (every pair accepted): rate = 8 (6 n + 6) B / time, the bytes of X, XN, GR, GRN read and
+      the slot of HS and HY written, beside (k) a copy of the same bytes;
+  (l) lbfgs_direction_batch_device at mem = MEM (8) with a full history (every pair used, the handle's bounds): rate =
+      8 (4 MEM n + 3 n + 5) B / time — the history read twice (2 * 2 * MEM * n), X, GR and D — beside (m) a copy of the
+      same bytes and (n) a copy of the bytes with the history counted once (the call's compulsory traffic if the second
+      pass were served by a cache);
+  (o) auglag_lbfgs_step_batch_device (one inner iteration, mem = MEM) beside the sum of its parts from the same
+      session (cost gradient + g auglag + j + l + h) and the share of j + l in it,
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -26,6 +34,7 @@ from towr2025_amd import formulation as F  # noqa: E402
 
 REPS = int(os.environ.get("REPS", "20"))
 ROUNDS = int(os.environ.get("ROUNDS", "5"))
+MEM = int(os.environ.get("MEM", "8"))
 PEAK = 8.0e12
 
 
@@ -68,6 +77,32 @@ def run(name, f, B):
     bytes_step = 8 * (3 * p.n + 5 + nv) * B
     src_s = torch.randn(bytes_step // 16, dtype=torch.float64, device=dev)
     dst_s = torch.empty_like(src_s)
+    # L-BFGS: a full history of MEM pairs with positive curvature (y = c s, c per column in [0.5, 2]), X -> XN a small move
+    mem = MEM
+    HS = 0.01 * torch.randn((B * mem, ld(p.n)), dtype=torch.float64, device=dev)
+    HY = HS * (0.5 + 1.5 * torch.rand((1, ld(p.n)), dtype=torch.float64, device=dev))
+    HMETA = torch.tensor([[mem, 0]] * B, dtype=torch.int32, device=dev)
+    XN = Xs + 0.01 * torch.randn_like(Xs)
+    GR = torch.randn_like(P)
+    GRN = GR + 1.3 * (XN - Xs)
+    D, USUM, DSUM = torch.empty_like(P), torch.empty((B, 16), dtype=torch.float64, device=dev), torch.empty((B, 16), dtype=torch.float64, device=dev)
+    Fv, GRo = torch.empty(B, dtype=torch.float64, device=dev), torch.empty_like(P)
+    RSUM = torch.empty_like(SUM)
+    # the fused iteration's own operands: a history of its own, X = Xs + a small move and the true gradient at Xs as
+    # GRPREV, so that its pair is a pair of the augmented Lagrangian (the share accepted is printed)
+    HS2, HY2, HMETA2 = HS.clone(), HY.clone(), HMETA.clone()
+    XN2 = Xs + 1e-4 * torch.randn_like(Xs)
+    GRP = torch.empty_like(P)
+    p.eval_cost_batch_device(Xs, Fv, GRAD=GRP, stream=stream)
+    p.eval_auglag_batch_device(Xs, RSUM, GRP, LAM=LAM, rho=rho, accumulate=True, stream=stream)
+    USUM2 = torch.zeros((B, 16), dtype=torch.float64, device=dev)
+    bytes_upd = 8 * (6 * p.n + 6) * B
+    bytes_dir = 8 * (4 * mem * p.n + 3 * p.n + 5) * B
+    bytes_dir1 = 8 * (2 * mem * p.n + 3 * p.n + 5) * B
+    copies = {}
+    for key, nb in (("k", bytes_upd), ("m", bytes_dir), ("n", bytes_dir1)):
+        a = torch.randn(nb // 16, dtype=torch.float64, device=dev)
+        copies[key] = (a, torch.empty_like(a))
 
     def fused(chunk):
         def f():
@@ -84,7 +119,16 @@ def run(name, f, B):
                 ("g auglag fused auto", lambda: (p.set_products_chunk(0),
                                                  p.eval_auglag_batch_device(X, SUM, Z, LAM=LAM, rho=rho, stream=stream))),
                 ("h step", lambda: p.step_batch_device(Xs, P, SSUM, XP=XP, alpha=0.01, stream=stream)),
-                ("i copy, step's bytes", lambda: dst_s.copy_(src_s))]
+                ("i copy, step's bytes", lambda: dst_s.copy_(src_s)),
+                ("j lbfgs update", lambda: p.lbfgs_update_batch_device(Xs, XN, GR, GRN, HS, HY, HMETA, USUM, mem, stream=stream)),
+                ("k copy, update's bytes", lambda: copies["k"][1].copy_(copies["k"][0])),
+                (f"l lbfgs direction mem={mem}", lambda: p.lbfgs_direction_batch_device(GR, HS, HY, HMETA, D, DSUM, mem, X=Xs, stream=stream)),
+                ("m copy, direction's bytes", lambda: copies["m"][1].copy_(copies["m"][0])),
+                ("n copy, history once", lambda: copies["n"][1].copy_(copies["n"][0])),
+                ("p cost gradient", lambda: p.eval_cost_batch_device(Xs, Fv, GRAD=GRo, stream=stream)),
+                (f"o auglag lbfgs step mem={mem}", lambda: (p.set_products_chunk(0), p.auglag_lbfgs_step_batch_device(
+                    XN2, GRo, XP, SSUM, RSUM, DSUM, HS2, HY2, HMETA2, mem, XPREV=Xs, GRPREV=GRP, USUM=USUM2, LAM=LAM, rho=rho,
+                    alpha=1e-6, F=Fv, stream=stream)))]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
         for _ in range(3):
             fn()
@@ -104,12 +148,20 @@ def run(name, f, B):
     for k, _ in variants:
         t = times[k]
         med = statistics.median(t)
-        nbytes = bytes_prod if k[0] in "bc" else bytes_res if k[0] in "ef" else bytes_step if k[0] in "hi" else 0
+        nbytes = (bytes_prod if k[0] in "bc" else bytes_res if k[0] in "ef" else bytes_step if k[0] in "hi" else
+                  bytes_upd if k[0] in "jk" else bytes_dir if k[0] in "lm" else bytes_dir1 if k[0] == "n" else 0)
         rate = f"  {nbytes / (med * 1e-3) / 1e12:.2f} TB/s = {100 * nbytes / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if nbytes else ""
         print(f"  {k:22s} {med:.4f} ms  (min {min(t):.4f} max {max(t):.4f}){rate}", flush=True)
     parts = sum(statistics.median(times[k]) for k in ("a eval_batch_device", "e residual", "c jac_tvec"))
     print(f"  residual bytes {bytes_res / 1e9:.3f} GB; auglag parts a + e + c {parts:.4f} ms, fused / parts "
           f"{statistics.median(times['g auglag fused auto']) / parts:.3f}", flush=True)
+    med = {k[0]: statistics.median(times[k]) for k, _ in variants if k[0] in "pgjlho"}
+    parts = med["p"] + med["g"] + med["j"] + med["l"] + med["h"]
+    print(f"  update bytes {bytes_upd / 1e9:.3f} GB, direction bytes {bytes_dir / 1e9:.3f} GB (history once {bytes_dir1 / 1e9:.3f} GB); "
+          f"lbfgs step parts p + g + j + l + h {parts:.4f} ms, fused / parts {med['o'] / parts:.3f}, "
+          f"update + direction {med['j'] + med['l']:.4f} ms = {100 * (med['j'] + med['l']) / med['o']:.1f} % of the fused iteration; "
+          f"accepted: update {USUM[:, 3].mean().item():.2f}, fused {USUM2[:, 3].mean().item():.2f}; pairs used: direction "
+          f"{DSUM[:, 0].mean().item():.2f}", flush=True)
     p.set_products_chunk(0)
 
 

@@ -73,6 +73,7 @@ COST_NODE, COST_ENERGY, COST_ANG_MOMENTUM, COST_EE_BASE_POS, COST_BASE_HEIGHT, C
 # towr_data_kind (side data of towr_gpu_create_ex)
 DATA_LINEAR_M, DATA_SOFT_BOUNDS, DATA_BOUNDS, DATA_VAR_BOUNDS = 0, 1, 2, 3
 MAX_COSTS = 128
+LBFGS_MAX_MEM = 16   # TOWR_LBFGS_MAX_MEM
 
 
 class CostDesc(C.Structure):
@@ -170,6 +171,22 @@ SYMBOLS = {
                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                      C.c_void_p]),
+    "towr_gpu_lbfgs_update_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_lbfgs_direction_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                         C.c_void_p, C.c_void_p, C.c_int64,
+                                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_auglag_lbfgs_step_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
+                                                           C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                                           C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -260,6 +260,38 @@ struct StepArgs {
 };
 const void* step_kernel();
 
+// The L-BFGS kernels (lbfgs.hip): the per-problem ring of (s, y) pairs and the two-loop recursion on the free columns
+// (towr_gpu.h); one block of kLbfgsBlock threads per problem. Pair k of problem b starts at HS / HY + (b*mem + k)*ldh,
+// HMETA[2b] = count, HMETA[2b + 1] = next. The kernels keep per-column state in dynamic LDS: lbfgs_update_lds(n) /
+// lbfgs_direction_lds(n) bytes (the launcher refuses an n whose state does not fit kLbfgsMaxLds).
+constexpr int kLbfgsBlock = 256;
+constexpr int64_t kLbfgsMaxLds = 60 * 1024;   // beside the kernels' static reduction buffers, within the default 64 KiB
+inline int64_t lbfgs_update_lds(int n) { return 16 * (int64_t)n; }      // s and y
+inline int64_t lbfgs_direction_lds(int n) { return 16 * (int64_t)n; }   // q / r and the pair's row kept for the update
+struct LbfgsUpdateArgs {
+  const double* X; int64_t ldx;
+  const double* XN; int64_t ldxn;
+  const double* GR; int64_t ldgr;
+  const double* GRN; int64_t ldgrn;
+  double *HS, *HY; int64_t ldh;
+  int32_t* HMETA;
+  double* SUM; int64_t lds;
+  double curv_eps;
+  int32_t n, mem;
+};
+struct LbfgsDirArgs {
+  const double* X; int64_t ldx;   // NULL: every column is free
+  const double* GR; int64_t ldgr;
+  const double *XL, *XU; int64_t ldb;
+  const double *HS, *HY; int64_t ldh;
+  const int32_t* HMETA;
+  double* D; int64_t ldd;
+  double* SUM; int64_t lds;
+  int32_t n, mem;
+};
+const void* lbfgs_update_kernel();
+const void* lbfgs_direction_kernel();
+
 struct Layout {
   int n = 0, m = 0;
   int64_t nnz = 0;

@@ -1,0 +1,245 @@
+// lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
+// and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device).
+//
+// The shape of resid.hip and step.hip. One block of kLbfgsBlock threads per problem. Lane l takes columns l,
+// l + kLbfgsBlock, ... in ascending order in every pass, so a column belongs to one lane for the whole kernel: the
+// per-column state in LDS (s and y of the update; q / r and the pair's row kept for the in-place update of the
+// direction) is lane-private and needs no barrier, and the held mask is a bit per column in a lane register. The rows
+// stream coalesced (8 bytes per lane, 512 per wave instruction).
+//   update:    one pass over X, XN, GR, GRN forms s and y once (into LDS) and the three sums; the decision is taken on
+//              the sums; only then the slot and HMETA are written, from LDS. A rejected problem writes SUM alone.
+//   direction: a pair costs one pass over (s_k, y_k) in the first loop — it forms sum s y, sum s q and sum y y, with
+//              y_k kept in LDS for q -= a y — and one more in the second (sum y r, s_k kept for r += (a - beta) s).
+//   sums: the lane's partial in column order, a fixed __shfl_down tree over the wave, the waves' partials added in wave
+//     order by one lane and the scalar broadcast through LDS behind a barrier: every lane takes the accept / used
+//     decisions on the same bits. No floating-point atomics.
+// Contraction is off: every product and sum is the plain IEEE expression the header states. Nothing depends on B, the
+// block's place in the grid, the stream or timing: the bits are a function of the problem.
+#include <hip/hip_runtime.h>
+
+#include "layout.h"
+
+namespace tg {
+namespace {
+
+constexpr int kLbfgsWaves = kLbfgsBlock / 64;
+constexpr double kSideInf = 1e19;   // as resid.hip / step.hip: a side beyond it does not count
+static_assert(kLbfgsMaxLds / 16 <= 32 * kLbfgsBlock, "the held mask is one 32-bit word per lane");
+static_assert(TOWR_LBFGS_MAX_MEM < 32, "the used pairs are one 32-bit mask");
+
+// v[k] <- the block's sum of v[k], the same bits in every lane (two barriers; s_part / s_bc may be reused at once)
+template <int K>
+__device__ inline void block_sums(double (&v)[K], double (*s_part)[kLbfgsWaves], double* s_bc, int tid) {
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] += __shfl_down(v[k], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_part[k][tid >> 6] = v[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      double t = s_part[k][0];
+      for (int w = 1; w < kLbfgsWaves; ++w) t += s_part[k][w];
+      s_bc[k] = t;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = s_bc[k];
+}
+
+__global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_update_kernel(LbfgsUpdateArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_dyn[];
+  __shared__ double s_part[3][kLbfgsWaves], s_bc[3];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int n = a.n, mem = a.mem;
+  double* s_s = s_dyn;
+  double* s_y = s_dyn + n;
+  const double* Xb = a.X + b * a.ldx;
+  const double* XNb = a.XN + b * a.ldxn;
+  const double* Gb = a.GR + b * a.ldgr;
+  const double* GNb = a.GRN + b * a.ldgrn;
+  int count = a.HMETA[2 * b], next = a.HMETA[2 * b + 1];   // (read by every lane before the sums' barriers)
+  if (count < 0 || count > mem || next < 0 || next >= mem) count = next = 0;
+
+  double v[3] = {0.0, 0.0, 0.0};   // sum s y, sum s s, sum y y
+#pragma unroll 4
+  for (int j = tid; j < n; j += kLbfgsBlock) {
+    const double s = XNb[j] - Xb[j];
+    const double y = GNb[j] - Gb[j];
+    s_s[j] = s;
+    s_y[j] = y;
+    v[0] += s * y;
+    v[1] += s * s;
+    v[2] += y * y;
+  }
+  block_sums<3>(v, s_part, s_bc, tid);
+  const bool accept = v[0] > a.curv_eps * v[2];   // (a NaN anywhere: false)
+  if (accept) {
+    double* S = a.HS + (b * mem + next) * a.ldh;
+    double* Y = a.HY + (b * mem + next) * a.ldh;
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock) {
+      S[j] = s_s[j];
+      Y[j] = s_y[j];
+    }
+  }
+  if (tid == 0) {
+    const int cnt = accept ? (count < mem ? count + 1 : mem) : count;
+    if (accept) {
+      a.HMETA[2 * b] = cnt;
+      a.HMETA[2 * b + 1] = next + 1 < mem ? next + 1 : 0;
+    }
+    double* Sb = a.SUM + b * a.lds;
+    Sb[0] = v[0];
+    Sb[1] = v[1];
+    Sb[2] = v[2];
+    Sb[3] = accept ? 1.0 : 0.0;
+    Sb[4] = (double)cnt;
+    Sb[5] = accept ? (double)next : -1.0;
+  }
+}
+
+__global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_direction_kernel(LbfgsDirArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_dyn[];
+  __shared__ double s_part[3][kLbfgsWaves], s_bc[3];
+  __shared__ double s_alpha[TOWR_LBFGS_MAX_MEM], s_c[TOWR_LBFGS_MAX_MEM];   // a_i and c_i of the used pairs, by i - 1
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int n = a.n, mem = a.mem;
+  double* s_q = s_dyn;       // q, then r; a held column keeps g
+  double* s_v = s_dyn + n;   // the pair's y (first loop) or s (second loop)
+  const double* Gb = a.GR + b * a.ldgr;
+  const double* HSb = a.HS + b * mem * a.ldh;
+  const double* HYb = a.HY + b * mem * a.ldh;
+  int count = a.HMETA[2 * b], next = a.HMETA[2 * b + 1];
+  if (count < 0 || count > mem || next < 0 || next >= mem) count = next = 0;
+
+  // q = g, the held mask (bit k: the lane's k-th column) and sum_free g^2
+  unsigned held = 0u;
+  double nheld = 0.0, gg = 0.0;
+  if (a.X) {
+    const double* Xb = a.X + b * a.ldx;
+    const double* Lb = a.XL + b * a.ldb;
+    const double* Ub = a.XU + b * a.ldb;
+    int k = 0;
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock, ++k) {
+      const double g = Gb[j], x = Xb[j], l = Lb[j], u = Ub[j];
+      const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+      const bool h = (has_l && x <= l && g > 0.0) || (has_u && x >= u && g < 0.0) || (has_l && has_u && l == u);
+      if (h) {
+        held |= 1u << k;
+        nheld += 1.0;
+      } else {
+        gg += g * g;
+      }
+      s_q[j] = g;
+    }
+  } else {
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock) {
+      const double g = Gb[j];
+      gg += g * g;
+      s_q[j] = g;
+    }
+  }
+
+  // first loop, newest to oldest
+  unsigned used = 0u;
+  int nused = 0;
+  double gamma = 1.0;
+  for (int i = 1; i <= count; ++i) {
+    const int slot = next - i < 0 ? next - i + mem : next - i;
+    const double* S = HSb + (int64_t)slot * a.ldh;
+    const double* Y = HYb + (int64_t)slot * a.ldh;
+    double v[3] = {0.0, 0.0, 0.0};   // sum_free s y, sum_free s q, sum_free y y
+    int k = 0;
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock, ++k) {
+      const double s = S[j], y = Y[j];
+      s_v[j] = y;
+      if (!((held >> k) & 1u)) {
+        v[0] += s * y;
+        v[1] += s * s_q[j];
+        v[2] += y * y;
+      }
+    }
+    block_sums<3>(v, s_part, s_bc, tid);
+    if (v[0] > 0.0) {   // (a NaN c_i: unused)
+      const double al = v[1] / v[0];
+      if (!used) gamma = v[0] / v[2];
+      used |= 1u << i;
+      ++nused;
+      if (tid == 0) {
+        s_alpha[i - 1] = al;
+        s_c[i - 1] = v[0];
+      }
+      k = 0;
+      for (int j = tid; j < n; j += kLbfgsBlock, ++k)
+        if (!((held >> k) & 1u)) s_q[j] = s_q[j] - al * s_v[j];
+    }
+  }
+
+  // r = gamma q (no pair used: r = q, bit for bit)
+  if (used) {
+    int k = 0;
+    for (int j = tid; j < n; j += kLbfgsBlock, ++k)
+      if (!((held >> k) & 1u)) s_q[j] = gamma * s_q[j];
+  }
+
+  // second loop, the used pairs oldest to newest
+  for (int i = count; i >= 1; --i) {
+    if (!((used >> i) & 1u)) continue;
+    const int slot = next - i < 0 ? next - i + mem : next - i;
+    const double* S = HSb + (int64_t)slot * a.ldh;
+    const double* Y = HYb + (int64_t)slot * a.ldh;
+    double v[1] = {0.0};   // sum_free y r
+    int k = 0;
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock, ++k) {
+      const double s = S[j], y = Y[j];
+      s_v[j] = s;
+      if (!((held >> k) & 1u)) v[0] += y * s_q[j];
+    }
+    block_sums<1>(v, s_part, s_bc, tid);   // (its barriers also order tid 0's s_alpha / s_c before the reads below)
+    const double beta = v[0] / s_c[i - 1];
+    const double co = s_alpha[i - 1] - beta;
+    k = 0;
+    for (int j = tid; j < n; j += kLbfgsBlock, ++k)
+      if (!((held >> k) & 1u)) s_q[j] = s_q[j] + co * s_v[j];
+  }
+
+  // D and the slope sum g D over all columns
+  double* Db = a.D + b * a.ldd;
+  double w[3] = {0.0, gg, nheld};   // (the held count: integers below 2^53, exact in any order)
+#pragma unroll 4
+  for (int j = tid; j < n; j += kLbfgsBlock) {
+    const double d = s_q[j], g = Gb[j];
+    Db[j] = d;
+    w[0] += g * d;
+  }
+  block_sums<3>(w, s_part, s_bc, tid);
+  if (tid == 0) {
+    double* Sb = a.SUM + b * a.lds;
+    Sb[0] = (double)nused;
+    Sb[1] = gamma;
+    Sb[2] = w[0];
+    Sb[3] = w[2];
+    Sb[4] = w[1];
+  }
+}
+
+}  // namespace
+
+const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
+const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }
+
+}  // namespace tg

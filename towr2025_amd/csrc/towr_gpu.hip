@@ -2100,6 +2100,143 @@ int towr_gpu_auglag_step_batch_device(towr_gpu_handle h, int32_t B, const double
   return rc ? rc : rr;
 }
 
+// ---- L-BFGS (lbfgs.hip) --------------------------------------------------------------------------------------------
+// the argument checks the L-BFGS entries and the fused entry share (before anything runs)
+static int lbfgs_args(towr_gpu_handle h, int32_t mem, const double* HS, const double* HY, int64_t ldh, const int32_t* HMETA,
+                      const double* SUM, int64_t lds, int64_t lds_min) {
+  if (!HS || !HY || !HMETA) return fail(h, TOWR_ERR_INVALID, "null HS, HY or HMETA");
+  if (!SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
+  if (mem < 1 || mem > TOWR_LBFGS_MAX_MEM) return fail(h, TOWR_ERR_INVALID, "mem outside 1..TOWR_LBFGS_MAX_MEM");
+  if (ldh < h->L.n) return fail(h, TOWR_ERR_INVALID, "ldh smaller than n");
+  if (lds < lds_min) return fail(h, TOWR_ERR_INVALID, lds_min == 6 ? "lds smaller than 6" : "lds smaller than 5");
+  return TOWR_OK;
+}
+static int lbfgs_update_args(towr_gpu_handle h, double curv_eps) {
+  if (!(curv_eps >= 0)) return fail(h, TOWR_ERR_INVALID, "curv_eps is negative or NaN");
+  return TOWR_OK;
+}
+static int lbfgs_bounds_args(towr_gpu_handle h, const double* XL, const double* XU, int64_t ldb) {
+  if ((XL == nullptr) != (XU == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XL / XU given");
+  if (XL && ldb != 0 && ldb < h->L.n) return fail(h, TOWR_ERR_INVALID, "ldb must be 0 (shared bounds) or >= n");
+  return TOWR_OK;
+}
+// the kernels' per-column state lives in LDS: the handle's n must fit (after bind: a layout-only handle has answered)
+static int lbfgs_fits(towr_gpu_handle h) {
+  if (std::max(lbfgs_update_lds(h->L.n), lbfgs_direction_lds(h->L.n)) > kLbfgsMaxLds)
+    return fail(h, TOWR_ERR_UNSUPPORTED, "n too large for the L-BFGS kernels' LDS");
+  return TOWR_OK;
+}
+
+static int launch_lbfgs_update(towr_gpu_handle h, int B, int mem, const double* X, int64_t ldx, const double* XN, int64_t ldxn,
+                               const double* GR, int64_t ldgr, const double* GRN, int64_t ldgrn, double curv_eps, double* HS,
+                               double* HY, int64_t ldh, int32_t* HMETA, double* SUM, int64_t lds, hipStream_t s) {
+  LbfgsUpdateArgs a{};
+  a.X = X; a.ldx = ldx; a.XN = XN; a.ldxn = ldxn; a.GR = GR; a.ldgr = ldgr; a.GRN = GRN; a.ldgrn = ldgrn;
+  a.HS = HS; a.HY = HY; a.ldh = ldh; a.HMETA = HMETA; a.SUM = SUM; a.lds = lds; a.curv_eps = curv_eps;
+  a.n = h->L.n; a.mem = mem;
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(lbfgs_update_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_update_lds(a.n), s));
+  return TOWR_OK;
+}
+
+// (X != NULL with XL == NULL: the handle's bounds, after step_ready)
+static int launch_lbfgs_direction(towr_gpu_handle h, int B, int mem, const double* X, int64_t ldx, const double* GR, int64_t ldgr,
+                                  const double* XL, const double* XU, int64_t ldb, const double* HS, const double* HY,
+                                  int64_t ldh, const int32_t* HMETA, double* D, int64_t ldd, double* SUM, int64_t lds,
+                                  hipStream_t s) {
+  LbfgsDirArgs a{};
+  a.X = X; a.ldx = ldx; a.GR = GR; a.ldgr = ldgr;
+  a.XL = XL ? XL : h->d_xlo; a.XU = XL ? XU : h->d_xup; a.ldb = XL ? ldb : 0;
+  a.HS = HS; a.HY = HY; a.ldh = ldh; a.HMETA = HMETA; a.D = D; a.ldd = ldd; a.SUM = SUM; a.lds = lds;
+  a.n = h->L.n; a.mem = mem;
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(lbfgs_direction_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_direction_lds(a.n), s));
+  return TOWR_OK;
+}
+
+int towr_gpu_lbfgs_update_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx, const double* XN,
+                                       int64_t ldxn, const double* GR, int64_t ldgr, const double* GRN, int64_t ldgrn,
+                                       double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA, double* SUM,
+                                       int64_t lds, void* stream) {
+  if (!h || B < 0 || !X || !XN || !GR || !GRN) return fail(h, TOWR_ERR_INVALID, "bad argument (null X, XN, GR or GRN, or B < 0)");
+  const int n = h->L.n;
+  if (ldx < n || ldxn < n || ldgr < n || ldgrn < n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X, XN, GR or GRN smaller than n");
+  if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, SUM, lds, 6)) return rc;
+  if (int rc = lbfgs_update_args(h, curv_eps)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  return launch_lbfgs_update(h, B, mem, X, ldx, XN, ldxn, GR, ldgr, GRN, ldgrn, curv_eps, HS, HY, ldh, HMETA, SUM, lds,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_lbfgs_direction_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx, const double* GR,
+                                          int64_t ldgr, const double* XL, const double* XU, int64_t ldb, const double* HS,
+                                          const double* HY, int64_t ldh, const int32_t* HMETA, double* D, int64_t ldd, double* SUM,
+                                          int64_t lds, void* stream) {
+  if (!h || B < 0 || !GR || !D) return fail(h, TOWR_ERR_INVALID, "bad argument (null GR or D, or B < 0)");
+  const int n = h->L.n;
+  if ((X && ldx < n) || ldgr < n || ldd < n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X, GR or D smaller than n");
+  if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, SUM, lds, 5)) return rc;
+  if (int rc = lbfgs_bounds_args(h, XL, XU, ldb)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (X && !XL)
+    if (int rc = step_ready(h)) return rc;
+  return launch_lbfgs_direction(h, B, mem, X, ldx, GR, ldgr, XL, XU, ldb, HS, HY, ldh, HMETA, D, ldd, SUM, lds,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+// The gradient of the augmented Lagrangian in the caller's GR (grad f from the cost launch, then + J^T lam+ per chunk of
+// the auglag sequence; g and lam+ in handle scratch), the history update with (XPREV -> X, GRPREV -> GR), the
+// direction in handle scratch (d_sd) and the step kernel behind it: what the five public calls launch, on the
+// caller's stream.
+int towr_gpu_auglag_lbfgs_step_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx,
+                                            const double* XPREV, int64_t ldxprev, const double* GRPREV, int64_t ldgrprev,
+                                            const double* GL, const double* GU, int64_t ldgb, const double* LAM, int64_t ldl,
+                                            double rho, const double* ALPHA, double alpha, const double* XL, const double* XU,
+                                            int64_t ldxb, double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA,
+                                            double* F, double* GR, int64_t ldgr, double* RSUM, int64_t ldrs, double* USUM,
+                                            int64_t ldus, double* DSUM, int64_t ldds, double* XP, int64_t ldxp, double* SSUM,
+                                            int64_t ldss, void* stream) {
+  if (!h || B < 0 || !X || !XP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null X, XP or GR, or B < 0)");
+  const Layout& L = h->L;
+  if (ldx < L.n || ldgr < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X or GR smaller than n");
+  if ((XPREV == nullptr) != (GRPREV == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XPREV / GRPREV given");
+  if (XPREV && (ldxprev < L.n || ldgrprev < L.n)) return fail(h, TOWR_ERR_INVALID, "leading dimension of XPREV or GRPREV smaller than n");
+  if (int rc = residual_args(h, GL, GU, ldgb, LAM, ldl, rho, true, L.m, RSUM, ldrs)) return rc;
+  if (XPREV)
+    if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, USUM, ldus, 6)) return rc;
+  if (int rc = lbfgs_update_args(h, curv_eps)) return rc;
+  if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, DSUM, ldds, 5)) return rc;
+  if (int rc = step_args(h, ALPHA, alpha, XL, XU, ldxb, ldxp, true, SSUM, ldss)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  const towr_terrain_t* ter;
+  int per;
+  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
+  if (B == 0) return TOWR_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = products_ready(h)) return rc;
+  if (int rc = residual_ready(h)) return rc;
+  if (int rc = step_ready(h)) return rc;
+  const int64_t ldn = std::max<int64_t>(16, ((int64_t)L.n + 15) & ~int64_t(15));   // rows on 128-byte boundaries
+  if (int rc = scratch_acquire(h, s)) return rc;
+  int rc = scratch_grow(h, &h->d_sd, &h->sd_cap, B, ldn);
+  if (rc == TOWR_OK && !F) rc = scratch_grow(h, &h->d_sf, &h->sf_cap, B, 1);
+  if (rc == TOWR_OK) rc = launch_cost(h, B, X, ldx, F ? F : h->d_sf, GR, ldgr, s, ter, per);
+  if (rc == TOWR_OK)
+    rc = auglag_chunks(h, B, X, ldx, GL, GU, ldgb, LAM, ldl, rho, nullptr, 0, nullptr, 0, RSUM, ldrs, GR, ldgr, 1, s, ter, per);
+  if (rc == TOWR_OK && XPREV)
+    rc = launch_lbfgs_update(h, B, mem, XPREV, ldxprev, X, ldx, GRPREV, ldgrprev, GR, ldgr, curv_eps, HS, HY, ldh, HMETA, USUM, ldus, s);
+  if (rc == TOWR_OK)
+    rc = launch_lbfgs_direction(h, B, mem, X, ldx, GR, ldgr, XL, XU, ldxb, HS, HY, ldh, HMETA, h->d_sd, ldn, DSUM, ldds, s);
+  if (rc == TOWR_OK) rc = launch_step(h, B, X, ldx, h->d_sd, ldn, ALPHA, alpha, XL, XU, ldxb, XP, ldxp, SSUM, ldss, s);
+  const int rr = scratch_release(h, s);
+  return rc ? rc : rr;
+}
+
 int towr_gpu_kernel_info(towr_gpu_handle h, int32_t kernel, const char** name, int32_t* n_tiles, int64_t* bytes_per_problem) {
   static const char* names[LC_COUNT] = {"dynamic", "range_of_motion", "force_discretized", "torque_discretized", "small_kinds"};
   if (!h || kernel < 0 || kernel >= towr_gpu_num_kernels()) return fail(h, TOWR_ERR_INVALID, "bad kernel index");

@@ -140,6 +140,31 @@ class Engine {
     return towr_gpu_auglag_step_batch_device(h_, B, X, ldx, GL, GU, ldgb, LAM, ldl, rho, ALPHA, alpha, XL, XU, ldxb, F, G, ldg,
                                              LAMP, ldlp, RSUM, ldrs, XP, ldxp, SSUM, ldss, stream);
   }
+  // the L-BFGS history update, the two-loop direction on the free columns and one bound-projected L-BFGS iteration of
+  // the augmented Lagrangian in one call (include/towr_gpu.h); they return the status
+  int LbfgsUpdateBatchDevice(int B, int mem, const double* X, int64_t ldx, const double* XN, int64_t ldxn, const double* GR,
+                             int64_t ldgr, const double* GRN, int64_t ldgrn, double curv_eps, double* HS, double* HY, int64_t ldh,
+                             int32_t* HMETA, double* SUM, int64_t lds, void* stream) const {
+    return towr_gpu_lbfgs_update_batch_device(h_, B, mem, X, ldx, XN, ldxn, GR, ldgr, GRN, ldgrn, curv_eps, HS, HY, ldh, HMETA, SUM,
+                                              lds, stream);
+  }
+  int LbfgsDirectionBatchDevice(int B, int mem, const double* X, int64_t ldx, const double* GR, int64_t ldgr, const double* XL,
+                                const double* XU, int64_t ldb, const double* HS, const double* HY, int64_t ldh,
+                                const int32_t* HMETA, double* D, int64_t ldd, double* SUM, int64_t lds, void* stream) const {
+    return towr_gpu_lbfgs_direction_batch_device(h_, B, mem, X, ldx, GR, ldgr, XL, XU, ldb, HS, HY, ldh, HMETA, D, ldd, SUM, lds,
+                                                 stream);
+  }
+  int AuglagLbfgsStepBatchDevice(int B, int mem, const double* X, int64_t ldx, const double* XPREV, int64_t ldxprev,
+                                 const double* GRPREV, int64_t ldgrprev, const double* GL, const double* GU, int64_t ldgb,
+                                 const double* LAM, int64_t ldl, double rho, const double* ALPHA, double alpha, const double* XL,
+                                 const double* XU, int64_t ldxb, double curv_eps, double* HS, double* HY, int64_t ldh,
+                                 int32_t* HMETA, double* F, double* GR, int64_t ldgr, double* RSUM, int64_t ldrs, double* USUM,
+                                 int64_t ldus, double* DSUM, int64_t ldds, double* XP, int64_t ldxp, double* SSUM, int64_t ldss,
+                                 void* stream) const {
+    return towr_gpu_auglag_lbfgs_step_batch_device(h_, B, mem, X, ldx, XPREV, ldxprev, GRPREV, ldgrprev, GL, GU, ldgb, LAM, ldl, rho,
+                                                   ALPHA, alpha, XL, XU, ldxb, curv_eps, HS, HY, ldh, HMETA, F, GR, ldgr, RSUM, ldrs,
+                                                   USUM, ldus, DSUM, ldds, XP, ldxp, SSUM, ldss, stream);
+  }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // page-lock caller memory for in-place host transfers (towr_gpu_register_host); returns the status
   int RegisterHost(void* p, size_t bytes) const { return towr_gpu_register_host(h_, p, (int64_t)bytes); }

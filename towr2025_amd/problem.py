@@ -508,6 +508,92 @@ class TowrGpuProblem:
             C.c_void_p(RSUM.data_ptr()), RSUM.stride(0), C.c_void_p(XP.data_ptr()), XP.stride(0),
             C.c_void_p(SSUM.data_ptr()), SSUM.stride(0), self._stream(stream, X)))
 
+    # -------------------------------------------------------------------- L-BFGS --------------
+    def _history_operands(self, B, mem, HS, HY, HMETA):
+        """(HS pointer, HY pointer, ldh, HMETA pointer) of an L-BFGS call: HS and HY 2-D (B * mem, >= n) with one
+        leading dimension, row b * mem + k = pair k of problem b; HMETA contiguous int32 of >= 2 B entries
+        ({count, next} per problem; zeros = an empty history)."""
+        import torch
+        if not (isinstance(mem, int) and 1 <= mem <= capi.LBFGS_MAX_MEM):
+            raise TowrGpuError(f"mem: expected an int in 1..{capi.LBFGS_MAX_MEM}")
+        self._check_rows(B * mem, (HS, "HS", self.n), (HY, "HY", self.n))
+        if HS.stride(0) != HY.stride(0) or HS.stride(0) < self.n:
+            raise TowrGpuError("HS and HY: they share one leading dimension (>= n)")
+        if HMETA.dtype != torch.int32:
+            raise TowrGpuError(f"HMETA: dtype {HMETA.dtype}, expected torch.int32")
+        if HMETA.device.type != "cuda" or HMETA.device.index != self.device:
+            raise TowrGpuError(f"HMETA: tensor on {HMETA.device}, expected the handle's HIP device")
+        if not HMETA.is_contiguous() or HMETA.numel() < 2 * B:
+            raise TowrGpuError("HMETA: expected a contiguous tensor of >= 2 B entries")
+        return C.c_void_p(HS.data_ptr()), C.c_void_p(HY.data_ptr()), HS.stride(0), C.c_void_p(HMETA.data_ptr())
+
+    def lbfgs_update_batch_device(self, X, XN, GR, GRN, HS, HY, HMETA, SUM, mem, curv_eps=0.0, stream=None):
+        """Offer the pair s = XN - X, y = GRN - GR of every problem to its history (HS, HY, HMETA, `mem` slots per
+        problem): accepted iff sum s y > curv_eps sum y y, then written to slot `next`; a rejected problem's history is
+        untouched. SUM (B, >= 6): sy, ss, yy, accepted, count, slot (towr_gpu.h)."""
+        B = X.shape[0]
+        self._check_rows(B, (X, "X", self.n), (XN, "XN", self.n), (GR, "GR", self.n), (GRN, "GRN", self.n), (SUM, "SUM", 6))
+        hs, hy, ldh, hm = self._history_operands(B, mem, HS, HY, HMETA)
+        self._check(self._lib.towr_gpu_lbfgs_update_batch_device(
+            self._h, B, mem, C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(XN.data_ptr()), XN.stride(0),
+            C.c_void_p(GR.data_ptr()), GR.stride(0), C.c_void_p(GRN.data_ptr()), GRN.stride(0), float(curv_eps),
+            hs, hy, ldh, hm, C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, GR)))
+
+    def lbfgs_direction_batch_device(self, GR, HS, HY, HMETA, D, SUM, mem, X=None, XL=None, XU=None, stream=None):
+        """D[b] = the two-loop L-BFGS direction of the gradient GR[b] on the free columns (held columns: D = GR), with
+        the columns held where X[b] sits on a bound and the gradient points outward; X None: every column is free.
+        XL / XU: None (the handle's bounds), 1-D (shared) or (B, >= n). SUM (B, >= 5): pairs used, gamma, slope
+        sum g D, held columns, sum_free g^2 (towr_gpu.h)."""
+        B = GR.shape[0]
+        ops = [(GR, "GR", self.n), (D, "D", self.n), (SUM, "SUM", 5)]
+        if X is not None:
+            ops.append((X, "X", self.n))
+        self._check_rows(B, *ops)
+        hs, hy, ldh, hm = self._history_operands(B, mem, HS, HY, HMETA)
+        xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        xp, ldx = (C.c_void_p(None), 0) if X is None else (C.c_void_p(X.data_ptr()), X.stride(0))
+        self._check(self._lib.towr_gpu_lbfgs_direction_batch_device(
+            self._h, B, mem, xp, ldx, C.c_void_p(GR.data_ptr()), GR.stride(0), xl, xu, ldb, hs, hy, ldh, hm,
+            C.c_void_p(D.data_ptr()), D.stride(0), C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, GR)))
+
+    def auglag_lbfgs_step_batch_device(self, X, GR, XP, SSUM, RSUM, DSUM, HS, HY, HMETA, mem, XPREV=None, GRPREV=None,
+                                       USUM=None, curv_eps=0.0, GL=None, GU=None, LAM=None, rho=1.0, alpha=1.0, XL=None,
+                                       XU=None, F=None, stream=None):
+        """One inner iteration in one call: the augmented Lagrangian's gradient at X into GR (RSUM the residual
+        summary, F optional), lbfgs_update_batch_device with (XPREV -> X, GRPREV -> GR) into USUM when XPREV / GRPREV
+        are given, lbfgs_direction_batch_device at (X, GR) (DSUM) and step_batch_device with that direction (XP,
+        SSUM). Bit-identical to the separate calls in sequence."""
+        B = X.shape[0]
+        ops = [(X, "X", self.n), (GR, "GR", self.n), (XP, "XP", self.n), (SSUM, "SSUM", 5 + self.desc.n_varsets),
+               (RSUM, "RSUM", 4 + self.desc.n_constraints), (DSUM, "DSUM", 5)]
+        if (XPREV is None) != (GRPREV is None):
+            raise TowrGpuError("XPREV and GRPREV: give both or neither")
+        if XPREV is not None:
+            if USUM is None:
+                raise TowrGpuError("USUM: required with XPREV / GRPREV")
+            ops += [(XPREV, "XPREV", self.n), (GRPREV, "GRPREV", self.n), (USUM, "USUM", 6)]
+        if LAM is not None:
+            ops.append((LAM, "LAM", self.m))
+        self._check_rows(B, *ops)
+        if F is not None:
+            _check_tensor(F, "F", 1, self.device)
+            if F.dim() != 1 or F.shape[0] < B or (B > 1 and F.stride(0) != 1):
+                raise TowrGpuError("F: expected a contiguous 1-D tensor of >= B entries")
+        hs, hy, ldh, hm = self._history_operands(B, mem, HS, HY, HMETA)
+        gl, gu, ldgb = self._bounds_operands(B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(B, XL, XU)
+        ap, a = self._alpha_operand(B, alpha)
+
+        def ptr(t):
+            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
+        (lp, ldl), (xq, ldxq), (gq, ldgq), (us, ldus) = ptr(LAM), ptr(XPREV), ptr(GRPREV), ptr(USUM if XPREV is not None else None)
+        self._check(self._lib.towr_gpu_auglag_lbfgs_step_batch_device(
+            self._h, B, mem, C.c_void_p(X.data_ptr()), X.stride(0), xq, ldxq, gq, ldgq, gl, gu, ldgb, lp, ldl, float(rho),
+            ap, a, xl, xu, ldxb, float(curv_eps), hs, hy, ldh, hm,
+            C.c_void_p(F.data_ptr() if F is not None else None), C.c_void_p(GR.data_ptr()), GR.stride(0),
+            C.c_void_p(RSUM.data_ptr()), RSUM.stride(0), us, ldus, C.c_void_p(DSUM.data_ptr()), DSUM.stride(0),
+            C.c_void_p(XP.data_ptr()), XP.stride(0), C.c_void_p(SSUM.data_ptr()), SSUM.stride(0), self._stream(stream, X)))
+
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
         self._check(self._lib.towr_gpu_set_products_chunk(self._h, int(k)))
