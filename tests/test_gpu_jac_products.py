@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests.configs import config_descs
+from tests.gpu_helpers import _bits, _dev, _nan, _padded, _same_bits
 from towr2025_amd import TowrGpuProblem, _capi as capi
 from towr2025_amd.problem import TowrGpuError
 
@@ -28,34 +29,6 @@ CASES = [("monoped_procedural", 1), ("monoped_procedural", 3), ("anymal_trot_2p4
          ("anymal_stairs_gaitopt", 3), ("hopper_gait_torque", 2), ("anymal_trot_rotvec", 3)]
 U = 2.0 ** -53
 EXT = np.finfo(np.longdouble).nmant > 52
-
-
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def _nan(rows, cols):
-    import torch
-    return torch.full((rows, cols), float("nan"), dtype=torch.float64, device=_dev())
-
-
-def _padded(a, ld):
-    """host (B, k) array -> device (B, ld) tensor, NaN beyond column k"""
-    import torch
-    t = _nan(a.shape[0], ld)
-    t[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-    return t
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int64)
-
-
-def _same_bits(a, b):
-    import torch
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _lds(p):

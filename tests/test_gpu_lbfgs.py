@@ -28,7 +28,7 @@ import pytest
 
 from tests import lbfgs_ref as R
 from tests.configs import config_descs, cost_descs
-from tests.test_gpu_step import _dev, _formulation, _nan, _np_bits, _padded, _same_bits, _terrains, _vec
+from tests.gpu_helpers import _dev, _formulation, _nan, _np_bits, _padded, _same_bits, _terrains, _vec
 from towr2025_amd import TowrGpuProblem
 from towr2025_amd import formulation as F
 
@@ -475,8 +475,8 @@ def test_direction_keeps_the_kept_jacobian():
 def test_fused_entry_is_bit_identical_to_the_separate_calls(name, B):
     """Three consecutive iterations (the first without XPREV) of eval_cost_batch_device (GRAD = GR),
     eval_auglag_batch_device (accumulate), lbfgs_update_batch_device, lbfgs_direction_batch_device and
-    step_batch_device against auglag_lbfgs_step_batch_device, at the automatic chunk and at chunk 1, with batch
-    terrains set."""
+    step_batch_device against auglag_lbfgs_step_batch_device, at the automatic chunk and at chunks 1 and 2 (a ragged last
+    chunk), with batch terrains set."""
     import torch
     gait = name == "anymal_stairs_gaitopt_costs"
     f = F.with_costs(F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True) if gait else F.anymal_trot())
@@ -536,7 +536,7 @@ def test_fused_entry_is_bit_identical_to_the_separate_calls(name, B):
     print(f"{name}: pairs accepted per problem {want[2]['M'].cpu().numpy()[:, 0].tolist()}, used {want[2]['DS'][:, 0].tolist()}")
     assert (want[2]["M"][:, 0] > 0).any() and (want[2]["DS"][:, 0] > 0).any(), "the history stayed empty: the comparison would show nothing"
     try:
-        for chunk in (0, 1):
+        for chunk in (0, 1, 2):
             for with_f in (True, False):
                 p.set_products_chunk(chunk)
                 got = fused(with_f)

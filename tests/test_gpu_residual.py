@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from tests.configs import config_descs, ext_cases
+from tests.gpu_helpers import _dev, _nan, _np_bits, _padded, _same_bits, _vec
 from towr2025_amd import TowrGpuProblem, _capi as capi
 
 pytestmark = pytest.mark.gpu
@@ -27,37 +28,6 @@ U = 2.0 ** -53
 CASES = [("monoped_procedural", 1), ("monoped_procedural", 3), ("anymal_trot_2p4s", 37), ("anymal_stairs_gaitopt", 3),
          ("procedural_soft", 2)]
 RHOS = (1.0, 1e3)
-
-
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def _nan(rows, cols):
-    import torch
-    return torch.full((rows, cols), float("nan"), dtype=torch.float64, device=_dev())
-
-
-def _padded(a, ld):
-    import torch
-    t = _nan(a.shape[0], ld)
-    t[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-    return t
-
-
-def _vec(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(_dev())
-
-
-def _same_bits(a, b):
-    import torch
-    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-
-
-def _np_bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _desc(name):

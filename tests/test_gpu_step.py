@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests.configs import config_descs, cost_descs
+from tests.gpu_helpers import _dev, _formulation, _nan, _np_bits, _padded, _same_bits, _terrains, _vec
 from towr2025_amd import TowrGpuProblem, _capi as capi
 from towr2025_amd import formulation as F
 
@@ -29,48 +30,6 @@ U = 2.0 ** -53
 # of nothing; schedule sets with a real box
 CASES = [("monoped_procedural", 1), ("monoped_procedural", 3), ("anymal_trot_2p4s", 37), ("anymal_stairs_gaitopt", 3)]
 ALPHA = 0.37
-
-
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def _nan(rows, cols):
-    import torch
-    return torch.full((rows, cols), float("nan"), dtype=torch.float64, device=_dev())
-
-
-def _padded(a, ld):
-    import torch
-    t = _nan(a.shape[0], ld)
-    t[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-    return t
-
-
-def _vec(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(_dev())
-
-
-def _same_bits(a, b):
-    import torch
-    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-
-
-def _np_bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _formulation(name):
-    """The formulation of a configuration of tests/configs.py and the arguments of its var_bounds_data()."""
-    if name == "monoped_procedural":
-        f, vs, cs, goal, T = F.procedural_monoped()
-        return f, dict(varsets=vs, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)
-    f = {"anymal_trot_2p4s": lambda: F.anymal_trot(),
-         "anymal_stairs_gaitopt": lambda: F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True)}[name]()
-    f.params_.enable_stance_tracking = False
-    return f, {}
 
 
 def reference(X, D, a, lo, up, col0):
@@ -327,21 +286,11 @@ def test_step_keeps_the_kept_jacobian():
     assert np.array_equal(v.view(np.int64), v_ref.view(np.int64))
 
 
-def _terrains(name, B, rng):
-    out = []
-    for b in range(B):
-        if name == "anymal_all_costs" and b % 2:
-            t = F.HeightMap.Flat(rng.uniform(0, 0.3))
-        else:
-            t = F.HeightMap(F.HeightMap.StairsID, (rng.uniform(0.8, 1.4), 0.4, rng.uniform(0.1, 0.25), rng.uniform(0.1, 0.25), 1.0))
-        out.append(t.to_c())
-    return out
-
-
 @pytest.mark.parametrize("name,B", [("anymal_all_costs", 5), ("anymal_stairs_gaitopt_costs", 3)])
 def test_fused_entry_is_bit_identical_to_the_three_calls(name, B):
     """eval_cost_batch_device (GRAD), eval_auglag_batch_device (accumulate) and step_batch_device in sequence against
-    auglag_step_batch_device, at the automatic chunk and at chunk 1, with batch terrains set."""
+    auglag_step_batch_device, at the automatic chunk and at chunks 1 and 2 (a ragged last chunk), with batch terrains
+    set."""
     import torch
     gait = name == "anymal_stairs_gaitopt_costs"
     f = F.with_costs(F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True) if gait else F.anymal_trot())
@@ -371,7 +320,7 @@ def test_fused_entry_is_bit_identical_to_the_three_calls(name, B):
     assert_inputs_exercise_the_clamp(ref, name)
     check(f"{name} separate", p, SS0, XP0, ref, ns)
     try:
-        for k in (0, 1):
+        for k in (0, 1, 2):
             p.set_products_chunk(k)
             Fk = torch.full((B,), float("nan"), dtype=torch.float64, device=_dev())
             G, LAMP, RS = _nan(B, p.m + 2), _nan(B, p.m + 5), _nan(B, 4 + nc + 3)

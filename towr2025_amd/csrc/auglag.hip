@@ -1,0 +1,527 @@
+// auglag.hip — the batched solver-step entry points of the C-ABI (include/towr_gpu.h), what a device-resident
+// augmented-Lagrangian loop calls between evaluations: Jacobian products (J p, J^T lam), constraint residuals and
+// multiplier updates, the projected step, the L-BFGS history and direction, and the fused sequences of these behind
+// an evaluation. Host code only: the kernels live in jprod.hip, resid.hip, step.hip and lbfgs.hip, their argument
+// structs in layout.h. The evaluator (towr_gpu.hip) is used through handle.h alone: launch, launch_cost,
+// batch_terrain, bind and the scratch helpers.
+//
+// Every entry point checks its arguments first (before bind: a layout-only handle still answers them), puts the
+// caller's operands into the kernel's argument struct (layout.h; they lead it, in the C signature's order) and hands
+// that to a launcher, which adds what the handle owns.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "handle.h"
+
+using namespace tg;
+using namespace tg::host;
+
+void towr_gpu_handle_s::AugLag::release() {
+  for (void* p : d_jp) if (p) (void)hipFree(p);
+  void* rest[] = {d_pv, d_set_row0, d_blo, d_bup, d_rg, d_rl, d_set_col0, d_xlo, d_xup, d_sd, d_sf};
+  for (void* p : rest) if (p) (void)hipFree(p);
+}
+
+namespace {
+
+// ---- padding and chunking -------------------------------------------------------------------------------------------
+// leading dimension of a scratch matrix with k columns: rows on 128-byte boundaries
+int64_t ld16(int64_t k) { return std::max<int64_t>(16, (k + 15) & ~int64_t(15)); }
+
+// Problems per chunk of a fused entry's values scratch (d_pv): towr_gpu_set_products_chunk, or automatic.
+// Automatic chunk: measured, a chunk sized to the Infinity Cache (128 MiB of values) gains nothing — the
+// fused call at chunk = B costs what the three separate calls cost — and every further chunk costs its launch
+// sequence and an underfilled chip (ANYmal gait, B = 1024: 18.8 ms in 15 chunks vs 2.6 ms in one). So the chunk is
+// as large as a 2 GiB scratch allows (the footprint bound), cut into equal parts.
+int chunk_plan(towr_gpu_handle h, int B) {
+  constexpr int64_t kAutoBytes = int64_t(2) << 30;
+  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ld16(h->L.nnz)));
+  const int64_t parts = (B + cap - 1) / cap;
+  return (int)std::min<int64_t>(B, h->al.products_chunk > 0 ? h->al.products_chunk : (B + parts - 1) / parts);
+}
+
+// row c0 of an optional operand (NULL stays NULL)
+template <class T>
+T* row_at(T* p, int c0, int64_t ld) { return p ? p + (int64_t)c0 * ld : nullptr; }
+
+// ---- device tables --------------------------------------------------------------------------------------------------
+// Tables uploaded together on the first call that needs them (towr_gpu_create and the single-problem callbacks never
+// pay for them; synchronous copies: that first call is not asynchronous). add() uploads one unless an earlier one
+// failed; commit() stores the device pointers where they belong, or frees them all if any upload failed.
+struct Uploads {
+  towr_gpu_handle h;
+  int rc = TOWR_OK;
+  std::vector<std::pair<const void**, void*>> made;   // (where it belongs, the device copy)
+  template <class T, class U>
+  void add(U** dst, const std::vector<T>& src) {   // U: T or const T
+    T* d = nullptr;
+    if (rc == TOWR_OK) rc = upload(h, &d, src);
+    if (d) made.emplace_back((const void**)dst, d);
+  }
+  int commit() {
+    for (auto& m : made) if (rc) (void)hipFree(m.second); else *m.first = m.second;
+    return rc;
+  }
+};
+
+int products_ready(towr_gpu_handle h) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.jp_ready) return TOWR_OK;
+  const Layout& L = h->L;
+  const size_t lv = jp_vec_lds(L.n, L.m), lt = jp_tvec_lds(L.n, L.m);
+  if (std::max(lv, lt) > kLdsMax) return fail(h, TOWR_ERR_UNSUPPORTED, "problem too large for the product kernels' LDS");
+  if ((lv > 64 * 1024 && hipFuncSetAttribute(jp_vec_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lv) != hipSuccess) ||
+      (lt > 64 * 1024 && hipFuncSetAttribute(jp_tvec_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lt) != hipSuccess))
+    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  const std::vector<int32_t> cp32(L.col_ptr.begin(), L.col_ptr.end());
+  Uploads u{h};
+  JpArgs a{};
+  u.add(&a.col, L.col); u.add(&a.row, L.jp_row); u.add(&a.cidx, L.jp_cidx); u.add(&a.rseg, L.jp_rseg); u.add(&a.cseg, L.jp_cseg);
+  u.add(&a.chunks, L.jp_chunks); u.add(&a.empty_rows, L.jp_empty_rows); u.add(&a.col_ptr, cp32);
+  if (int rc = u.commit()) return rc;
+  a.nnz = L.nnz; a.n = L.n; a.m = L.m;
+  a.n_chunks = (int32_t)L.jp_chunks.size(); a.n_empty = (int32_t)L.jp_empty_rows.size();
+  for (size_t i = 0; i < u.made.size(); ++i) al.d_jp[i] = u.made[i].second;
+  al.jp = a;
+  al.jp_ready = true;
+  return TOWR_OK;
+}
+
+// the residual kernel's tables: the sets' row ranges and, when every set's bounds are known, the description bounds
+int residual_ready(towr_gpu_handle h) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.res_ready) return TOWR_OK;
+  const Layout& L = h->L;
+  std::vector<int32_t> row0;
+  for (const ConsInfo& c : L.cons) row0.push_back(c.row0);
+  row0.push_back(L.m);
+  Uploads u{h};
+  u.add(&al.d_set_row0, row0);
+  if (L.bounds_err.empty()) { u.add(&al.d_blo, L.g_lower); u.add(&al.d_bup, L.g_upper); }
+  if (int rc = u.commit()) return rc;
+  al.res_ready = true;
+  return TOWR_OK;
+}
+
+// the step kernel's tables: the variable sets' column ranges and the description's variable bounds
+int step_ready(towr_gpu_handle h) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.step_ready) return TOWR_OK;
+  const Layout& L = h->L;
+  std::vector<int32_t> col0;
+  for (const VarSetInfo& v : L.varsets) col0.push_back(v.col0);
+  col0.push_back(L.n);
+  Uploads u{h};
+  u.add(&al.d_set_col0, col0); u.add(&al.d_xlo, L.x_lower); u.add(&al.d_xup, L.x_upper);
+  if (int rc = u.commit()) return rc;
+  al.step_ready = true;
+  return TOWR_OK;
+}
+
+// ---- argument checks (before anything runs) ------------------------------------------------------------------------
+// optional bounds (lo, up), `pair` in messages: both or neither; ldb is 0 (one row for every problem) or >= dim (`d`)
+int box_args(towr_gpu_handle h, const double* lo, const double* up, int64_t ldb, int64_t dim, const char* pair, const char* d) {
+  if ((lo == nullptr) != (up == nullptr)) return fail(h, TOWR_ERR_INVALID, std::string("only one of ") + pair + " given");
+  if (lo && ldb != 0 && ldb < dim) return fail(h, TOWR_ERR_INVALID, std::string("ldb must be 0 (shared bounds) or >= ") + d);
+  return TOWR_OK;
+}
+
+// the residual stage's operands (G is the entry's own business). lamp: the multiplier update runs — always in the
+// fused entries, where a NULL LAMP only keeps lam+ in handle scratch
+int residual_args(towr_gpu_handle h, const ResArgs& a, bool lamp) {
+  const Layout& L = h->L;
+  if (!a.SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
+  if (a.lds < 4 + (int64_t)L.cons.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 4 + n_constraints");
+  if (int rc = box_args(h, a.GL, a.GU, a.ldb, L.m, "GL / GU", "m")) return rc;
+  if (!a.GL && !L.bounds_err.empty()) return fail(h, TOWR_ERR_INVALID, L.bounds_err);
+  if (lamp && !(a.rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 with LAMP");
+  if (a.LAMP && a.ldlp < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAMP smaller than m");
+  if (lamp && a.LAM && a.ldl < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAM smaller than m");
+  return TOWR_OK;
+}
+
+// the step stage's operands (X, D and their leading dimensions are the entry's own business)
+int step_args(towr_gpu_handle h, const StepArgs& a) {
+  const Layout& L = h->L;
+  if (!a.SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
+  if (a.lds < 5 + (int64_t)L.varsets.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 5 + n_varsets");
+  if (int rc = box_args(h, a.XL, a.XU, a.ldb, L.n, "XL / XU", "n")) return rc;
+  if (!a.ALPHA && a.alpha != a.alpha) return fail(h, TOWR_ERR_INVALID, "alpha is NaN");
+  if (a.XP && a.ldxp < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of XP smaller than n");
+  return TOWR_OK;
+}
+
+// the history and summary of an L-BFGS stage (a: LbfgsUpdateArgs, lds_min 6, or LbfgsDirArgs, 5)
+template <class Args>
+int lbfgs_args(towr_gpu_handle h, const Args& a, int64_t lds_min) {
+  if (!a.HS || !a.HY || !a.HMETA) return fail(h, TOWR_ERR_INVALID, "null HS, HY or HMETA");
+  if (!a.SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
+  if (a.mem < 1 || a.mem > TOWR_LBFGS_MAX_MEM) return fail(h, TOWR_ERR_INVALID, "mem outside 1..TOWR_LBFGS_MAX_MEM");
+  if (a.ldh < h->L.n) return fail(h, TOWR_ERR_INVALID, "ldh smaller than n");
+  if (a.lds < lds_min) return fail(h, TOWR_ERR_INVALID, lds_min == 6 ? "lds smaller than 6" : "lds smaller than 5");
+  return TOWR_OK;
+}
+// the kernels' per-column state lives in LDS: the handle's n must fit (after bind: a layout-only handle has answered)
+int lbfgs_fits(towr_gpu_handle h) {
+  if (std::max(lbfgs_update_lds(h->L.n), lbfgs_direction_lds(h->L.n)) > kLbfgsMaxLds)
+    return fail(h, TOWR_ERR_UNSUPPORTED, "n too large for the L-BFGS kernels' LDS");
+  return TOWR_OK;
+}
+
+// ---- launchers: one block per problem; the caller's operands in `a`, the handle's tables and sizes added here ----------
+// one product's operands: Y = J p (Vec = P, Out = Y) or Z (+)= J^T lam (Vec = LAM, Out = Z)
+JpArgs product(const double* V, int64_t ldv, const double* vec, int64_t ldvec, double* out, int64_t ldo, int accumulate) {
+  JpArgs a{V, ldv, vec, ldvec, out, ldo};
+  a.accumulate = accumulate;
+  return a;
+}
+int launch_product(towr_gpu_handle h, bool tvec, int B, const JpArgs& call, hipStream_t s) {
+  JpArgs a = h->al.jp;   // the tables (products_ready)
+  a.V = call.V; a.ldv = call.ldv; a.Vec = call.Vec; a.ldvec = call.ldvec; a.Out = call.Out; a.ldo = call.ldo;
+  a.accumulate = call.accumulate;
+  const size_t lds = tvec ? jp_tvec_lds(a.n, a.m) : jp_vec_lds(a.n, a.m);
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(tvec ? jp_tvec_kernel() : jp_vec_kernel(), dim3((unsigned)B), dim3(kJpBlock), args, lds, s));
+  return TOWR_OK;
+}
+
+// (GL NULL: the handle's bounds, one row; without LAMP only the violation summary: LAM and rho are not used)
+int launch_residual(towr_gpu_handle h, int B, ResArgs a, hipStream_t s) {
+  if (!a.GL) { a.GL = h->al.d_blo; a.GU = h->al.d_bup; a.ldb = 0; }
+  if (!a.LAMP) { a.LAM = nullptr; a.rho = 1.0; }
+  a.set_row0 = h->al.d_set_row0; a.m = h->L.m; a.n_sets = (int32_t)h->L.cons.size();
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(res_kernel(), dim3((unsigned)B), dim3(kResBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+// (XL NULL: the handle's bounds, one row)
+int launch_step(towr_gpu_handle h, int B, StepArgs a, hipStream_t s) {
+  if (!a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
+  a.set_col0 = h->al.d_set_col0; a.n = h->L.n; a.n_sets = (int32_t)h->L.varsets.size();
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(step_kernel(), dim3((unsigned)B), dim3(kStepBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+int launch_lbfgs_update(towr_gpu_handle h, int B, LbfgsUpdateArgs a, hipStream_t s) {
+  a.n = h->L.n;
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(lbfgs_update_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_update_lds(a.n), s));
+  return TOWR_OK;
+}
+
+// (XL NULL: the handle's bounds, one row — with X, after step_ready)
+int launch_lbfgs_direction(towr_gpu_handle h, int B, LbfgsDirArgs a, hipStream_t s) {
+  if (!a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
+  a.n = h->L.n;
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(lbfgs_direction_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_direction_lds(a.n), s));
+  return TOWR_OK;
+}
+
+// ---- fused calls ----------------------------------------------------------------------------------------------------
+// the stream and terrains of a fused call
+struct Batch {
+  hipStream_t s;
+  const towr_terrain_t* ter;
+  int per;
+  const towr_terrain_t* terrain_at(int c0) const { return per ? ter + c0 : ter; }
+};
+
+// What the fused entries share behind bind: the batch terrains, nothing to do for B = 0, the tables the call needs
+// (`ready`), then body(batch) holding the handle's scratch on the caller's stream — acquired once the tables are ready,
+// released on every path behind that (also after a failure: what was queued still orders the scratch); the first code
+// that is not TOWR_OK is the answer. A call that needs no table uses none of this file's scratch: its body runs as it is.
+using Ready = int (*)(towr_gpu_handle);
+template <class Body>
+int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> ready, Body body) {
+  Batch b{reinterpret_cast<hipStream_t>(stream), nullptr, 0};
+  if (int rc = batch_terrain(h, B, false, &b.ter, &b.per)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (ready.size() == 0) return body(b);
+  for (Ready r : ready)
+    if (int rc = r(h)) return rc;
+  if (int rc = scratch_acquire(h, b.s)) return rc;
+  const int rc = body(b);
+  const int rr = scratch_release(h, b.s);
+  return rc ? rc : rr;
+}
+
+// The chunks of towr_gpu_eval_auglag_batch_device, shared by the two step entries (inside fused()): per chunk of
+// problems the evaluation at e.X (values into d_pv, never d_v, so the kept Jacobian survives), the residual kernel on
+// that g and the J^T product with lam+ into z.Out, back to back on the caller's stream. e.G / r.LAMP NULL: g / lam+
+// stay in handle scratch (d_rg / d_rl). e, r and z hold the whole batch's operands (r.G, z.V and z.Vec are not used); a
+// chunk launches with its rows of them.
+struct EvalStage { const double* X; int64_t ldx; double* G; int64_t ldg; };
+int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r, const JpArgs& z, const Batch& b) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  const int64_t ldv = ld16(h->L.nnz), ldr = ld16(h->L.m);
+  const int C = chunk_plan(h, B);
+  int rc = scratch_grow(h, &al.d_pv, &al.pv_cap, C, ldv);
+  if (rc == TOWR_OK && !e.G) rc = scratch_grow(h, &al.d_rg, &al.rg_cap, C, ldr);
+  if (rc == TOWR_OK && !r.LAMP) rc = scratch_grow(h, &al.d_rl, &al.rl_cap, C, ldr);
+  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
+    const int cb = std::min(C, B - c0);
+    double* g = e.G ? e.G + (int64_t)c0 * e.ldg : al.d_rg;
+    ResArgs a = r;
+    a.G = g; a.ldg = e.G ? e.ldg : ldr;
+    if (r.LAMP) a.LAMP = r.LAMP + (int64_t)c0 * r.ldlp; else { a.LAMP = al.d_rl; a.ldlp = ldr; }
+    a.GL = row_at(r.GL, c0, r.ldb); a.GU = row_at(r.GU, c0, r.ldb); a.LAM = row_at(r.LAM, c0, r.ldl);
+    a.SUM = r.SUM + (int64_t)c0 * r.lds;
+    rc = launch(h, cb, e.X + (int64_t)c0 * e.ldx, e.ldx, g, a.ldg, al.d_pv, ldv, 1, 1, b.s, b.terrain_at(c0), b.per, -1);
+    if (rc == TOWR_OK) rc = launch_residual(h, cb, a, b.s);
+    if (rc == TOWR_OK)
+      rc = launch_product(h, true, cb, product(al.d_pv, ldv, a.LAMP, a.ldlp, z.Out + (int64_t)c0 * z.ldo, z.ldo, z.accumulate), b.s);
+  }
+  return rc;
+}
+
+}  // namespace
+
+// =================================================================================================
+// C-ABI
+// =================================================================================================
+extern "C" {
+
+// ---- Jacobian products (jprod.hip) ----------------------------------------------------------------------------
+int towr_gpu_jac_csc(towr_gpu_handle h, int64_t* col_ptr, int32_t* row, int32_t* csr_index) {
+  if (!h || !col_ptr || !row || !csr_index) return fail(h, TOWR_ERR_INVALID, "null argument");
+  const Layout& L = h->L;
+  std::memcpy(col_ptr, L.col_ptr.data(), sizeof(int64_t) * L.col_ptr.size());
+  if (L.nnz) {
+    std::memcpy(row, L.csc_row.data(), sizeof(int32_t) * L.csc_row.size());
+    std::memcpy(csr_index, L.csc_index.data(), sizeof(int32_t) * L.csc_index.size());
+  }
+  return TOWR_OK;
+}
+
+int towr_gpu_jac_vec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv, const double* P, int64_t ldp,
+                                  double* Y, int64_t ldy, void* stream) {
+  if (!h || B < 0 || !V || !P || !Y) return fail(h, TOWR_ERR_INVALID, "bad argument (null pointer or B < 0)");
+  const Layout& L = h->L;
+  if (ldv < L.nnz || ldp < L.n || ldy < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / n (P) / m (Y)");
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = products_ready(h)) return rc;
+  return launch_product(h, false, B, product(V, ldv, P, ldp, Y, ldy, 0), reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_jac_tvec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv, const double* LAM, int64_t ldl,
+                                   double* Z, int64_t ldz, int32_t accumulate, void* stream) {
+  if (!h || B < 0 || !V || !LAM || !Z) return fail(h, TOWR_ERR_INVALID, "bad argument (null pointer or B < 0)");
+  const Layout& L = h->L;
+  if (ldv < L.nnz || ldl < L.m || ldz < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAM) / n (Z)");
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = products_ready(h)) return rc;
+  return launch_product(h, true, B, product(V, ldv, LAM, ldl, Z, ldz, accumulate != 0), reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_set_products_chunk(towr_gpu_handle h, int32_t problems) {
+  if (!h || problems < 0) return fail(h, TOWR_ERR_INVALID, "bad argument");
+  h->al.products_chunk = problems;
+  return TOWR_OK;
+}
+
+// The values of `chunk` problems at a time in the handle's own scratch (d_pv, ordered across streams like the other
+// scratch: fused()), each chunk evaluated by the batch launch sequence and consumed by the product kernels behind it
+// on the caller's stream. Without LAM and P there are no values to keep: the plain evaluation of g.
+int towr_gpu_eval_products_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, double* G, int64_t ldg,
+                                        const double* LAM, int64_t ldl, double* Z, int64_t ldz, int32_t accumulate,
+                                        const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream) {
+  if (!h || B < 0 || !X) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or B < 0)");
+  const Layout& L = h->L;
+  if ((Z && !LAM) || (Y && !P)) return fail(h, TOWR_ERR_INVALID, "Z given without LAM, or Y without P");
+  if ((LAM && !Z) || (P && !Y)) return fail(h, TOWR_ERR_INVALID, "LAM given without Z, or P without Y");
+  if (ldx < L.n || (G && ldg < L.m) || (LAM && (ldl < L.m || ldz < L.n)) || (P && (ldp < L.n || ldy < L.m)))
+    return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X, P, Z) / m (G, LAM, Y)");
+  if (int rc = bind(h)) return rc;
+  const bool want_v = LAM || P;
+  auto none = std::initializer_list<Ready>{};
+  return fused(h, B, stream, want_v ? std::initializer_list<Ready>{products_ready} : none, [&](const Batch& b) -> int {
+    if (!want_v) return G ? launch(h, B, X, ldx, G, ldg, nullptr, 0, 1, 0, b.s, b.ter, b.per, -1) : TOWR_OK;
+    towr_gpu_handle_s::AugLag& al = h->al;
+    const int64_t ldv = ld16(L.nnz);
+    const int C = chunk_plan(h, B);
+    int rc = scratch_grow(h, &al.d_pv, &al.pv_cap, C, ldv);
+    for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
+      const int cb = std::min(C, B - c0);
+      rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, row_at(G, c0, ldg), ldg, al.d_pv, ldv, G != nullptr, 1, b.s, b.terrain_at(c0),
+                  b.per, -1);
+      if (rc == TOWR_OK && LAM)
+        rc = launch_product(h, true, cb, product(al.d_pv, ldv, LAM + (int64_t)c0 * ldl, ldl, Z + (int64_t)c0 * ldz, ldz, accumulate != 0),
+                            b.s);
+      if (rc == TOWR_OK && P)
+        rc = launch_product(h, false, cb, product(al.d_pv, ldv, P + (int64_t)c0 * ldp, ldp, Y + (int64_t)c0 * ldy, ldy, 0), b.s);
+    }
+    return rc;
+  });
+}
+
+// ---- residuals (resid.hip) ---------------------------------------------------------------------------------------
+int towr_gpu_residual_batch_device(towr_gpu_handle h, int32_t B, const double* G, int64_t ldg, const double* GL, const double* GU,
+                                   int64_t ldb, const double* LAM, int64_t ldl, double rho, double* LAMP, int64_t ldlp,
+                                   double* SUM, int64_t lds, void* stream) {
+  if (!h || B < 0 || !G) return fail(h, TOWR_ERR_INVALID, "bad argument (null G or B < 0)");
+  if (ldg < h->L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of G smaller than m");
+  ResArgs a{G, ldg, GL, GU, ldb, LAM, ldl, LAMP, ldlp, SUM, lds};
+  a.rho = rho;
+  if (int rc = residual_args(h, a, LAMP != nullptr)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = residual_ready(h)) return rc;
+  return launch_residual(h, B, a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// As towr_gpu_eval_products_batch_device: a chunk of problems at a time through the handle's scratch (the values in
+// d_pv; g and lam+ in d_rg / d_rl when the caller does not want them), the three launches of a chunk back to back on
+// the caller's stream (auglag_chunks).
+int towr_gpu_eval_auglag_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* GL, const double* GU,
+                                      int64_t ldb, const double* LAM, int64_t ldl, double rho, double* G, int64_t ldg,
+                                      double* LAMP, int64_t ldlp, double* SUM, int64_t lds, double* Z, int64_t ldz,
+                                      int32_t accumulate, void* stream) {
+  if (!h || B < 0 || !X || !Z) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or Z, or B < 0)");
+  const Layout& L = h->L;
+  if (ldx < L.n || ldz < L.n || (G && ldg < L.m)) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X, Z) / m (G)");
+  ResArgs r{nullptr, 0, GL, GU, ldb, LAM, ldl, LAMP, ldlp, SUM, lds};   // (G: the evaluation's, auglag_chunks)
+  r.rho = rho;
+  if (int rc = residual_args(h, r, true)) return rc;
+  if (int rc = bind(h)) return rc;
+  return fused(h, B, stream, {products_ready, residual_ready}, [&](const Batch& b) {
+    return auglag_chunks(h, B, EvalStage{X, ldx, G, ldg}, r, product(nullptr, 0, nullptr, 0, Z, ldz, accumulate != 0), b);
+  });
+}
+
+// ---- steps (step.hip) ----------------------------------------------------------------------------------------------
+int towr_gpu_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* D, int64_t ldd,
+                               const double* ALPHA, double alpha, const double* XL, const double* XU, int64_t ldb,
+                               double* XP, int64_t ldxp, double* SUM, int64_t lds, void* stream) {
+  if (!h || B < 0 || !X || !D) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or D, or B < 0)");
+  if (ldx < h->L.n || ldd < h->L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X or D smaller than n");
+  const StepArgs a{X, ldx, D, ldd, ALPHA, alpha, XL, XU, ldb, XP, ldxp, SUM, lds};
+  if (int rc = step_args(h, a)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = step_ready(h)) return rc;
+  return launch_step(h, B, a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The gradient of the whole batch in handle scratch (d_sd: grad f from the cost launch, then + J^T lam+ per chunk of
+// the auglag sequence), the step kernel behind it: what the three public calls launch, on the caller's stream.
+int towr_gpu_auglag_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* GL, const double* GU,
+                                      int64_t ldgb, const double* LAM, int64_t ldl, double rho, const double* ALPHA, double alpha,
+                                      const double* XL, const double* XU, int64_t ldxb, double* F, double* G, int64_t ldg,
+                                      double* LAMP, int64_t ldlp, double* RSUM, int64_t ldrs, double* XP, int64_t ldxp,
+                                      double* SSUM, int64_t ldss, void* stream) {
+  if (!h || B < 0 || !X || !XP) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or XP, or B < 0)");
+  const Layout& L = h->L;
+  if (ldx < L.n || (G && ldg < L.m)) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X) / m (G)");
+  ResArgs r{nullptr, 0, GL, GU, ldgb, LAM, ldl, LAMP, ldlp, RSUM, ldrs};
+  r.rho = rho;
+  if (int rc = residual_args(h, r, true)) return rc;
+  StepArgs st{X, ldx, nullptr, 0, ALPHA, alpha, XL, XU, ldxb, XP, ldxp, SSUM, ldss};   // (D: handle scratch, set below)
+  if (int rc = step_args(h, st)) return rc;
+  if (int rc = bind(h)) return rc;
+  return fused(h, B, stream, {products_ready, residual_ready, step_ready}, [&](const Batch& b) {
+    towr_gpu_handle_s::AugLag& al = h->al;
+    const int64_t ldn = ld16(L.n);
+    int rc = scratch_grow(h, &al.d_sd, &al.sd_cap, B, ldn);
+    if (rc == TOWR_OK && !F) rc = scratch_grow(h, &al.d_sf, &al.sf_cap, B, 1);
+    if (rc == TOWR_OK) rc = launch_cost(h, B, X, ldx, F ? F : al.d_sf, al.d_sd, ldn, b.s, b.ter, b.per);
+    if (rc == TOWR_OK) rc = auglag_chunks(h, B, EvalStage{X, ldx, G, ldg}, r, product(nullptr, 0, nullptr, 0, al.d_sd, ldn, 1), b);
+    st.D = al.d_sd; st.ldd = ldn;
+    if (rc == TOWR_OK) rc = launch_step(h, B, st, b.s);
+    return rc;
+  });
+}
+
+// ---- L-BFGS (lbfgs.hip) --------------------------------------------------------------------------------------------
+int towr_gpu_lbfgs_update_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx, const double* XN,
+                                       int64_t ldxn, const double* GR, int64_t ldgr, const double* GRN, int64_t ldgrn,
+                                       double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA, double* SUM,
+                                       int64_t lds, void* stream) {
+  if (!h || B < 0 || !X || !XN || !GR || !GRN) return fail(h, TOWR_ERR_INVALID, "bad argument (null X, XN, GR or GRN, or B < 0)");
+  const int n = h->L.n;
+  if (ldx < n || ldxn < n || ldgr < n || ldgrn < n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X, XN, GR or GRN smaller than n");
+  const LbfgsUpdateArgs a{X, ldx, XN, ldxn, GR, ldgr, GRN, ldgrn, HS, HY, ldh, HMETA, SUM, lds, curv_eps, 0, mem};
+  if (int rc = lbfgs_args(h, a, 6)) return rc;
+  if (!(curv_eps >= 0)) return fail(h, TOWR_ERR_INVALID, "curv_eps is negative or NaN");
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  return launch_lbfgs_update(h, B, a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_lbfgs_direction_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx, const double* GR,
+                                          int64_t ldgr, const double* XL, const double* XU, int64_t ldb, const double* HS,
+                                          const double* HY, int64_t ldh, const int32_t* HMETA, double* D, int64_t ldd, double* SUM,
+                                          int64_t lds, void* stream) {
+  if (!h || B < 0 || !GR || !D) return fail(h, TOWR_ERR_INVALID, "bad argument (null GR or D, or B < 0)");
+  const int n = h->L.n;
+  if ((X && ldx < n) || ldgr < n || ldd < n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X, GR or D smaller than n");
+  const LbfgsDirArgs a{X, ldx, GR, ldgr, XL, XU, ldb, HS, HY, ldh, HMETA, D, ldd, SUM, lds, 0, mem};
+  if (int rc = lbfgs_args(h, a, 5)) return rc;
+  if (int rc = box_args(h, XL, XU, ldb, n, "XL / XU", "n")) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (X && !XL)
+    if (int rc = step_ready(h)) return rc;
+  return launch_lbfgs_direction(h, B, a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The gradient of the augmented Lagrangian in the caller's GR (grad f from the cost launch, then + J^T lam+ per chunk of
+// the auglag sequence; g and lam+ in handle scratch), the history update with (XPREV -> X, GRPREV -> GR), the
+// direction in handle scratch (d_sd) and the step kernel behind it: what the five public calls launch, on the
+// caller's stream.
+int towr_gpu_auglag_lbfgs_step_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx,
+                                            const double* XPREV, int64_t ldxprev, const double* GRPREV, int64_t ldgrprev,
+                                            const double* GL, const double* GU, int64_t ldgb, const double* LAM, int64_t ldl,
+                                            double rho, const double* ALPHA, double alpha, const double* XL, const double* XU,
+                                            int64_t ldxb, double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA,
+                                            double* F, double* GR, int64_t ldgr, double* RSUM, int64_t ldrs, double* USUM,
+                                            int64_t ldus, double* DSUM, int64_t ldds, double* XP, int64_t ldxp, double* SSUM,
+                                            int64_t ldss, void* stream) {
+  if (!h || B < 0 || !X || !XP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null X, XP or GR, or B < 0)");
+  const Layout& L = h->L;
+  if (ldx < L.n || ldgr < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X or GR smaller than n");
+  if ((XPREV == nullptr) != (GRPREV == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XPREV / GRPREV given");
+  if (XPREV && (ldxprev < L.n || ldgrprev < L.n)) return fail(h, TOWR_ERR_INVALID, "leading dimension of XPREV or GRPREV smaller than n");
+  ResArgs r{nullptr, 0, GL, GU, ldgb, LAM, ldl, nullptr, 0, RSUM, ldrs};   // (g and lam+ stay in handle scratch)
+  r.rho = rho;
+  if (int rc = residual_args(h, r, true)) return rc;
+  // the pair (X - XPREV, GR - GRPREV)
+  const LbfgsUpdateArgs up{XPREV, ldxprev, X, ldx, GRPREV, ldgrprev, GR, ldgr, HS, HY, ldh, HMETA, USUM, ldus, curv_eps, 0, mem};
+  if (XPREV)
+    if (int rc = lbfgs_args(h, up, 6)) return rc;
+  if (!(curv_eps >= 0)) return fail(h, TOWR_ERR_INVALID, "curv_eps is negative or NaN");   // (also without XPREV)
+  LbfgsDirArgs dir{X, ldx, GR, ldgr, XL, XU, ldxb, HS, HY, ldh, HMETA, nullptr, 0, DSUM, ldds, 0, mem};   // (D: as st.D)
+  if (int rc = lbfgs_args(h, dir, 5)) return rc;
+  StepArgs st{X, ldx, nullptr, 0, ALPHA, alpha, XL, XU, ldxb, XP, ldxp, SSUM, ldss};   // (D: handle scratch, set below)
+  if (int rc = step_args(h, st)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  return fused(h, B, stream, {products_ready, residual_ready, step_ready}, [&](const Batch& b) {
+    towr_gpu_handle_s::AugLag& al = h->al;
+    const int64_t ldn = ld16(L.n);
+    int rc = scratch_grow(h, &al.d_sd, &al.sd_cap, B, ldn);
+    if (rc == TOWR_OK && !F) rc = scratch_grow(h, &al.d_sf, &al.sf_cap, B, 1);
+    if (rc == TOWR_OK) rc = launch_cost(h, B, X, ldx, F ? F : al.d_sf, GR, ldgr, b.s, b.ter, b.per);
+    if (rc == TOWR_OK) rc = auglag_chunks(h, B, EvalStage{X, ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, GR, ldgr, 1), b);
+    if (rc == TOWR_OK && XPREV) rc = launch_lbfgs_update(h, B, up, b.s);
+    dir.D = al.d_sd; dir.ldd = ldn;
+    if (rc == TOWR_OK) rc = launch_lbfgs_direction(h, B, dir, b.s);
+    st.D = al.d_sd; st.ldd = ldn;
+    if (rc == TOWR_OK) rc = launch_step(h, B, st, b.s);
+    return rc;
+  });
+}
+
+}  // extern "C"

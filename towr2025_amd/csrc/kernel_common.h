@@ -1,6 +1,6 @@
 // kernel_common.h — device-side definitions shared by the engine's translation units
 // (tiles.hip: tile / small-kind / fused kernels; gstream.hip: the phase-duration path's record and
-// compose kernels; cost_traj.hip; towr_gpu.hip: the C-ABI): the launch parameter block and the staging
+// compose kernels; cost_traj.hip; towr_gpu.hip: the evaluator's C-ABI): the launch parameter block and the staging
 // and copy-out helpers.
 #pragma once
 
@@ -422,8 +422,9 @@ __device__ __forceinline__ Ctx gait_record_setup(const KParams& P, int b, double
   return c;
 }
 
-// Kernels of the other translation units, for the host side (towr_gpu.hip): tiles.hip (tile, small-kind
-// and fused kernels), cost_traj.hip (objective, trajectory export)
+// Kernels of the other translation units, for the evaluator's host side (towr_gpu.hip): tiles.hip (tile, small-kind
+// and fused kernels), cost_traj.hip (objective, trajectory export). The solver-step kernels (jprod.hip, resid.hip,
+// step.hip, lbfgs.hip) are declared in layout.h beside their argument structs, for their host side (auglag.hip).
 const void* tile_kernel_for(int type, bool gait, bool rotvec);
 const void* misc_kernel_for(bool gait);
 const void* step_kernel_for(bool gait, bool rotvec, int kblock);

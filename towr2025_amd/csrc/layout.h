@@ -231,6 +231,7 @@ struct TqBound { int32_t row, pcol[2], fcol[3]; double k; };
 // The residual kernel (resid.hip): per-problem violation summary of G against (GL, GU) and, with LAMP, the augmented
 // Lagrangian's multiplier update; one block of kResBlock threads per problem. set_row0[s] .. set_row0[s + 1] are the
 // rows of constraint set s (description order; a soft set's range is empty). ldb = 0: one bounds row for all problems.
+// The host side of this and the following kernels (argument checks, handle tables, launches) is auglag.hip.
 constexpr int kResBlock = 256;
 struct ResArgs {
   const double* G; int64_t ldg;
@@ -263,7 +264,7 @@ const void* step_kernel();
 // The L-BFGS kernels (lbfgs.hip): the per-problem ring of (s, y) pairs and the two-loop recursion on the free columns
 // (towr_gpu.h); one block of kLbfgsBlock threads per problem. Pair k of problem b starts at HS / HY + (b*mem + k)*ldh,
 // HMETA[2b] = count, HMETA[2b + 1] = next. The kernels keep per-column state in dynamic LDS: lbfgs_update_lds(n) /
-// lbfgs_direction_lds(n) bytes (the launcher refuses an n whose state does not fit kLbfgsMaxLds).
+// lbfgs_direction_lds(n) bytes (the host side, auglag.hip, refuses an n whose state does not fit kLbfgsMaxLds).
 constexpr int kLbfgsBlock = 256;
 constexpr int64_t kLbfgsMaxLds = 60 * 1024;   // beside the kernels' static reduction buffers, within the default 64 KiB
 inline int64_t lbfgs_update_lds(int n) { return 16 * (int64_t)n; }      // s and y
@@ -412,7 +413,8 @@ void build_jprod(Layout& L);   // fills the jp_ / csc members above from row_ptr
 // the (-L, L) rows of the node TorqueConstraints at x on terrain `ter`, written into lower / upper (m doubles each)
 void torque_bounds(const Layout& L, const double* x, const towr_terrain_t& ter, double* lower, double* upper);
 // the product kernels (jprod.hip): one block of kJpBlock threads per problem; Vec = P (ldvec >= n) and Out = Y for
-// J p, Vec = LAM (>= m) and Out = Z for J^T lam; the tables are the device copies of the members above
+// J p, Vec = LAM (>= m) and Out = Z for J^T lam; the tables are the device copies of the members above (uploaded and
+// launched by auglag.hip)
 struct JpArgs {
   const double* V; int64_t ldv;
   const double* Vec; int64_t ldvec;

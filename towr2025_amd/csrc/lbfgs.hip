@@ -17,13 +17,13 @@
 // block's place in the grid, the stream or timing: the bits are a function of the problem.
 #include <hip/hip_runtime.h>
 
+#include "consumer_common.h"
 #include "layout.h"
 
 namespace tg {
 namespace {
 
 constexpr int kLbfgsWaves = kLbfgsBlock / 64;
-constexpr double kSideInf = 1e19;   // as resid.hip / step.hip: a side beyond it does not count
 static_assert(kLbfgsMaxLds / 16 <= 32 * kLbfgsBlock, "the held mask is one 32-bit word per lane");
 static_assert(TOWR_LBFGS_MAX_MEM < 32, "the used pairs are one 32-bit mask");
 

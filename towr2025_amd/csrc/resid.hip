@@ -13,6 +13,7 @@
 // Nothing depends on B, the block's place in the grid, the stream or timing: the bits are a function of the problem.
 #include <hip/hip_runtime.h>
 
+#include "consumer_common.h"
 #include "layout.h"
 
 namespace tg {
@@ -20,10 +21,6 @@ namespace {
 
 constexpr int kResUnroll = 4;
 constexpr int kResWaves = kResBlock / 64;
-constexpr unsigned long long kNanBits = 0x7ff8000000000000ull;
-constexpr double kSideInf = 1e19;   // IPOPT's nlp_lower / upper_bound_inf: a side beyond it does not count
-
-__device__ inline unsigned long long v_bits(double v) { return v != v ? kNanBits : (unsigned long long)__double_as_longlong(v); }
 
 __global__ void __launch_bounds__(kResBlock) towr_residual_kernel(ResArgs a) {
   __shared__ int32_t s_row0[TOWR_MAX_CONSTRAINTS + 1];

@@ -16,6 +16,7 @@
 // stream or timing: the bits are a function of the problem.
 #include <hip/hip_runtime.h>
 
+#include "consumer_common.h"
 #include "layout.h"
 
 namespace tg {
@@ -27,10 +28,6 @@ namespace {
 #endif
 constexpr int kStepUnroll = TOWR_STEP_UNROLL;
 constexpr int kStepWaves = kStepBlock / 64;
-constexpr unsigned long long kNanBits = 0x7ff8000000000000ull;
-constexpr double kSideInf = 1e19;   // as resid.hip: a side beyond it does not count
-
-__device__ inline unsigned long long v_bits(double v) { return v != v ? kNanBits : (unsigned long long)__double_as_longlong(v); }
 
 __global__ void __launch_bounds__(kStepBlock) towr_proj_step_kernel(StepArgs a) {
 #pragma clang fp contract(off)

@@ -1,6 +1,9 @@
-// towr_gpu.hip — the C-ABI (include/towr_gpu.h) and host side of the eval_g / eval_jac_g engine: handle,
-// device tables, launch sequencing, host-pointer entry points. The kernels live in tiles.hip,
-// gstream.hip and cost_traj.hip.
+// towr_gpu.hip — the evaluator's part of the C-ABI (include/towr_gpu.h) and the host side of the eval_g /
+// eval_jac_g / objective engine: handle creation and destruction, device tables, launch sequencing, host-pointer
+// and batch evaluation entry points, trajectory export. The kernels live in tiles.hip, gstream.hip and
+// cost_traj.hip. The handle itself and the host helpers defined here that other translation units use (namespace
+// tg::host) are declared in handle.h; the batched solver-step entry points built on them (Jacobian products,
+// residuals, steps, L-BFGS) live in auglag.hip.
 //
 // One fused launch evaluates, for a batch of B problems sharing one layout, every constraint value
 // g and every Jacobian nonzero of ifopt's RowMajor CSR (what IpoptAdapter::eval_g / eval_jac_g
@@ -27,181 +30,16 @@
 #include <vector>
 
 #include "engine_math.h"
+#include "handle.h"
 #include "kernel_common.h"
 #include "layout.h"
 
 using namespace tg;
-
-
-// =================================================================================================
-// handle
-// =================================================================================================
-struct towr_gpu_handle_s {
-  Layout L;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  // device tables
-  ItemDesc* d_items = nullptr;
-  SlotGroup* d_slots = nullptr;
-  TileDesc* d_tiles = nullptr;
-  int32_t* d_nodecol = nullptr;
-  SplineMeta* d_spl = nullptr;
-  double* d_dur = nullptr;
-  void* d_segs = nullptr;      // SegSoA storage
-  SegSoA sg{};
-  PolyPhase* d_pinfo = nullptr;
-  PhaseCol* d_pcols = nullptr;
-  int32_t* d_pact = nullptr;
-  SchedInfo* d_sched = nullptr;
-  int32_t* d_misc = nullptr;
-  int32_t* d_misc_lds = nullptr;
-  MiscWave* d_misc_wave = nullptr;
-  ItemDesc* d_misc_items = nullptr;
-  int32_t* d_xspan = nullptr;
-  EELinDef* d_eelin = nullptr;
-  LinNz* d_lin = nullptr;
-  uint4* d_gtab = nullptr;     // GAIT: PhaseSpline tables blob (GaitTables)
-  ItemDirect* d_idir = nullptr;
-  CostItem* d_citems = nullptr;
-  double* d_cq = nullptr;
-  FsBlock* d_fsb = nullptr;    // streaming ForceConstraintDiscretized tables (layout.h FsBlock)
-  double* d_fs_t = nullptr;
-  int32_t* d_fs_tmpl = nullptr;
-  int32_t* d_fs_ws = nullptr;
-  int32_t* d_fs_iee = nullptr;
-  int32_t* d_fs_irow = nullptr;
-  int32_t* d_fs_iblk = nullptr;
-  double* d_fsrec = nullptr;   // per-problem instant records of the streaming path (scratch, grown on demand)
-  int64_t fsrec_cap = 0;       // problems it holds
-  GsGeo* d_gs_geo = nullptr;   // streaming RangeOfMotion / Dynamic tables (layout.h GsGeo)
-  int32_t* d_gs_tmpl = nullptr;
-  uint8_t* d_gs_pcode = nullptr;
-  GsSeg* d_gs_segs = nullptr;
-  uint8_t* d_gs_tseg = nullptr;
-  uint32_t* d_gs_vmap = nullptr;
-  int16_t* d_gs_ws = nullptr;
-  uint4* d_gs_blob = nullptr;
-  GsBlock* d_gs_blk[GS_COUNT] = {};
-  GsInst* d_gs_inst[GS_COUNT] = {};
-  double* d_rvc = nullptr;     // fixed gait, RotVec: the Dynamic base-angular coefficients of the pre-pass (scratch)
-  int64_t rvc_cap = 0;
-  RvInst* d_rvi = nullptr;
-  double* d_gsrec = nullptr;   // their records, both classes (scratch, grown on demand)
-  int64_t gsrec_cap = 0;
-  // The scratch above (and the soft child's g / values, d_sg / d_sv) is shared by every call on the
-  // handle: a call on another stream than the previous one waits for the previous call's work (this
-  // event), and growing a buffer waits for it on the host before the old one is freed.
-  hipEvent_t scr_ev = nullptr;
-  hipStream_t scr_stream = nullptr;
-  bool scr_used = false;
-  bool sync_call = false;   // host_eval: the call synchronises its stream before returning (no event needed)
-  // towr_gpu_eval_g_keep_jac: the Jacobian of kept_x waits in the device staging d_v (kept: until any other
-  // host-pointer evaluation reuses the staging)
-  bool kept = false;
-  std::vector<double> kept_x;
-  // fusion groups (TOWR_GPU_FUSE, see towr_step_kernel): classes that run in one launch
-  struct FuseGroup {
-    uint32_t mask = 0;        // bit lc: launch class lc belongs to the group
-    int kblock = 0;
-    UnitDesc* d_units = nullptr;
-    int32_t n_units = 0;
-    size_t lds = 0;
-  };
-  static constexpr int kMaxFuse = 2;
-  FuseGroup fuse[kMaxFuse];
-  int n_fuse = 0;
-  // one problem through host pointers (eval_g / eval_jac_values / eval_g_jac): every class in ONE
-  // launch (the fused kernel over all units), so the per-call latency is one kernel, not three
-  FuseGroup single;
-  // host entry points: caller memory page-locked by towr_gpu_register_host (DMA straight to / from
-  // it), the copy stream of the chunked host batch and its per-chunk events
-  struct Pinned { const char* p; size_t n; char* dev; };   // host range and its device address
-  std::vector<Pinned> pinned;
-  double *hd_x = nullptr, *hd_g = nullptr, *hd_v = nullptr;   // device addresses of the pinned staging
-  hipStream_t copy_stream = nullptr;
-  std::vector<hipEvent_t> ev_c, ev_d;
-  std::string fuse_name[kMaxFuse];   // towr_gpu_kernel_info
-  // fork-join of the per-kind launches (TOWR_GPU_STREAMS = total streams incl. the caller's, 1..4)
-  static constexpr int kMaxSide = 3;
-  int n_side = 0;
-  hipStream_t side[kMaxSide] = {};
-  hipEvent_t fork = nullptr, join[kMaxSide] = {};
-  bool rv_overlap = false;   // RotVec without fusion groups: Dynamic and the small kinds on side stream 0 (launch_classes)
-  towr_terrain_t* d_terrain = nullptr;      // base terrain (1 entry)
-  towr_terrain_t* d_bterrain = nullptr;     // per-problem batch terrains
-  int32_t bterrain_n = 0;
-  std::vector<towr_terrain_t> bterrain_h;   // their host copy (the frozen-pattern check)
-  // staging for host-pointer entry points
-  double *d_x = nullptr, *d_g = nullptr, *d_v = nullptr;
-  double *h_x = nullptr, *h_g = nullptr, *h_v = nullptr;
-  int32_t stage_B = 0;
-  double *d_f = nullptr, *d_grad = nullptr;   // host-pointer objective entry points (one problem)
-  // trajectory export: fixed phase table and the sample times of the last dt
-  double* d_traj_pd = nullptr;
-  int32_t* d_traj_n = nullptr;
-  int32_t* d_traj_c0 = nullptr;
-  double* d_traj_t = nullptr;
-  double traj_dt = 0.0;
-  int32_t traj_ns = 0;
-  // SoftConstraint terms: a second handle over the wrapped sets (soft_desc), its CSR pattern, the
-  // bounds' mid-points b (rows in its order) and its per-batch g / values scratch
-  towr_gpu_handle_s* soft = nullptr;
-  std::vector<double> soft_b;
-  double* d_soft_b = nullptr;
-  int32_t* d_soft_cptr = nullptr;   // the soft pattern by column (KParams::s_cptr / s_cent)
-  int2* d_soft_cent = nullptr;
-  uint16_t* d_c_cptr = nullptr;     // the cost gradient's slot lists (Layout::cost_cptr / cost_cslot)
-  uint16_t* d_c_cslot = nullptr;
-  int cost_grid[3] = {1, 1, 1};     // the cost kernel's persistent grid per accumulation (launch_cost)
-  double *d_sg = nullptr, *d_sv = nullptr;
-  int64_t soft_cap_g = 0, soft_cap_v = 0;   // problems the scratch holds
-  // Jacobian products (jprod.hip): the tables' device copies, uploaded by the first product call on the handle
-  // (products_ready), and the fused entry's own values scratch (a chunk of problems; never d_v, so the kept
-  // Jacobian survives); products_chunk: towr_gpu_set_products_chunk (0 = automatic)
-  bool jp_ready = false;
-  JpArgs jp{};
-  void* d_jp[8] = {};
-  double* d_pv = nullptr;
-  int64_t pv_cap = 0;
-  int32_t products_chunk = 0;
-  // Residuals (resid.hip): the device copies of the constraint sets' row ranges and of the description bounds,
-  // uploaded by the first residual call on the handle, and the fused entry's g / lam+ scratch (a chunk of problems)
-  bool res_ready = false;
-  int32_t* d_set_row0 = nullptr;
-  double *d_blo = nullptr, *d_bup = nullptr;
-  double *d_rg = nullptr, *d_rl = nullptr;
-  int64_t rg_cap = 0, rl_cap = 0;
-  // Steps (step.hip): the device copies of the variable sets' column ranges and of the description's variable
-  // bounds, uploaded by the first step call on the handle, and the fused entry's gradient / f scratch (the batch)
-  bool step_ready = false;
-  int32_t* d_set_col0 = nullptr;
-  double *d_xlo = nullptr, *d_xup = nullptr;
-  double *d_sd = nullptr, *d_sf = nullptr;
-  int64_t sd_cap = 0, sf_cap = 0;
-};
+using namespace tg::host;
 
 namespace {
 std::mutex g_err_mu;
 std::string g_last_error;
-
-int fail(towr_gpu_handle h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  std::lock_guard<std::mutex> lk(g_err_mu);
-  g_last_error = msg;
-  return code;
-}
-
-#define HIPCHK(h, expr)                                                                         \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return fail((h), TOWR_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
-// Every kernel launch of the engine. With TOWR_GPU_LAUNCH_LOG set (read once), the first launch of each (kernel, block,
-// dynamic LDS) is written to stderr as "towr-launch <symbol> block <threads> lds <bytes> grid <blocks>": the dynamic
-// LDS is a host-side choice the code object does not record, so tools/kernel_resources.py joins these lines with the
-// code objects' register / scratch metadata into profiles/kernel_resources.txt (occupancy per launch).
 #ifdef TOWR_STAMPS
 // experiment build (tools/stamps.py): launch i after towr_gpu_debug_stamps(buf) stores its TG_STAMP slots in region i
 // of buf (kStampRegion slots each, kStampRegions regions); the kernel of each region is kept for the tool
@@ -212,7 +50,23 @@ int g_stamp_n = 0;
 const void* g_stamp_fn[kStampRegions];
 #endif
 bool launch_log_on() { static const bool log = std::getenv("TOWR_GPU_LAUNCH_LOG") != nullptr; return log; }
-hipError_t launch_kernel(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s) {
+}  // namespace
+
+// =================================================================================================
+// the helpers declared in handle.h (launch, launch_cost and batch_terrain: further down)
+// =================================================================================================
+int tg::host::fail(towr_gpu_handle h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  std::lock_guard<std::mutex> lk(g_err_mu);
+  g_last_error = msg;
+  return code;
+}
+
+// Every kernel launch of the engine. With TOWR_GPU_LAUNCH_LOG set (read once), the first launch of each (kernel, block,
+// dynamic LDS) is written to stderr as "towr-launch <symbol> block <threads> lds <bytes> grid <blocks>": the dynamic
+// LDS is a host-side choice the code object does not record, so tools/kernel_resources.py joins these lines with the
+// code objects' register / scratch metadata into profiles/kernel_resources.txt (occupancy per launch).
+hipError_t tg::host::launch_kernel(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s) {
 #ifdef TOWR_STAMPS
   if (g_stamps && g_stamp_n < kStampRegions && (size_t)grid.x * 64 <= kStampRegion) {
     static_cast<KParams*>(args[0])->stamps = g_stamps + kStampRegion * g_stamp_n;   // every kernel's first argument
@@ -233,14 +87,40 @@ hipError_t launch_kernel(const void* fn, dim3 grid, dim3 block, void** args, siz
   return hipLaunchKernel(fn, grid, block, args, lds, s);
 }
 
-template <class T>
-int upload(towr_gpu_handle h, T** dst, const std::vector<T>& src) {
-  const size_t bytes = sizeof(T) * (src.empty() ? 1 : src.size());
-  HIPCHK(h, hipMalloc(reinterpret_cast<void**>(dst), bytes));
-  if (!src.empty()) HIPCHK(h, hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+int tg::host::bind(towr_gpu_handle h) {
+  if (h->device < 0) return fail(h, TOWR_ERR_NO_DEVICE, "layout-only handle (created with device < 0) cannot evaluate");
+  if (hipSetDevice(h->device) != hipSuccess) return fail(h, TOWR_ERR_HIP, "hipSetDevice failed");
   return TOWR_OK;
 }
 
+int tg::host::scratch_acquire(towr_gpu_handle h, hipStream_t s) {
+  if (h->scr_used && h->scr_stream != s) HIPCHK(h, hipStreamWaitEvent(s, h->scr_ev, 0));
+  return TOWR_OK;
+}
+int tg::host::scratch_release(towr_gpu_handle h, hipStream_t s) {
+  if (h->sync_call) {   // synchronised before the entry point returns: no later call needs to wait for it
+    h->scr_used = false;
+    return TOWR_OK;
+  }
+  HIPCHK(h, hipEventRecord(h->scr_ev, s));
+  h->scr_stream = s;
+  h->scr_used = true;
+  return TOWR_OK;
+}
+int tg::host::scratch_grow(towr_gpu_handle h, double** buf, int64_t* cap, int64_t problems, int64_t doubles_per_problem) {
+  if (*cap >= problems) return TOWR_OK;
+  if (*buf) {
+    if (h->scr_used) HIPCHK(h, hipEventSynchronize(h->scr_ev));
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+  }
+  HIPCHK(h, hipMalloc(buf, sizeof(double) * (size_t)problems * (size_t)std::max<int64_t>(1, doubles_per_problem)));
+  *cap = problems;
+  return TOWR_OK;
+}
+
+namespace {
 // a copy padded to whole 16-byte units (k elements), for a kernel that stages it with 16-byte loads
 template <class T>
 std::vector<T> padded(const std::vector<T>& v, size_t k) {
@@ -254,42 +134,6 @@ std::vector<uint16_t> cost_slot_table(const Layout& L) {
   std::vector<uint16_t> t(L.cost_cslot);
   t.resize(std::max(t.size(), (size_t)L.cost_nslot), 0);
   return padded(t, 8);
-}
-
-// every evaluation entry point: refuse layout-only handles, make the handle's device current
-int bind(towr_gpu_handle h) {
-  if (h->device < 0) return fail(h, TOWR_ERR_NO_DEVICE, "layout-only handle (created with device < 0) cannot evaluate");
-  if (hipSetDevice(h->device) != hipSuccess) return fail(h, TOWR_ERR_HIP, "hipSetDevice failed");
-  return TOWR_OK;
-}
-
-// Handle scratch ordering (see towr_gpu_handle_s::scr_ev): acquire before a call's first use on stream s,
-// release after its last; grow() reallocates a per-problem buffer once every earlier use has finished.
-int scratch_acquire(towr_gpu_handle h, hipStream_t s) {
-  if (h->scr_used && h->scr_stream != s) HIPCHK(h, hipStreamWaitEvent(s, h->scr_ev, 0));
-  return TOWR_OK;
-}
-int scratch_release(towr_gpu_handle h, hipStream_t s) {
-  if (h->sync_call) {   // synchronised before the entry point returns: no later call needs to wait for it
-    h->scr_used = false;
-    return TOWR_OK;
-  }
-  HIPCHK(h, hipEventRecord(h->scr_ev, s));
-  h->scr_stream = s;
-  h->scr_used = true;
-  return TOWR_OK;
-}
-int scratch_grow(towr_gpu_handle h, double** buf, int64_t* cap, int64_t problems, int64_t doubles_per_problem) {
-  if (*cap >= problems) return TOWR_OK;
-  if (*buf) {
-    if (h->scr_used) HIPCHK(h, hipEventSynchronize(h->scr_ev));
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-  }
-  HIPCHK(h, hipMalloc(buf, sizeof(double) * (size_t)problems * (size_t)std::max<int64_t>(1, doubles_per_problem)));
-  *cap = problems;
-  return TOWR_OK;
 }
 
 // The PhaseSpline tables a tile block stages in LDS under phase-duration optimisation, as one blob of
@@ -519,7 +363,6 @@ size_t gs_rec_lds(const Layout& L) {
 // a Dynamic part also its states and scratch (gs_rec_lds). A launch with the FDISC part and no RangeOfMotion /
 // Dynamic part stages the FDISC tables (FsBlock, window, template) after that region when they fit in 160 kB
 // (*fs_lds: their byte offset), else its lanes read them in global memory (*fs_lds = 0).
-constexpr size_t kLdsMax = 160 * 1024;
 size_t rec_launch_lds(const Layout& L, bool dyn, bool fdisc_only, int32_t* fs_lds) {
   const size_t base = dyn ? gs_rec_lds(L) : fs_inst_lds_bytes(L);
   if (fs_lds) *fs_lds = 0;
@@ -713,8 +556,9 @@ bool uses_scratch(const Layout& L) { return gait_streamed(L) || !L.rv_inst.empty
 
 int launch_classes(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* G, int64_t ldg, double* V, int64_t ldv,
                    int want_g, int want_jac, hipStream_t s, const towr_terrain_t* terrains, int per_problem, int only_class);
-int launch(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* G, int64_t ldg, double* V, int64_t ldv,
-           int want_g, int want_jac, hipStream_t s, const towr_terrain_t* terrains, int per_problem, int only_class) {
+}  // namespace
+int tg::host::launch(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* G, int64_t ldg, double* V, int64_t ldv,
+                     int want_g, int want_jac, hipStream_t s, const towr_terrain_t* terrains, int per_problem, int only_class) {
   if (B <= 0) return TOWR_OK;
   const bool scr = uses_scratch(h->L);
   if (scr)
@@ -729,6 +573,7 @@ int launch(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* G, in
   }
   return scr ? scratch_release(h, s) : TOWR_OK;
 }
+namespace {
 
 int launch_classes(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* G, int64_t ldg, double* V, int64_t ldv,
                    int want_g, int want_jac, hipStream_t s, const towr_terrain_t* terrains, int per_problem, int only_class) {
@@ -839,9 +684,6 @@ size_t cost_red_off(const Layout& L, int acc) {   // ... after x and the node ta
 }
 size_t cost_lds_bytes(const Layout& L, int acc) { return sizeof(double) * (cost_red_off(L, acc) + kCostBlock / 64 + 2); }
 
-int launch(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* G, int64_t ldg, double* V, int64_t ldv,
-           int want_g, int want_jac, hipStream_t s, const towr_terrain_t* terrains, int per_problem, int only_class);
-
 // SoftConstraint terms: the soft child evaluates the wrapped sets' g (and, for the gradient, their
 // Jacobian values) of the batch into the handle's scratch, on the same stream, before the cost launch
 int launch_soft(towr_gpu_handle h, int B, const double* X, int64_t ldx, bool grad, hipStream_t s,
@@ -858,8 +700,9 @@ int launch_soft(towr_gpu_handle h, int B, const double* X, int64_t ldx, bool gra
   return TOWR_OK;
 }
 
-int launch_cost(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* F, double* GR, int64_t ldgr,
-                hipStream_t s, const towr_terrain_t* terrains, int per_problem) {
+}  // namespace
+int tg::host::launch_cost(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* F, double* GR, int64_t ldgr,
+                          hipStream_t s, const towr_terrain_t* terrains, int per_problem) {
   if (B <= 0) return TOWR_OK;
   const Layout& L = h->L;
   KParams P{};
@@ -886,6 +729,7 @@ int launch_cost(towr_gpu_handle h, int B, const double* X, int64_t ldx, double* 
                             dim3(kCostBlock), args, cost_lds_bytes(L, acc), s));
   return h->soft ? scratch_release(h, s) : TOWR_OK;
 }
+namespace {
 
 // SaveTrajectoryToCSV's sample times: t = 0, dt, ... accumulated while t <= T + 1e-9, with
 // T = base_linear_->GetTotalTime() (save_data.cpp:14, 55-58)
@@ -955,10 +799,8 @@ int ensure_stage(towr_gpu_handle h, int B) {
   return TOWR_OK;
 }
 
-// Terrain of a batch launch: the per-problem set (towr_gpu_set_batch_terrain) when one is set, which
-// must then hold exactly B entries; else the description's terrain for every problem. `single`
-// entry points (one problem through host pointers) always use the description's terrain.
-int batch_terrain(towr_gpu_handle h, int B, bool single, const towr_terrain_t** ter, int* per) {
+}  // namespace
+int tg::host::batch_terrain(towr_gpu_handle h, int B, bool single, const towr_terrain_t** ter, int* per) {
   *ter = h->d_terrain; *per = 0;
   if (single || !h->d_bterrain) return TOWR_OK;
   if (h->bterrain_n != B)
@@ -967,6 +809,7 @@ int batch_terrain(towr_gpu_handle h, int B, bool single, const towr_terrain_t** 
   *ter = h->d_bterrain; *per = 1;
   return TOWR_OK;
 }
+namespace {
 
 // [p, p + bytes) inside caller memory registered with towr_gpu_register_host
 bool is_registered(towr_gpu_handle h, const void* p, size_t bytes) {
@@ -1443,12 +1286,7 @@ int towr_gpu_destroy(towr_gpu_handle h) {
                  h->single.d_units, h->d_gs_geo, h->d_gs_tmpl, h->d_gs_pcode, h->d_gs_blk[0], h->d_gs_blk[1], h->d_gs_blk[2],
                  h->d_gs_inst[0], h->d_gs_inst[1], h->d_gs_inst[2], h->d_gsrec, h->d_rvc, h->d_rvi, h->d_gs_segs, h->d_gs_tseg, h->d_gs_vmap, h->d_gs_ws, h->d_gs_blob};
   if (h->device >= 0) for (void* p : dev) if (p) (void)hipFree(p);
-  if (h->device >= 0) {
-    for (void* p : h->d_jp) if (p) (void)hipFree(p);
-    if (h->d_pv) (void)hipFree(h->d_pv);
-    void* res[] = {h->d_set_row0, h->d_blo, h->d_bup, h->d_rg, h->d_rl, h->d_set_col0, h->d_xlo, h->d_xup, h->d_sd, h->d_sf};
-    for (void* p : res) if (p) (void)hipFree(p);
-  }
+  if (h->device >= 0) h->al.release();
   void* host[] = {h->h_x, h->h_g, h->h_v};
   for (void* p : host) if (p) (void)hipHostFree(p);
   for (const auto& r : h->pinned) (void)hipHostUnregister(const_cast<char*>(r.p));
@@ -1757,484 +1595,6 @@ int towr_gpu_eval_batch_device(towr_gpu_handle h, int32_t B, const double* X, in
   if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);   // NULL = HIP's default stream
   return launch(h, B, X, ldx, G, ldg, V, ldv, want_g, want_jac, s, ter, per, -1);
-}
-
-// ---- Jacobian products (jprod.hip) ----------------------------------------------------------------------------
-int towr_gpu_jac_csc(towr_gpu_handle h, int64_t* col_ptr, int32_t* row, int32_t* csr_index) {
-  if (!h || !col_ptr || !row || !csr_index) return fail(h, TOWR_ERR_INVALID, "null argument");
-  const Layout& L = h->L;
-  std::memcpy(col_ptr, L.col_ptr.data(), sizeof(int64_t) * L.col_ptr.size());
-  if (L.nnz) {
-    std::memcpy(row, L.csc_row.data(), sizeof(int32_t) * L.csc_row.size());
-    std::memcpy(csr_index, L.csc_index.data(), sizeof(int32_t) * L.csc_index.size());
-  }
-  return TOWR_OK;
-}
-
-// The product tables' device copies, on the first product call of the handle (towr_gpu_create and the single-problem
-// callbacks never pay for them). Synchronous copies: that first call is not asynchronous.
-static int products_ready(towr_gpu_handle h) {
-  if (h->jp_ready) return TOWR_OK;
-  const Layout& L = h->L;
-  const size_t lv = jp_vec_lds(L.n, L.m), lt = jp_tvec_lds(L.n, L.m);
-  if (std::max(lv, lt) > kLdsMax) return fail(h, TOWR_ERR_UNSUPPORTED, "problem too large for the product kernels' LDS");
-  if ((lv > 64 * 1024 && hipFuncSetAttribute(jp_vec_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lv) != hipSuccess) ||
-      (lt > 64 * 1024 && hipFuncSetAttribute(jp_tvec_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lt) != hipSuccess))
-    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-  const std::vector<int32_t> cp32(L.col_ptr.begin(), L.col_ptr.end());
-  int32_t *col = nullptr, *row = nullptr, *er = nullptr, *cp = nullptr;
-  uint16_t* cidx = nullptr;
-  JpSeg *rs = nullptr, *cs = nullptr;
-  JpChunk* ch = nullptr;
-  int r = 0;
-  (void)((r = upload(h, &col, L.col)) || (r = upload(h, &row, L.jp_row)) || (r = upload(h, &cidx, L.jp_cidx)) ||
-         (r = upload(h, &rs, L.jp_rseg)) || (r = upload(h, &cs, L.jp_cseg)) || (r = upload(h, &ch, L.jp_chunks)) ||
-         (r = upload(h, &er, L.jp_empty_rows)) || (r = upload(h, &cp, cp32)));
-  void* all[8] = {col, row, cidx, rs, cs, ch, er, cp};
-  if (r) {
-    for (void* p : all) if (p) (void)hipFree(p);
-    return r;
-  }
-  std::copy(all, all + 8, h->d_jp);
-  JpArgs& a = h->jp;
-  a.col = col; a.row = row; a.cidx = cidx; a.rseg = rs; a.cseg = cs; a.chunks = ch; a.empty_rows = er; a.col_ptr = cp;
-  a.nnz = L.nnz; a.n = L.n; a.m = L.m;
-  a.n_chunks = (int32_t)L.jp_chunks.size(); a.n_empty = (int32_t)L.jp_empty_rows.size();
-  h->jp_ready = true;
-  return TOWR_OK;
-}
-
-// one product launch over B problems: Y = J p (tvec = false) or Z (+)= J^T lam
-static int launch_product(towr_gpu_handle h, bool tvec, int B, const double* V, int64_t ldv, const double* vec, int64_t ldvec,
-                          double* out, int64_t ldo, int accumulate, hipStream_t s) {
-  JpArgs a = h->jp;
-  a.V = V; a.ldv = ldv; a.Vec = vec; a.ldvec = ldvec; a.Out = out; a.ldo = ldo; a.accumulate = accumulate;
-  void* args[] = {&a};
-  const size_t lds = tvec ? jp_tvec_lds(a.n, a.m) : jp_vec_lds(a.n, a.m);
-  HIPCHK(h, launch_kernel(tvec ? jp_tvec_kernel() : jp_vec_kernel(), dim3((unsigned)B), dim3(kJpBlock), args, lds, s));
-  return TOWR_OK;
-}
-
-int towr_gpu_jac_vec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv, const double* P, int64_t ldp,
-                                  double* Y, int64_t ldy, void* stream) {
-  if (!h || B < 0 || !V || !P || !Y) return fail(h, TOWR_ERR_INVALID, "bad argument (null pointer or B < 0)");
-  const Layout& L = h->L;
-  if (ldv < L.nnz || ldp < L.n || ldy < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / n (P) / m (Y)");
-  if (int rc = bind(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  if (int rc = products_ready(h)) return rc;
-  return launch_product(h, false, B, V, ldv, P, ldp, Y, ldy, 0, reinterpret_cast<hipStream_t>(stream));
-}
-
-int towr_gpu_jac_tvec_batch_device(towr_gpu_handle h, int32_t B, const double* V, int64_t ldv, const double* LAM, int64_t ldl,
-                                   double* Z, int64_t ldz, int32_t accumulate, void* stream) {
-  if (!h || B < 0 || !V || !LAM || !Z) return fail(h, TOWR_ERR_INVALID, "bad argument (null pointer or B < 0)");
-  const Layout& L = h->L;
-  if (ldv < L.nnz || ldl < L.m || ldz < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAM) / n (Z)");
-  if (int rc = bind(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  if (int rc = products_ready(h)) return rc;
-  return launch_product(h, true, B, V, ldv, LAM, ldl, Z, ldz, accumulate != 0, reinterpret_cast<hipStream_t>(stream));
-}
-
-int towr_gpu_set_products_chunk(towr_gpu_handle h, int32_t problems) {
-  if (!h || problems < 0) return fail(h, TOWR_ERR_INVALID, "bad argument");
-  h->products_chunk = problems;
-  return TOWR_OK;
-}
-
-// The values of `chunk` problems at a time in the handle's own scratch (d_pv, ordered across streams like the other
-// scratch: scratch_acquire / scratch_release), each chunk evaluated by the batch launch sequence and consumed by the
-// product kernels behind it on the caller's stream.
-int towr_gpu_eval_products_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, double* G, int64_t ldg,
-                                        const double* LAM, int64_t ldl, double* Z, int64_t ldz, int32_t accumulate,
-                                        const double* P, int64_t ldp, double* Y, int64_t ldy, void* stream) {
-  if (!h || B < 0 || !X) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or B < 0)");
-  const Layout& L = h->L;
-  if ((Z && !LAM) || (Y && !P)) return fail(h, TOWR_ERR_INVALID, "Z given without LAM, or Y without P");
-  if ((LAM && !Z) || (P && !Y)) return fail(h, TOWR_ERR_INVALID, "LAM given without Z, or P without Y");
-  if (ldx < L.n || (G && ldg < L.m) || (LAM && (ldl < L.m || ldz < L.n)) || (P && (ldp < L.n || ldy < L.m)))
-    return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X, P, Z) / m (G, LAM, Y)");
-  if (int rc = bind(h)) return rc;
-  const towr_terrain_t* ter;
-  int per;
-  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
-  if (B == 0) return TOWR_OK;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool want_v = LAM || P;
-  if (!want_v) return G ? launch(h, B, X, ldx, G, ldg, nullptr, 0, 1, 0, s, ter, per, -1) : TOWR_OK;
-  if (int rc = products_ready(h)) return rc;
-  // Automatic chunk: measured, a chunk sized to the Infinity Cache (128 MiB of values) gains nothing — the
-  // fused call at chunk = B costs what the three separate calls cost — and every further chunk costs its launch
-  // sequence and an underfilled chip (ANYmal gait, B = 1024: 18.8 ms in 15 chunks vs 2.6 ms in one). So the chunk is
-  // as large as a 2 GiB scratch allows (the footprint bound), cut into equal parts.
-  constexpr int64_t kAutoBytes = int64_t(2) << 30;
-  const int64_t ldv = std::max<int64_t>(16, (L.nnz + 15) & ~int64_t(15));   // rows on 128-byte boundaries
-  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ldv));
-  const int64_t parts = (B + cap - 1) / cap;
-  const int C = (int)std::min<int64_t>(B, h->products_chunk > 0 ? h->products_chunk : (B + parts - 1) / parts);
-  if (int rc = scratch_acquire(h, s)) return rc;
-  int rc = scratch_grow(h, &h->d_pv, &h->pv_cap, C, ldv);
-  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
-    const int cb = std::min(C, B - c0);
-    rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, G ? G + (int64_t)c0 * ldg : nullptr, ldg, h->d_pv, ldv, G != nullptr, 1, s,
-                per ? ter + c0 : ter, per, -1);
-    if (rc == TOWR_OK && LAM)
-      rc = launch_product(h, true, cb, h->d_pv, ldv, LAM + (int64_t)c0 * ldl, ldl, Z + (int64_t)c0 * ldz, ldz, accumulate != 0, s);
-    if (rc == TOWR_OK && P) rc = launch_product(h, false, cb, h->d_pv, ldv, P + (int64_t)c0 * ldp, ldp, Y + (int64_t)c0 * ldy, ldy, 0, s);
-  }
-  const int rr = scratch_release(h, s);   // (also after a failure: what was queued still orders the scratch)
-  return rc ? rc : rr;
-}
-
-// ---- residuals (resid.hip) ---------------------------------------------------------------------------------------
-// The residual kernel's tables, on the first residual call of the handle (synchronous copies, as products_ready): the
-// sets' row ranges and, when every set's bounds are known, the description bounds.
-static int residual_ready(towr_gpu_handle h) {
-  if (h->res_ready) return TOWR_OK;
-  const Layout& L = h->L;
-  std::vector<int32_t> row0;
-  for (const ConsInfo& c : L.cons) row0.push_back(c.row0);
-  row0.push_back(L.m);
-  int32_t* d_row0 = nullptr;
-  double *lo = nullptr, *up = nullptr;
-  int r = upload(h, &d_row0, row0);
-  if (!r && L.bounds_err.empty()) (void)((r = upload(h, &lo, L.g_lower)) || (r = upload(h, &up, L.g_upper)));
-  if (r) {
-    void* all[] = {d_row0, lo, up};
-    for (void* p : all) if (p) (void)hipFree(p);
-    return r;
-  }
-  h->d_set_row0 = d_row0; h->d_blo = lo; h->d_bup = up;
-  h->res_ready = true;
-  return TOWR_OK;
-}
-
-// the argument checks the residual entry and the fused entry share (before anything runs)
-static int residual_args(towr_gpu_handle h, const double* GL, const double* GU, int64_t ldb, const double* LAM, int64_t ldl,
-                         double rho, bool lamp, int64_t ldlp, const double* SUM, int64_t lds) {
-  const Layout& L = h->L;
-  if (!SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
-  if (lds < 4 + (int64_t)L.cons.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 4 + n_constraints");
-  if ((GL == nullptr) != (GU == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of GL / GU given");
-  if (GL && ldb != 0 && ldb < L.m) return fail(h, TOWR_ERR_INVALID, "ldb must be 0 (shared bounds) or >= m");
-  if (!GL && !L.bounds_err.empty()) return fail(h, TOWR_ERR_INVALID, L.bounds_err);
-  if (lamp && !(rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 with LAMP");
-  if (lamp && ldlp < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAMP smaller than m");
-  if (lamp && LAM && ldl < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAM smaller than m");
-  return TOWR_OK;
-}
-
-static int launch_residual(towr_gpu_handle h, int B, const double* G, int64_t ldg, const double* GL, const double* GU, int64_t ldb,
-                           const double* LAM, int64_t ldl, double rho, double* LAMP, int64_t ldlp, double* SUM, int64_t lds,
-                           hipStream_t s) {
-  ResArgs a{};
-  a.G = G; a.ldg = ldg;
-  a.GL = GL ? GL : h->d_blo; a.GU = GL ? GU : h->d_bup; a.ldb = GL ? ldb : 0;
-  a.LAM = LAMP ? LAM : nullptr; a.ldl = ldl; a.LAMP = LAMP; a.ldlp = ldlp; a.SUM = SUM; a.lds = lds;
-  a.set_row0 = h->d_set_row0; a.rho = LAMP ? rho : 1.0; a.m = h->L.m; a.n_sets = (int32_t)h->L.cons.size();
-  void* args[] = {&a};
-  HIPCHK(h, launch_kernel(res_kernel(), dim3((unsigned)B), dim3(kResBlock), args, 0, s));
-  return TOWR_OK;
-}
-
-int towr_gpu_residual_batch_device(towr_gpu_handle h, int32_t B, const double* G, int64_t ldg, const double* GL, const double* GU,
-                                   int64_t ldb, const double* LAM, int64_t ldl, double rho, double* LAMP, int64_t ldlp,
-                                   double* SUM, int64_t lds, void* stream) {
-  if (!h || B < 0 || !G) return fail(h, TOWR_ERR_INVALID, "bad argument (null G or B < 0)");
-  if (ldg < h->L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of G smaller than m");
-  if (int rc = residual_args(h, GL, GU, ldb, LAM, ldl, rho, LAMP != nullptr, ldlp, SUM, lds)) return rc;
-  if (int rc = bind(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  if (int rc = residual_ready(h)) return rc;
-  return launch_residual(h, B, G, ldg, GL, GU, ldb, LAM, ldl, rho, LAMP, ldlp, SUM, lds, reinterpret_cast<hipStream_t>(stream));
-}
-
-// The chunks of towr_gpu_eval_auglag_batch_device, shared with towr_gpu_auglag_step_batch_device (the caller holds the
-// scratch: scratch_acquire / scratch_release)
-static int auglag_chunks(towr_gpu_handle h, int B, const double* X, int64_t ldx, const double* GL, const double* GU, int64_t ldb,
-                         const double* LAM, int64_t ldl, double rho, double* G, int64_t ldg, double* LAMP, int64_t ldlp,
-                         double* SUM, int64_t lds, double* Z, int64_t ldz, int32_t accumulate, hipStream_t s,
-                         const towr_terrain_t* ter, int per) {
-  const Layout& L = h->L;
-  constexpr int64_t kAutoBytes = int64_t(2) << 30;   // the automatic chunk of towr_gpu_eval_products_batch_device
-  const int64_t ldv = std::max<int64_t>(16, (L.nnz + 15) & ~int64_t(15));
-  const int64_t ldr = std::max<int64_t>(16, ((int64_t)L.m + 15) & ~int64_t(15));
-  const int64_t cap = std::max<int64_t>(1, kAutoBytes / (8 * ldv));
-  const int64_t parts = (B + cap - 1) / cap;
-  const int C = (int)std::min<int64_t>(B, h->products_chunk > 0 ? h->products_chunk : (B + parts - 1) / parts);
-  int rc = scratch_grow(h, &h->d_pv, &h->pv_cap, C, ldv);
-  if (rc == TOWR_OK && !G) rc = scratch_grow(h, &h->d_rg, &h->rg_cap, C, ldr);
-  if (rc == TOWR_OK && !LAMP) rc = scratch_grow(h, &h->d_rl, &h->rl_cap, C, ldr);
-  for (int c0 = 0; c0 < B && rc == TOWR_OK; c0 += C) {
-    const int cb = std::min(C, B - c0);
-    double* g = G ? G + (int64_t)c0 * ldg : h->d_rg;
-    const int64_t lg = G ? ldg : ldr;
-    double* lp = LAMP ? LAMP + (int64_t)c0 * ldlp : h->d_rl;
-    const int64_t llp = LAMP ? ldlp : ldr;
-    rc = launch(h, cb, X + (int64_t)c0 * ldx, ldx, g, lg, h->d_pv, ldv, 1, 1, s, per ? ter + c0 : ter, per, -1);
-    if (rc == TOWR_OK)
-      rc = launch_residual(h, cb, g, lg, GL ? GL + (int64_t)c0 * ldb : nullptr, GL ? GU + (int64_t)c0 * ldb : nullptr, ldb,
-                           LAM ? LAM + (int64_t)c0 * ldl : nullptr, ldl, rho, lp, llp, SUM + (int64_t)c0 * lds, lds, s);
-    if (rc == TOWR_OK) rc = launch_product(h, true, cb, h->d_pv, ldv, lp, llp, Z + (int64_t)c0 * ldz, ldz, accumulate != 0, s);
-  }
-  return rc;
-}
-
-// As towr_gpu_eval_products_batch_device: a chunk of problems at a time through the handle's scratch (the values in
-// d_pv; g and lam+ in d_rg / d_rl when the caller does not want them), the three launches of a chunk back to back on
-// the caller's stream.
-int towr_gpu_eval_auglag_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* GL, const double* GU,
-                                      int64_t ldb, const double* LAM, int64_t ldl, double rho, double* G, int64_t ldg,
-                                      double* LAMP, int64_t ldlp, double* SUM, int64_t lds, double* Z, int64_t ldz,
-                                      int32_t accumulate, void* stream) {
-  if (!h || B < 0 || !X || !Z) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or Z, or B < 0)");
-  const Layout& L = h->L;
-  if (ldx < L.n || ldz < L.n || (G && ldg < L.m)) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X, Z) / m (G)");
-  if (int rc = residual_args(h, GL, GU, ldb, LAM, ldl, rho, true, LAMP ? ldlp : L.m, SUM, lds)) return rc;
-  if (int rc = bind(h)) return rc;
-  const towr_terrain_t* ter;
-  int per;
-  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
-  if (B == 0) return TOWR_OK;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = products_ready(h)) return rc;
-  if (int rc = residual_ready(h)) return rc;
-  if (int rc = scratch_acquire(h, s)) return rc;
-  const int rc = auglag_chunks(h, B, X, ldx, GL, GU, ldb, LAM, ldl, rho, G, ldg, LAMP, ldlp, SUM, lds, Z, ldz, accumulate, s, ter, per);
-  const int rr = scratch_release(h, s);
-  return rc ? rc : rr;
-}
-
-// ---- steps (step.hip) ----------------------------------------------------------------------------------------------
-// The step kernel's tables, on the first step call of the handle (synchronous copies, as residual_ready): the variable
-// sets' column ranges and the description's variable bounds.
-static int step_ready(towr_gpu_handle h) {
-  if (h->step_ready) return TOWR_OK;
-  const Layout& L = h->L;
-  std::vector<int32_t> col0;
-  for (const VarSetInfo& v : L.varsets) col0.push_back(v.col0);
-  col0.push_back(L.n);
-  int32_t* d_col0 = nullptr;
-  double *lo = nullptr, *up = nullptr;
-  int r = 0;
-  (void)((r = upload(h, &d_col0, col0)) || (r = upload(h, &lo, L.x_lower)) || (r = upload(h, &up, L.x_upper)));
-  if (r) {
-    void* all[] = {d_col0, lo, up};
-    for (void* p : all) if (p) (void)hipFree(p);
-    return r;
-  }
-  h->d_set_col0 = d_col0; h->d_xlo = lo; h->d_xup = up;
-  h->step_ready = true;
-  return TOWR_OK;
-}
-
-// the argument checks the step entry and the fused entry share (before anything runs)
-static int step_args(towr_gpu_handle h, const double* ALPHA, double alpha, const double* XL, const double* XU, int64_t ldb,
-                     int64_t ldxp, bool xp, const double* SUM, int64_t lds) {
-  const Layout& L = h->L;
-  if (!SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
-  if (lds < 5 + (int64_t)L.varsets.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 5 + n_varsets");
-  if ((XL == nullptr) != (XU == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XL / XU given");
-  if (XL && ldb != 0 && ldb < L.n) return fail(h, TOWR_ERR_INVALID, "ldb must be 0 (shared bounds) or >= n");
-  if (!ALPHA && alpha != alpha) return fail(h, TOWR_ERR_INVALID, "alpha is NaN");
-  if (xp && ldxp < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of XP smaller than n");
-  return TOWR_OK;
-}
-
-static int launch_step(towr_gpu_handle h, int B, const double* X, int64_t ldx, const double* D, int64_t ldd, const double* ALPHA,
-                       double alpha, const double* XL, const double* XU, int64_t ldb, double* XP, int64_t ldxp, double* SUM,
-                       int64_t lds, hipStream_t s) {
-  StepArgs a{};
-  a.X = X; a.ldx = ldx; a.D = D; a.ldd = ldd; a.ALPHA = ALPHA; a.alpha = alpha;
-  a.XL = XL ? XL : h->d_xlo; a.XU = XL ? XU : h->d_xup; a.ldb = XL ? ldb : 0;
-  a.XP = XP; a.ldxp = ldxp; a.SUM = SUM; a.lds = lds;
-  a.set_col0 = h->d_set_col0; a.n = h->L.n; a.n_sets = (int32_t)h->L.varsets.size();
-  void* args[] = {&a};
-  HIPCHK(h, launch_kernel(step_kernel(), dim3((unsigned)B), dim3(kStepBlock), args, 0, s));
-  return TOWR_OK;
-}
-
-int towr_gpu_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* D, int64_t ldd,
-                               const double* ALPHA, double alpha, const double* XL, const double* XU, int64_t ldb,
-                               double* XP, int64_t ldxp, double* SUM, int64_t lds, void* stream) {
-  if (!h || B < 0 || !X || !D) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or D, or B < 0)");
-  if (ldx < h->L.n || ldd < h->L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X or D smaller than n");
-  if (int rc = step_args(h, ALPHA, alpha, XL, XU, ldb, ldxp, XP != nullptr, SUM, lds)) return rc;
-  if (int rc = bind(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  if (int rc = step_ready(h)) return rc;
-  return launch_step(h, B, X, ldx, D, ldd, ALPHA, alpha, XL, XU, ldb, XP, ldxp, SUM, lds, reinterpret_cast<hipStream_t>(stream));
-}
-
-// The gradient of the whole batch in handle scratch (d_sd: grad f from the cost launch, then + J^T lam+ per chunk of
-// the auglag sequence), the step kernel behind it: what the three public calls launch, on the caller's stream.
-int towr_gpu_auglag_step_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx, const double* GL, const double* GU,
-                                      int64_t ldgb, const double* LAM, int64_t ldl, double rho, const double* ALPHA, double alpha,
-                                      const double* XL, const double* XU, int64_t ldxb, double* F, double* G, int64_t ldg,
-                                      double* LAMP, int64_t ldlp, double* RSUM, int64_t ldrs, double* XP, int64_t ldxp,
-                                      double* SSUM, int64_t ldss, void* stream) {
-  if (!h || B < 0 || !X || !XP) return fail(h, TOWR_ERR_INVALID, "bad argument (null X or XP, or B < 0)");
-  const Layout& L = h->L;
-  if (ldx < L.n || (G && ldg < L.m)) return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than n (X) / m (G)");
-  if (int rc = residual_args(h, GL, GU, ldgb, LAM, ldl, rho, true, LAMP ? ldlp : L.m, RSUM, ldrs)) return rc;
-  if (int rc = step_args(h, ALPHA, alpha, XL, XU, ldxb, ldxp, true, SSUM, ldss)) return rc;
-  if (int rc = bind(h)) return rc;
-  const towr_terrain_t* ter;
-  int per;
-  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
-  if (B == 0) return TOWR_OK;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = products_ready(h)) return rc;
-  if (int rc = residual_ready(h)) return rc;
-  if (int rc = step_ready(h)) return rc;
-  const int64_t ldn = std::max<int64_t>(16, ((int64_t)L.n + 15) & ~int64_t(15));   // rows on 128-byte boundaries
-  if (int rc = scratch_acquire(h, s)) return rc;
-  int rc = scratch_grow(h, &h->d_sd, &h->sd_cap, B, ldn);
-  if (rc == TOWR_OK && !F) rc = scratch_grow(h, &h->d_sf, &h->sf_cap, B, 1);
-  if (rc == TOWR_OK) rc = launch_cost(h, B, X, ldx, F ? F : h->d_sf, h->d_sd, ldn, s, ter, per);
-  if (rc == TOWR_OK)
-    rc = auglag_chunks(h, B, X, ldx, GL, GU, ldgb, LAM, ldl, rho, G, ldg, LAMP, ldlp, RSUM, ldrs, h->d_sd, ldn, 1, s, ter, per);
-  if (rc == TOWR_OK) rc = launch_step(h, B, X, ldx, h->d_sd, ldn, ALPHA, alpha, XL, XU, ldxb, XP, ldxp, SSUM, ldss, s);
-  const int rr = scratch_release(h, s);
-  return rc ? rc : rr;
-}
-
-// ---- L-BFGS (lbfgs.hip) --------------------------------------------------------------------------------------------
-// the argument checks the L-BFGS entries and the fused entry share (before anything runs)
-static int lbfgs_args(towr_gpu_handle h, int32_t mem, const double* HS, const double* HY, int64_t ldh, const int32_t* HMETA,
-                      const double* SUM, int64_t lds, int64_t lds_min) {
-  if (!HS || !HY || !HMETA) return fail(h, TOWR_ERR_INVALID, "null HS, HY or HMETA");
-  if (!SUM) return fail(h, TOWR_ERR_INVALID, "null SUM");
-  if (mem < 1 || mem > TOWR_LBFGS_MAX_MEM) return fail(h, TOWR_ERR_INVALID, "mem outside 1..TOWR_LBFGS_MAX_MEM");
-  if (ldh < h->L.n) return fail(h, TOWR_ERR_INVALID, "ldh smaller than n");
-  if (lds < lds_min) return fail(h, TOWR_ERR_INVALID, lds_min == 6 ? "lds smaller than 6" : "lds smaller than 5");
-  return TOWR_OK;
-}
-static int lbfgs_update_args(towr_gpu_handle h, double curv_eps) {
-  if (!(curv_eps >= 0)) return fail(h, TOWR_ERR_INVALID, "curv_eps is negative or NaN");
-  return TOWR_OK;
-}
-static int lbfgs_bounds_args(towr_gpu_handle h, const double* XL, const double* XU, int64_t ldb) {
-  if ((XL == nullptr) != (XU == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XL / XU given");
-  if (XL && ldb != 0 && ldb < h->L.n) return fail(h, TOWR_ERR_INVALID, "ldb must be 0 (shared bounds) or >= n");
-  return TOWR_OK;
-}
-// the kernels' per-column state lives in LDS: the handle's n must fit (after bind: a layout-only handle has answered)
-static int lbfgs_fits(towr_gpu_handle h) {
-  if (std::max(lbfgs_update_lds(h->L.n), lbfgs_direction_lds(h->L.n)) > kLbfgsMaxLds)
-    return fail(h, TOWR_ERR_UNSUPPORTED, "n too large for the L-BFGS kernels' LDS");
-  return TOWR_OK;
-}
-
-static int launch_lbfgs_update(towr_gpu_handle h, int B, int mem, const double* X, int64_t ldx, const double* XN, int64_t ldxn,
-                               const double* GR, int64_t ldgr, const double* GRN, int64_t ldgrn, double curv_eps, double* HS,
-                               double* HY, int64_t ldh, int32_t* HMETA, double* SUM, int64_t lds, hipStream_t s) {
-  LbfgsUpdateArgs a{};
-  a.X = X; a.ldx = ldx; a.XN = XN; a.ldxn = ldxn; a.GR = GR; a.ldgr = ldgr; a.GRN = GRN; a.ldgrn = ldgrn;
-  a.HS = HS; a.HY = HY; a.ldh = ldh; a.HMETA = HMETA; a.SUM = SUM; a.lds = lds; a.curv_eps = curv_eps;
-  a.n = h->L.n; a.mem = mem;
-  void* args[] = {&a};
-  HIPCHK(h, launch_kernel(lbfgs_update_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_update_lds(a.n), s));
-  return TOWR_OK;
-}
-
-// (X != NULL with XL == NULL: the handle's bounds, after step_ready)
-static int launch_lbfgs_direction(towr_gpu_handle h, int B, int mem, const double* X, int64_t ldx, const double* GR, int64_t ldgr,
-                                  const double* XL, const double* XU, int64_t ldb, const double* HS, const double* HY,
-                                  int64_t ldh, const int32_t* HMETA, double* D, int64_t ldd, double* SUM, int64_t lds,
-                                  hipStream_t s) {
-  LbfgsDirArgs a{};
-  a.X = X; a.ldx = ldx; a.GR = GR; a.ldgr = ldgr;
-  a.XL = XL ? XL : h->d_xlo; a.XU = XL ? XU : h->d_xup; a.ldb = XL ? ldb : 0;
-  a.HS = HS; a.HY = HY; a.ldh = ldh; a.HMETA = HMETA; a.D = D; a.ldd = ldd; a.SUM = SUM; a.lds = lds;
-  a.n = h->L.n; a.mem = mem;
-  void* args[] = {&a};
-  HIPCHK(h, launch_kernel(lbfgs_direction_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_direction_lds(a.n), s));
-  return TOWR_OK;
-}
-
-int towr_gpu_lbfgs_update_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx, const double* XN,
-                                       int64_t ldxn, const double* GR, int64_t ldgr, const double* GRN, int64_t ldgrn,
-                                       double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA, double* SUM,
-                                       int64_t lds, void* stream) {
-  if (!h || B < 0 || !X || !XN || !GR || !GRN) return fail(h, TOWR_ERR_INVALID, "bad argument (null X, XN, GR or GRN, or B < 0)");
-  const int n = h->L.n;
-  if (ldx < n || ldxn < n || ldgr < n || ldgrn < n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X, XN, GR or GRN smaller than n");
-  if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, SUM, lds, 6)) return rc;
-  if (int rc = lbfgs_update_args(h, curv_eps)) return rc;
-  if (int rc = bind(h)) return rc;
-  if (int rc = lbfgs_fits(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  return launch_lbfgs_update(h, B, mem, X, ldx, XN, ldxn, GR, ldgr, GRN, ldgrn, curv_eps, HS, HY, ldh, HMETA, SUM, lds,
-                             reinterpret_cast<hipStream_t>(stream));
-}
-
-int towr_gpu_lbfgs_direction_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx, const double* GR,
-                                          int64_t ldgr, const double* XL, const double* XU, int64_t ldb, const double* HS,
-                                          const double* HY, int64_t ldh, const int32_t* HMETA, double* D, int64_t ldd, double* SUM,
-                                          int64_t lds, void* stream) {
-  if (!h || B < 0 || !GR || !D) return fail(h, TOWR_ERR_INVALID, "bad argument (null GR or D, or B < 0)");
-  const int n = h->L.n;
-  if ((X && ldx < n) || ldgr < n || ldd < n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X, GR or D smaller than n");
-  if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, SUM, lds, 5)) return rc;
-  if (int rc = lbfgs_bounds_args(h, XL, XU, ldb)) return rc;
-  if (int rc = bind(h)) return rc;
-  if (int rc = lbfgs_fits(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  if (X && !XL)
-    if (int rc = step_ready(h)) return rc;
-  return launch_lbfgs_direction(h, B, mem, X, ldx, GR, ldgr, XL, XU, ldb, HS, HY, ldh, HMETA, D, ldd, SUM, lds,
-                                reinterpret_cast<hipStream_t>(stream));
-}
-
-// The gradient of the augmented Lagrangian in the caller's GR (grad f from the cost launch, then + J^T lam+ per chunk of
-// the auglag sequence; g and lam+ in handle scratch), the history update with (XPREV -> X, GRPREV -> GR), the
-// direction in handle scratch (d_sd) and the step kernel behind it: what the five public calls launch, on the
-// caller's stream.
-int towr_gpu_auglag_lbfgs_step_batch_device(towr_gpu_handle h, int32_t B, int32_t mem, const double* X, int64_t ldx,
-                                            const double* XPREV, int64_t ldxprev, const double* GRPREV, int64_t ldgrprev,
-                                            const double* GL, const double* GU, int64_t ldgb, const double* LAM, int64_t ldl,
-                                            double rho, const double* ALPHA, double alpha, const double* XL, const double* XU,
-                                            int64_t ldxb, double curv_eps, double* HS, double* HY, int64_t ldh, int32_t* HMETA,
-                                            double* F, double* GR, int64_t ldgr, double* RSUM, int64_t ldrs, double* USUM,
-                                            int64_t ldus, double* DSUM, int64_t ldds, double* XP, int64_t ldxp, double* SSUM,
-                                            int64_t ldss, void* stream) {
-  if (!h || B < 0 || !X || !XP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null X, XP or GR, or B < 0)");
-  const Layout& L = h->L;
-  if (ldx < L.n || ldgr < L.n) return fail(h, TOWR_ERR_INVALID, "leading dimension of X or GR smaller than n");
-  if ((XPREV == nullptr) != (GRPREV == nullptr)) return fail(h, TOWR_ERR_INVALID, "only one of XPREV / GRPREV given");
-  if (XPREV && (ldxprev < L.n || ldgrprev < L.n)) return fail(h, TOWR_ERR_INVALID, "leading dimension of XPREV or GRPREV smaller than n");
-  if (int rc = residual_args(h, GL, GU, ldgb, LAM, ldl, rho, true, L.m, RSUM, ldrs)) return rc;
-  if (XPREV)
-    if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, USUM, ldus, 6)) return rc;
-  if (int rc = lbfgs_update_args(h, curv_eps)) return rc;
-  if (int rc = lbfgs_args(h, mem, HS, HY, ldh, HMETA, DSUM, ldds, 5)) return rc;
-  if (int rc = step_args(h, ALPHA, alpha, XL, XU, ldxb, ldxp, true, SSUM, ldss)) return rc;
-  if (int rc = bind(h)) return rc;
-  if (int rc = lbfgs_fits(h)) return rc;
-  const towr_terrain_t* ter;
-  int per;
-  if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
-  if (B == 0) return TOWR_OK;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = products_ready(h)) return rc;
-  if (int rc = residual_ready(h)) return rc;
-  if (int rc = step_ready(h)) return rc;
-  const int64_t ldn = std::max<int64_t>(16, ((int64_t)L.n + 15) & ~int64_t(15));   // rows on 128-byte boundaries
-  if (int rc = scratch_acquire(h, s)) return rc;
-  int rc = scratch_grow(h, &h->d_sd, &h->sd_cap, B, ldn);
-  if (rc == TOWR_OK && !F) rc = scratch_grow(h, &h->d_sf, &h->sf_cap, B, 1);
-  if (rc == TOWR_OK) rc = launch_cost(h, B, X, ldx, F ? F : h->d_sf, GR, ldgr, s, ter, per);
-  if (rc == TOWR_OK)
-    rc = auglag_chunks(h, B, X, ldx, GL, GU, ldgb, LAM, ldl, rho, nullptr, 0, nullptr, 0, RSUM, ldrs, GR, ldgr, 1, s, ter, per);
-  if (rc == TOWR_OK && XPREV)
-    rc = launch_lbfgs_update(h, B, mem, XPREV, ldxprev, X, ldx, GRPREV, ldgrprev, GR, ldgr, curv_eps, HS, HY, ldh, HMETA, USUM, ldus, s);
-  if (rc == TOWR_OK)
-    rc = launch_lbfgs_direction(h, B, mem, X, ldx, GR, ldgr, XL, XU, ldxb, HS, HY, ldh, HMETA, h->d_sd, ldn, DSUM, ldds, s);
-  if (rc == TOWR_OK) rc = launch_step(h, B, X, ldx, h->d_sd, ldn, ALPHA, alpha, XL, XU, ldxb, XP, ldxp, SSUM, ldss, s);
-  const int rr = scratch_release(h, s);
-  return rc ? rc : rr;
 }
 
 int towr_gpu_kernel_info(towr_gpu_handle h, int32_t kernel, const char** name, int32_t* n_tiles, int64_t* bytes_per_problem) {

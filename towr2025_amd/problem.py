@@ -48,6 +48,21 @@ def _check_tensor(t, what, min_cols, device=None):
         raise TowrGpuError(f"{what}: expected a 1-D or 2-D tensor")
 
 
+def _opt(t):
+    """(pointer, leading dimension) of a 2-D operand, which may be optional: None is (NULL, 0), which the C-ABI never
+    touches. Call sites unpack it in place: *_opt(X)."""
+    return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
+
+
+def _check_per_problem(t, what, B, device):
+    """An optional 1-D operand with one entry per problem, such as F: None, or >= B contiguous entries."""
+    if t is None:
+        return
+    _check_tensor(t, what, 1, device)
+    if t.dim() != 1 or t.shape[0] < B or (B > 1 and t.stride(0) != 1):
+        raise TowrGpuError(f"{what}: expected a contiguous 1-D tensor of >= B entries")
+
+
 class TowrGpuProblem:
     """`data`: side data of towr_gpu_create_ex, [(towr_data_kind, index, float64 array)]: the matrix M of
     each LinearEqualityConstraint (capi.DATA_LINEAR_M, constraint index, rows x n_set row-major) and the
@@ -241,9 +256,7 @@ class TowrGpuProblem:
         import torch
         B = X.shape[0]
         _check_tensor(X, "X", self.n, self.device)
-        _check_tensor(F, "F", 1, self.device)
-        if F.dim() != 1 or F.shape[0] < B or (B > 1 and F.stride(0) != 1):
-            raise TowrGpuError("F: expected a contiguous 1-D tensor of >= B entries")
+        _check_per_problem(F, "F", B, self.device)
         if GRAD is not None:
             _check_tensor(GRAD, "GRAD", self.n, self.device)
             if GRAD.shape[0] < B:
@@ -251,7 +264,7 @@ class TowrGpuProblem:
         if stream is None:
             stream = torch.cuda.current_stream(X.device)
         self._check(self._lib.towr_gpu_eval_cost_batch_device(
-            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(F.data_ptr()),
+            self._h, B, *_opt(X), C.c_void_p(F.data_ptr()),
             C.c_void_p(GRAD.data_ptr() if GRAD is not None else 0), GRAD.stride(0) if GRAD is not None else 0,
             C.c_void_p(stream.cuda_stream)))
 
@@ -280,7 +293,7 @@ class TowrGpuProblem:
         if stream is None:
             stream = torch.cuda.current_stream(X.device)
         self._check(self._lib.towr_gpu_sample_trajectory_batch_device(
-            self._h, X.shape[0], C.c_void_p(X.data_ptr()), X.stride(0), dt, C.c_void_p(OUT.data_ptr()), OUT.stride(0),
+            self._h, X.shape[0], *_opt(X), dt, *_opt(OUT),
             C.c_void_p(stream.cuda_stream)))
 
     def set_batch_terrain(self, terrains):
@@ -309,12 +322,8 @@ class TowrGpuProblem:
         self._check_batch(X, G, V, want_g, want_jac)
         if stream is None:
             stream = torch.cuda.current_stream(X.device)
-        def ptr(t):   # an output that is not wanted may be None (NULL: the C-ABI never touches it)
-            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
-        (gp, ldg), (vp, ldv) = ptr(G), ptr(V)
-        self._check(self._lib.towr_gpu_eval_batch_device(
-            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gp, ldg, vp, ldv,
-            int(want_g), int(want_jac), C.c_void_p(stream.cuda_stream)))
+        self._check(self._lib.towr_gpu_eval_batch_device(   # (an output that is not wanted may be None)
+            self._h, B, *_opt(X), *_opt(G), *_opt(V), int(want_g), int(want_jac), C.c_void_p(stream.cuda_stream)))
 
     def _check_batch(self, X, G, V, want_g=True, want_jac=True):
         B = X.shape[0]
@@ -351,16 +360,14 @@ class TowrGpuProblem:
         B = V.shape[0]
         self._check_rows(B, (V, "V", self.nnz), (P, "P", self.n), (Y, "Y", self.m))
         self._check(self._lib.towr_gpu_jac_vec_batch_device(
-            self._h, B, C.c_void_p(V.data_ptr()), V.stride(0), C.c_void_p(P.data_ptr()), P.stride(0),
-            C.c_void_p(Y.data_ptr()), Y.stride(0), self._stream(stream, V)))
+            self._h, B, *_opt(V), *_opt(P), *_opt(Y), self._stream(stream, V)))
 
     def jac_tvec_batch_device(self, V, LAM, Z, accumulate=False, stream=None):
         """Z[b] (+)= J_b^T LAM[b]: V (B, ldv >= nnz), LAM (B, >= m), Z (B, >= n); accumulate adds to what Z holds."""
         B = V.shape[0]
         self._check_rows(B, (V, "V", self.nnz), (LAM, "LAM", self.m), (Z, "Z", self.n))
         self._check(self._lib.towr_gpu_jac_tvec_batch_device(
-            self._h, B, C.c_void_p(V.data_ptr()), V.stride(0), C.c_void_p(LAM.data_ptr()), LAM.stride(0),
-            C.c_void_p(Z.data_ptr()), Z.stride(0), int(bool(accumulate)), self._stream(stream, V)))
+            self._h, B, *_opt(V), *_opt(LAM), *_opt(Z), int(bool(accumulate)), self._stream(stream, V)))
 
     def eval_products_batch_device(self, X, G=None, LAM=None, Z=None, P=None, Y=None, accumulate=False, stream=None):
         """Evaluate J_b at X[b] (and g into G when given), then Z[b] (+)= J_b^T LAM[b] and / or Y[b] = J_b P[b]; the
@@ -370,34 +377,38 @@ class TowrGpuProblem:
         ops += [(t, name, cols) for t, name, cols in ((G, "G", self.m), (LAM, "LAM", self.m), (Z, "Z", self.n),
                                                        (P, "P", self.n), (Y, "Y", self.m)) if t is not None]
         self._check_rows(B, *ops)
-
-        def ptr(t):
-            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
-        (gp, ldg), (lp, ldl), (zp, ldz), (pp, ldp), (yp, ldy) = ptr(G), ptr(LAM), ptr(Z), ptr(P), ptr(Y)
         self._check(self._lib.towr_gpu_eval_products_batch_device(
-            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gp, ldg, lp, ldl, zp, ldz, int(bool(accumulate)),
-            pp, ldp, yp, ldy, self._stream(stream, X)))
+            self._h, B, *_opt(X), *_opt(G), *_opt(LAM), *_opt(Z), int(bool(accumulate)), *_opt(P), *_opt(Y),
+            self._stream(stream, X)))
 
     # -------------------------------------------------------------------- residuals -----------
-    def _bounds_operands(self, B, GL, GU):
-        """(GL pointer, GU pointer, ldb) of a residual call: both None (the handle's bounds), both 1-D of >= m entries
-        (one row shared by all problems, ldb = 0) or both 2-D (B, >= m)."""
-        if GL is None and GU is None:
+    def _box_operands(self, B, lo, up, cols, names):
+        """(lower pointer, upper pointer, ldb) of an optional pair of bounds (names: the pair's and its dimension's,
+        for messages): both None (the handle's bounds), both 1-D of >= cols entries (one row shared by all problems,
+        ldb = 0) or both 2-D (B, >= cols) with one leading dimension."""
+        nl, nu, dim = names
+        if lo is None and up is None:
             return C.c_void_p(None), C.c_void_p(None), 0
-        if GL is None or GU is None:
-            raise TowrGpuError("GL and GU: give both or neither")
-        if GL.dim() != GU.dim():
-            raise TowrGpuError("GL and GU: one is shared (1-D), the other per problem (2-D)")
-        if GL.dim() == 1:
-            for t, name in ((GL, "GL"), (GU, "GU")):
-                _check_tensor(t, name, self.m, self.device)
-                if t.shape[0] < self.m or (t.shape[0] > 1 and t.stride(0) != 1):
-                    raise TowrGpuError(f"{name}: expected >= {self.m} contiguous entries")
-            return C.c_void_p(GL.data_ptr()), C.c_void_p(GU.data_ptr()), 0
-        self._check_rows(B, (GL, "GL", self.m), (GU, "GU", self.m))
-        if GL.stride(0) != GU.stride(0) or GL.stride(0) < self.m:
-            raise TowrGpuError("GL and GU: they share one leading dimension (>= m)")
-        return C.c_void_p(GL.data_ptr()), C.c_void_p(GU.data_ptr()), GL.stride(0)
+        if lo is None or up is None:
+            raise TowrGpuError(f"{nl} and {nu}: give both or neither")
+        if lo.dim() != up.dim():
+            raise TowrGpuError(f"{nl} and {nu}: one is shared (1-D), the other per problem (2-D)")
+        if lo.dim() == 1:
+            for t, name in ((lo, nl), (up, nu)):
+                _check_tensor(t, name, cols, self.device)
+                if t.shape[0] < cols or (t.shape[0] > 1 and t.stride(0) != 1):
+                    raise TowrGpuError(f"{name}: expected >= {cols} contiguous entries")
+            return C.c_void_p(lo.data_ptr()), C.c_void_p(up.data_ptr()), 0
+        self._check_rows(B, (lo, nl, cols), (up, nu, cols))
+        if lo.stride(0) != up.stride(0) or lo.stride(0) < cols:
+            raise TowrGpuError(f"{nl} and {nu}: they share one leading dimension (>= {dim})")
+        return C.c_void_p(lo.data_ptr()), C.c_void_p(up.data_ptr()), lo.stride(0)
+
+    def _bounds_operands(self, B, GL, GU):
+        return self._box_operands(B, GL, GU, self.m, ("GL", "GU", "m"))
+
+    def _var_bounds_operands(self, B, XL, XU):
+        return self._box_operands(B, XL, XU, self.n, ("XL", "XU", "n"))
 
     def residual_batch_device(self, G, SUM, GL=None, GU=None, LAM=None, rho=1.0, LAMP=None, stream=None):
         """Per-problem violation summary of G (B, >= m) against the bounds into SUM (B, >= 4 + n_constraints): max,
@@ -408,13 +419,8 @@ class TowrGpuProblem:
         ops += [(t, name, self.m) for t, name in ((LAM, "LAM"), (LAMP, "LAMP")) if t is not None]
         self._check_rows(B, *ops)
         gl, gu, ldb = self._bounds_operands(B, GL, GU)
-
-        def ptr(t):
-            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
-        (lp, ldl), (pp, ldlp) = ptr(LAM), ptr(LAMP)
         self._check(self._lib.towr_gpu_residual_batch_device(
-            self._h, B, C.c_void_p(G.data_ptr()), G.stride(0), gl, gu, ldb, lp, ldl, float(rho), pp, ldlp,
-            C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, G)))
+            self._h, B, *_opt(G), gl, gu, ldb, *_opt(LAM), float(rho), *_opt(LAMP), *_opt(SUM), self._stream(stream, G)))
 
     def eval_auglag_batch_device(self, X, SUM, Z, GL=None, GU=None, LAM=None, rho=1.0, G=None, LAMP=None,
                                  accumulate=False, stream=None):
@@ -425,36 +431,11 @@ class TowrGpuProblem:
         ops += [(t, name, self.m) for t, name in ((LAM, "LAM"), (G, "G"), (LAMP, "LAMP")) if t is not None]
         self._check_rows(B, *ops)
         gl, gu, ldb = self._bounds_operands(B, GL, GU)
-
-        def ptr(t):
-            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
-        (lp, ldl), (gp, ldg), (pp, ldlp) = ptr(LAM), ptr(G), ptr(LAMP)
         self._check(self._lib.towr_gpu_eval_auglag_batch_device(
-            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gl, gu, ldb, lp, ldl, float(rho), gp, ldg, pp, ldlp,
-            C.c_void_p(SUM.data_ptr()), SUM.stride(0), C.c_void_p(Z.data_ptr()), Z.stride(0), int(bool(accumulate)),
-            self._stream(stream, X)))
+            self._h, B, *_opt(X), gl, gu, ldb, *_opt(LAM), float(rho), *_opt(G), *_opt(LAMP), *_opt(SUM), *_opt(Z),
+            int(bool(accumulate)), self._stream(stream, X)))
 
     # -------------------------------------------------------------------- steps ---------------
-    def _var_bounds_operands(self, B, XL, XU):
-        """(XL pointer, XU pointer, ldb) of a step call: both None (the handle's bounds), both 1-D of >= n entries (one
-        row shared by all problems, ldb = 0) or both 2-D (B, >= n)."""
-        if XL is None and XU is None:
-            return C.c_void_p(None), C.c_void_p(None), 0
-        if XL is None or XU is None:
-            raise TowrGpuError("XL and XU: give both or neither")
-        if XL.dim() != XU.dim():
-            raise TowrGpuError("XL and XU: one is shared (1-D), the other per problem (2-D)")
-        if XL.dim() == 1:
-            for t, name in ((XL, "XL"), (XU, "XU")):
-                _check_tensor(t, name, self.n, self.device)
-                if t.shape[0] < self.n or (t.shape[0] > 1 and t.stride(0) != 1):
-                    raise TowrGpuError(f"{name}: expected >= {self.n} contiguous entries")
-            return C.c_void_p(XL.data_ptr()), C.c_void_p(XU.data_ptr()), 0
-        self._check_rows(B, (XL, "XL", self.n), (XU, "XU", self.n))
-        if XL.stride(0) != XU.stride(0) or XL.stride(0) < self.n:
-            raise TowrGpuError("XL and XU: they share one leading dimension (>= n)")
-        return C.c_void_p(XL.data_ptr()), C.c_void_p(XU.data_ptr()), XL.stride(0)
-
     def _alpha_operand(self, B, alpha):
         """(ALPHA pointer, scalar) of a step call: a float, or a contiguous 1-D device tensor of >= B step lengths."""
         if isinstance(alpha, (int, float)):
@@ -476,10 +457,8 @@ class TowrGpuProblem:
         self._check_rows(B, *ops)
         xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
         ap, a = self._alpha_operand(B, alpha)
-        xp, ldxp = (C.c_void_p(None), 0) if XP is None else (C.c_void_p(XP.data_ptr()), XP.stride(0))
         self._check(self._lib.towr_gpu_step_batch_device(
-            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(D.data_ptr()), D.stride(0), ap, a, xl, xu, ldb,
-            xp, ldxp, C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, X)))
+            self._h, B, *_opt(X), *_opt(D), ap, a, xl, xu, ldb, *_opt(XP), *_opt(SUM), self._stream(stream, X)))
 
     def auglag_step_batch_device(self, X, XP, SSUM, RSUM, GL=None, GU=None, LAM=None, rho=1.0, alpha=1.0, XL=None, XU=None,
                                  F=None, G=None, LAMP=None, stream=None):
@@ -491,22 +470,13 @@ class TowrGpuProblem:
                (RSUM, "RSUM", 4 + self.desc.n_constraints)]
         ops += [(t, name, self.m) for t, name in ((LAM, "LAM"), (G, "G"), (LAMP, "LAMP")) if t is not None]
         self._check_rows(B, *ops)
-        if F is not None:
-            _check_tensor(F, "F", 1, self.device)
-            if F.dim() != 1 or F.shape[0] < B or (B > 1 and F.stride(0) != 1):
-                raise TowrGpuError("F: expected a contiguous 1-D tensor of >= B entries")
+        _check_per_problem(F, "F", B, self.device)
         gl, gu, ldgb = self._bounds_operands(B, GL, GU)
         xl, xu, ldxb = self._var_bounds_operands(B, XL, XU)
         ap, a = self._alpha_operand(B, alpha)
-
-        def ptr(t):
-            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
-        (lp, ldl), (gp, ldg), (pp, ldlp) = ptr(LAM), ptr(G), ptr(LAMP)
         self._check(self._lib.towr_gpu_auglag_step_batch_device(
-            self._h, B, C.c_void_p(X.data_ptr()), X.stride(0), gl, gu, ldgb, lp, ldl, float(rho), ap, a, xl, xu, ldxb,
-            C.c_void_p(F.data_ptr() if F is not None else None), gp, ldg, pp, ldlp,
-            C.c_void_p(RSUM.data_ptr()), RSUM.stride(0), C.c_void_p(XP.data_ptr()), XP.stride(0),
-            C.c_void_p(SSUM.data_ptr()), SSUM.stride(0), self._stream(stream, X)))
+            self._h, B, *_opt(X), gl, gu, ldgb, *_opt(LAM), float(rho), ap, a, xl, xu, ldxb, _opt(F)[0], *_opt(G), *_opt(LAMP),
+            *_opt(RSUM), *_opt(XP), *_opt(SSUM), self._stream(stream, X)))
 
     # -------------------------------------------------------------------- L-BFGS --------------
     def _history_operands(self, B, mem, HS, HY, HMETA):
@@ -535,9 +505,8 @@ class TowrGpuProblem:
         self._check_rows(B, (X, "X", self.n), (XN, "XN", self.n), (GR, "GR", self.n), (GRN, "GRN", self.n), (SUM, "SUM", 6))
         hs, hy, ldh, hm = self._history_operands(B, mem, HS, HY, HMETA)
         self._check(self._lib.towr_gpu_lbfgs_update_batch_device(
-            self._h, B, mem, C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(XN.data_ptr()), XN.stride(0),
-            C.c_void_p(GR.data_ptr()), GR.stride(0), C.c_void_p(GRN.data_ptr()), GRN.stride(0), float(curv_eps),
-            hs, hy, ldh, hm, C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, GR)))
+            self._h, B, mem, *_opt(X), *_opt(XN), *_opt(GR), *_opt(GRN), float(curv_eps), hs, hy, ldh, hm, *_opt(SUM),
+            self._stream(stream, GR)))
 
     def lbfgs_direction_batch_device(self, GR, HS, HY, HMETA, D, SUM, mem, X=None, XL=None, XU=None, stream=None):
         """D[b] = the two-loop L-BFGS direction of the gradient GR[b] on the free columns (held columns: D = GR), with
@@ -551,10 +520,8 @@ class TowrGpuProblem:
         self._check_rows(B, *ops)
         hs, hy, ldh, hm = self._history_operands(B, mem, HS, HY, HMETA)
         xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
-        xp, ldx = (C.c_void_p(None), 0) if X is None else (C.c_void_p(X.data_ptr()), X.stride(0))
         self._check(self._lib.towr_gpu_lbfgs_direction_batch_device(
-            self._h, B, mem, xp, ldx, C.c_void_p(GR.data_ptr()), GR.stride(0), xl, xu, ldb, hs, hy, ldh, hm,
-            C.c_void_p(D.data_ptr()), D.stride(0), C.c_void_p(SUM.data_ptr()), SUM.stride(0), self._stream(stream, GR)))
+            self._h, B, mem, *_opt(X), *_opt(GR), xl, xu, ldb, hs, hy, ldh, hm, *_opt(D), *_opt(SUM), self._stream(stream, GR)))
 
     def auglag_lbfgs_step_batch_device(self, X, GR, XP, SSUM, RSUM, DSUM, HS, HY, HMETA, mem, XPREV=None, GRPREV=None,
                                        USUM=None, curv_eps=0.0, GL=None, GU=None, LAM=None, rho=1.0, alpha=1.0, XL=None,
@@ -575,24 +542,15 @@ class TowrGpuProblem:
         if LAM is not None:
             ops.append((LAM, "LAM", self.m))
         self._check_rows(B, *ops)
-        if F is not None:
-            _check_tensor(F, "F", 1, self.device)
-            if F.dim() != 1 or F.shape[0] < B or (B > 1 and F.stride(0) != 1):
-                raise TowrGpuError("F: expected a contiguous 1-D tensor of >= B entries")
+        _check_per_problem(F, "F", B, self.device)
         hs, hy, ldh, hm = self._history_operands(B, mem, HS, HY, HMETA)
         gl, gu, ldgb = self._bounds_operands(B, GL, GU)
         xl, xu, ldxb = self._var_bounds_operands(B, XL, XU)
         ap, a = self._alpha_operand(B, alpha)
-
-        def ptr(t):
-            return (C.c_void_p(None), 0) if t is None else (C.c_void_p(t.data_ptr()), t.stride(0))
-        (lp, ldl), (xq, ldxq), (gq, ldgq), (us, ldus) = ptr(LAM), ptr(XPREV), ptr(GRPREV), ptr(USUM if XPREV is not None else None)
         self._check(self._lib.towr_gpu_auglag_lbfgs_step_batch_device(
-            self._h, B, mem, C.c_void_p(X.data_ptr()), X.stride(0), xq, ldxq, gq, ldgq, gl, gu, ldgb, lp, ldl, float(rho),
-            ap, a, xl, xu, ldxb, float(curv_eps), hs, hy, ldh, hm,
-            C.c_void_p(F.data_ptr() if F is not None else None), C.c_void_p(GR.data_ptr()), GR.stride(0),
-            C.c_void_p(RSUM.data_ptr()), RSUM.stride(0), us, ldus, C.c_void_p(DSUM.data_ptr()), DSUM.stride(0),
-            C.c_void_p(XP.data_ptr()), XP.stride(0), C.c_void_p(SSUM.data_ptr()), SSUM.stride(0), self._stream(stream, X)))
+            self._h, B, mem, *_opt(X), *_opt(XPREV), *_opt(GRPREV), gl, gu, ldgb, *_opt(LAM), float(rho), ap, a, xl, xu, ldxb,
+            float(curv_eps), hs, hy, ldh, hm, _opt(F)[0], *_opt(GR), *_opt(RSUM), *_opt(USUM if XPREV is not None else None),
+            *_opt(DSUM), *_opt(XP), *_opt(SSUM), self._stream(stream, X)))
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
@@ -633,7 +591,7 @@ class TowrGpuProblem:
         if not (isinstance(counts, np.ndarray) and counts.dtype == np.int32 and counts.flags.c_contiguous and counts.size >= X.shape[0]):
             raise TowrGpuError("counts: contiguous int32 numpy array with one entry per problem expected")
         s = stream.cuda_stream if stream is not None else torch.cuda.current_stream(X.device).cuda_stream
-        self._check(self._lib.towr_gpu_pattern_outside_batch_device(self._h, X.shape[0], C.c_void_p(X.data_ptr()), X.stride(0),
+        self._check(self._lib.towr_gpu_pattern_outside_batch_device(self._h, X.shape[0], *_opt(X),
                                                                      counts.ctypes.data_as(capi._IP), C.c_void_p(s)))
 
     def kernel_path(self, kernel: int) -> int:
@@ -647,9 +605,7 @@ class TowrGpuProblem:
         """Launch one kernel only: a launch class or a fusion group (roofline accounting)."""
         self._check_batch(X, G, V)
         self._check(self._lib.towr_gpu_eval_batch_device_kernel(
-            self._h, kernel, X.shape[0], C.c_void_p(X.data_ptr()), X.stride(0),
-            C.c_void_p(G.data_ptr()), G.stride(0), C.c_void_p(V.data_ptr()), V.stride(0),
-            C.c_void_p(stream.cuda_stream)))
+            self._h, kernel, X.shape[0], *_opt(X), *_opt(G), *_opt(V), C.c_void_p(stream.cuda_stream)))
 
     def set_tiles_per_block(self, t: int):
         self._check(self._lib.towr_gpu_set_tiles_per_block(self._h, t))
