@@ -1913,7 +1913,7 @@ static int trip_cmp(const void* a, const void* b) {
 }
 /* sort + sum duplicates, in place; returns new count */
 static long trip_compress(TripList* L) {
-  qsort(L->t, (size_t)L->n, sizeof(Trip), trip_cmp);
+  if (L->n > 1) qsort(L->t, (size_t)L->n, sizeof(Trip), trip_cmp);   /* an empty list has a null base */
   long w = 0;
   for (long i = 0; i < L->n; ++i) {
     if (w > 0 && L->t[w - 1].r == L->t[i].r && L->t[w - 1].c == L->t[i].c) L->t[w - 1].v += L->t[i].v;

@@ -1,0 +1,115 @@
+"""Seeded generator of formulation shapes (a helper of tests/test_shape_sweep.py and tests/test_sanitizers.py; not a
+test). The parity configurations of tests/configs.py all use the reference's default shape parameters; make(seed)
+draws the ones that select the engine's code: polynomial counts, time steps, phase counts and durations, which foot
+starts in flight or never touches down, and the optional constraint sets (DESIGN.md "Shape sweep").
+
+make(seed) -> (NlpFormulation, info); np.random.default_rng(seed) is the only randomness and every knob is drawn for
+every seed, in a fixed order, so a seed is one shape for good. Reproducing a case is make(seed)[0].to_desc().
+
+Left out on purpose: Gap terrain (it moves the reference pattern; the Gap configurations and tests/gap_frozen.py cover
+it) and Chimney. With the Swing constraint every foot has an odd phase count and starts in contact: a foot in swing at
+a trajectory boundary makes SwingConstraint index out of range in the reference, and both the oracle and the engine
+refuse it (refused_descs below)."""
+import numpy as np
+
+from towr2025_amd import formulation as F
+
+ROBOTS = (F.RobotModel.Monoped, F.RobotModel.Biped, F.RobotModel.Anymal)
+TERRAINS = (F.HeightMap.FlatID, F.HeightMap.StairsID, F.HeightMap.BlockID, F.HeightMap.SlopeID, F.HeightMap.StepsID)
+TOTAL_TIMES = (0.7, 1.0, 1.13, 1.5, 2.0, 2.4)
+BASE_POLY = (0.1, 0.07, 0.25, 0.3, 1.0)
+FORCE_POLYS = (1, 2, 3, 4, 5)
+SWING_POLYS = (2, 3, 4)
+DT_ROM = (0.08, 0.05, 0.11, 0.3)
+DT_DYNAMIC = (0.1, 0.07, 0.13, 0.4)
+DT_BASE_MOTION = (0.025, 0.03, 0.2)
+DT_NODE_OR_GRID = (0.02, 0.03, 0.17, 0.0)     # 0: the node-based Force / Torque constraint
+SWING_PHASES = (1, 3, 5, 7)
+P_SWING, P_TORQUE, P_TERRAIN_HARD, P_BASE_ROM, P_OPTIMIZE, P_ROTVEC = 0.7, 0.5, 0.3, 0.3, 0.4, 0.4
+
+
+def _pick(rng, values):
+    return values[int(rng.integers(len(values)))]
+
+
+def _durations(rng, n, T):
+    """n weights in [0.5, 1.5] scaled to sum to T: the sums are not representable and differ in ulps between feet."""
+    w = rng.uniform(0.5, 1.5, n)
+    return [float(v) for v in w * (T / w.sum())]
+
+
+def make(seed):
+    rng = np.random.default_rng(seed)
+    info = {"seed": seed}
+    f = F.NlpFormulation()
+    P = f.params_
+    info["robot"] = _pick(rng, ROBOTS)
+    f.model_ = F.RobotModel(info["robot"])
+    nominal = f.model_.kinematic_model.nominal_stance
+    E = info["n_ee"] = len(nominal)
+    info["terrain"] = _pick(rng, TERRAINS)
+    f.terrain_ = F.HeightMap.MakeTerrain(info["terrain"])
+    info["goal"] = (float(rng.uniform(0.3, 2.0)), float(rng.uniform(-0.3, 0.3)))
+    info["goal_yaw"] = float(rng.uniform(-0.4, 0.4))
+    f.initial_ee_W_ = [(p[0], p[1], 0.0) for p in nominal]
+    f.initial_base_ = F.BaseState(lin_p=(0.0, 0.0, -nominal[0][2]))
+    f.final_base_ = F.BaseState(lin_p=(info["goal"][0], info["goal"][1], -nominal[0][2]), ang_p=(0.0, 0.0, info["goal_yaw"]))
+    T = info["T"] = _pick(rng, TOTAL_TIMES)
+    info["swing"] = bool(rng.random() < P_SWING)
+    info["phases"], info["contact_at_start"] = [], []
+    for ee in range(E):
+        if info["swing"]:
+            n, contact = _pick(rng, SWING_PHASES), True
+        else:
+            n, contact = int(rng.integers(1, 7)), bool(rng.random() < 0.5)
+        info["phases"].append(n)
+        info["contact_at_start"].append(contact)
+        P.ee_phase_durations_.append(_durations(rng, n, T))
+        P.ee_in_contact_at_start_.append(contact)
+    P.duration_base_polynomial_ = info["base_poly"] = _pick(rng, BASE_POLY)
+    P.force_polynomials_per_stance_phase_ = info["force_polys"] = _pick(rng, FORCE_POLYS)
+    P.torque_polynomials_per_stance_phase_ = info["torque_polys"] = _pick(rng, FORCE_POLYS)
+    P.ee_polynomials_per_swing_phase_ = info["swing_polys"] = _pick(rng, SWING_POLYS)
+    P.dt_constraint_range_of_motion_ = info["dt_rom"] = _pick(rng, DT_ROM)
+    P.dt_constraint_dynamic_ = info["dt_dynamic"] = _pick(rng, DT_DYNAMIC)
+    P.dt_constraint_base_motion_ = info["dt_base_motion"] = _pick(rng, DT_BASE_MOTION)
+    P.dt_constraint_force_ = info["dt_force"] = _pick(rng, DT_NODE_OR_GRID)
+    P.dt_constraint_torque_ = info["dt_torque"] = _pick(rng, DT_NODE_OR_GRID)
+    info["torque"] = bool(rng.random() < P_TORQUE)
+    info["terrain_hard"] = bool(rng.random() < P_TERRAIN_HARD)
+    info["base_rom"] = bool(rng.random() < P_BASE_ROM)
+    info["optimize"] = bool(rng.random() < P_OPTIMIZE)
+    info["rotvec"] = bool(rng.random() < P_ROTVEC)
+    if not info["swing"]:
+        P.constraints_.remove(F.Parameters.Swing)
+    for on, name in ((info["torque"], F.Parameters.Torque), (info["terrain_hard"], F.Parameters.TerrainHard),
+                     (info["base_rom"], F.Parameters.BaseRom)):
+        if on:
+            P.constraints_.append(name)
+    if info["optimize"]:
+        P.OptimizePhaseDurations()
+    P.angular_rep_ = int(info["rotvec"])
+    # what the shape amounts to (tests/test_shape_sweep.py test_gpu_seeds_cover_the_shapes)
+    info["starts_in_flight"] = [ee for ee in range(E) if not info["contact_at_start"][ee]]
+    info["never_touches_down"] = [ee for ee in range(E) if info["phases"][ee] == 1 and not info["contact_at_start"][ee]]
+    info["single_stance"] = [ee for ee in range(E) if info["phases"][ee] == 1 and info["contact_at_start"][ee]]
+    return f, info
+
+
+def refused_descs():
+    """name -> (ProblemDesc, foot): three descriptions with the Swing constraint and foot `foot` in swing at a
+    trajectory boundary (its first or last phase), which the reference's SwingConstraint reads out of range
+    (swing_constraint.cc:41-52 with the node before / after a boundary node)."""
+    out = {}
+    f = F.monoped_hopper()                                   # starts in flight
+    f.params_.ee_in_contact_at_start_[0] = False
+    f.params_.ee_phase_durations_[0] = [0.3, 0.4, 0.3]
+    out["monoped_starts_in_flight"] = (f.to_desc(), 0)
+    f = F.biped_walk()                                       # foot 1 ends in flight (an even phase count)
+    f.params_.ee_phase_durations_[1] = [0.5, 0.4, 0.6, 0.5]
+    out["biped_ends_in_flight"] = (f.to_desc(), 1)
+    f = F.anymal_trot(optimize_timings=True)                 # foot 2 never touches down
+    f.params_.ee_phase_durations_[2] = [2.4]
+    f.params_.ee_in_contact_at_start_[2] = False
+    out["anymal_never_touches_down"] = (f.to_desc(), 2)
+    return out

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.configs import config_descs, cost_descs, ext_cases
+from tests.shape_sweep import make as sweep_make
 from towr2025_amd import _capi as capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +22,8 @@ def _cases():
     out = {k: (v, []) for k, v in config_descs().items()}
     out.update({k: (v, []) for k, v in cost_descs().items()})
     out.update(ext_cases())
+    # shapes of the seeded sweep (tests/shape_sweep.py); 13, 85, 86 and 131 have a foot that never touches down
+    out.update({f"sweep_seed_{s}": (sweep_make(s)[0].to_desc(), []) for s in (0, 10, 13, 35, 59, 85, 86, 131)})
     return out
 
 

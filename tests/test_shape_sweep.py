@@ -1,0 +1,196 @@
+"""Seeded sweep of formulation shapes (tests/shape_sweep.py) against the oracle. tests/configs.py keeps the reference's
+default shape parameters; here the polynomial counts, time steps, phase counts and durations, feet that start in flight
+or never touch down, and the optional constraint sets vary, since they select the spline tables, instant counts, tile
+emitters and, under phase-duration optimisation, the record + compose path or its fallbacks to the tile path.
+
+CPU, seeds 0..199: the layout-only handle (sizes, x0, pattern, bounds) and the values of the test-only host emulation.
+GPU, the 32 seeds of GPU_SEEDS: single calls, the fused call and a device batch, against the oracle and each other.
+The gate is tests/parity.py's, unchanged. DESIGN.md "Shape sweep" has the generator's table and the results."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle.oracle import Oracle
+from tests import bounds_ref as R
+from tests.parity import assert_close, residue_cols
+from tests.shape_sweep import FORCE_POLYS, ROBOTS, SWING_POLYS, TERRAINS, make, refused_descs
+from towr2025_amd import TowrGpuProblem, _capi as capi
+from towr2025_amd.problem import TowrGpuError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+D = C.POINTER(C.c_double)
+CPU_SEEDS = range(200)
+# chosen with layout-only handles, small problems first, so that test_gpu_seeds_cover_the_shapes holds; 13, 86 and 131
+# are the shape that used to divide by zero in build_fstream (phase-duration optimisation with a foot that never
+# touches down; 86 also has TorqueConstraintDiscretized on that foot), 85 has such a foot with a fixed gait
+GPU_SEEDS = [0, 10, 13, 16, 18, 35, 45, 59, 74, 79, 82, 83, 85, 86, 94, 99, 109, 110, 116, 117, 123, 126, 131, 154, 160, 167,
+             176, 182, 191, 194, 195, 196]
+DYN, ROM, FDISC, TQDISC = 0, 1, 2, 3   # launch classes of TowrGpuProblem.kernel_path
+
+
+@pytest.fixture(scope="module")
+def emu():
+    lib = os.path.join(HERE, "host_emu", "build", "libemu.so")
+    if not os.path.exists(lib):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "host_emu")])
+    L = C.CDLL(lib)
+    L.emu_eval.argtypes = [C.POINTER(capi.ProblemDesc), D, D, D, C.c_char_p, C.c_int]
+    return L
+
+
+def _case(seed):
+    """(description, info, oracle, x0, reference rows, reference cols) of a seed. The oracle accepts every seed of the
+    generator: a refusal here is a generator bug, never a skip."""
+    f, info = make(seed)
+    desc = f.to_desc()
+    o = Oracle(desc)
+    x0 = o.initial_x()
+    r, c, _ = o.eval_jac(x0)
+    return desc, info, o, x0, r, c
+
+
+def _points(seed, x0, count):
+    """x0 and count - 1 perturbations x0 + 0.05 N(0, 1)."""
+    rng = np.random.default_rng(1000003 + seed)
+    return [x0] + [x0 + 0.05 * rng.standard_normal(x0.size) for _ in range(count - 1)]
+
+
+def _reference(o, r, c, x, what):
+    rr, cc, v = o.eval_jac(x)
+    assert np.array_equal(rr, r) and np.array_equal(cc, c), f"{what}: the reference pattern moved (no Gap terrain here)"
+    return o.eval_g(x), v
+
+
+def _assert_pattern(p, o, x0, r, c, what):
+    assert (p.n, p.m, p.nnz) == (o.n, o.m, len(r)), what
+    np.testing.assert_array_equal(p.initial_x().view(np.uint64), x0.view(np.uint64), err_msg=what)
+    pr, pc = p.jac_structure()
+    np.testing.assert_array_equal(pr, r, err_msg=what)
+    np.testing.assert_array_equal(pc, c, err_msg=what)
+
+
+@pytest.mark.parametrize("seed", CPU_SEEDS)
+def test_layout_matches_oracle(seed):
+    """Layout-only handle: n, m, nnz, x0 and the (row, col) list bit-exact against the oracle; the constraint sets'
+    rows against the oracle's and their bounds against tests/bounds_ref.py (bit-exact but the node-Torque (-L, L)
+    rows, within 4 ulp as in tests/test_bounds.py)."""
+    desc, info, o, x0, r, c = _case(seed)
+    p = TowrGpuProblem(desc, device=-1)
+    _assert_pattern(p, o, x0, r, c, f"seed {seed}")
+    assert [(r0, n) for _, _, r0, n in p.constraint_info()] == o.constraint_rows()
+    assert [(c0, n) for _, _, c0, n in p.varset_info()] == o.varset_cols()
+    lo, up, sets = R.bounds_ref(desc, x0)
+    assert [s[3] for s in sets] == [n for _, _, _, n in p.constraint_info()]
+    got = p.constraint_bounds()
+    exact = np.ones(p.m, dtype=bool)
+    tq = R.torque_rows(desc)
+    exact[tq] = False
+    for g, ref, side in ((got[0], lo, "lower"), (got[1], up, "upper")):
+        np.testing.assert_array_equal(g[exact].view(np.uint64), ref[exact].view(np.uint64), err_msg=f"seed {seed}: {side}")
+        assert (np.abs(g[tq] - ref[tq]) <= 4 * np.spacing(np.abs(ref[tq]))).all(), f"seed {seed}: {side} (-L, L) rows"
+
+
+@pytest.mark.parametrize("seed", CPU_SEEDS)
+def test_emulated_values_match_oracle(emu, seed):
+    """The host emulation of the kernels' item loop at x0 and one perturbation, outputs pre-filled with NaN."""
+    desc, info, o, x0, r, c = _case(seed)
+    fc = residue_cols(desc, o.n)
+    for k, x in enumerate(_points(seed, x0, 2)):
+        g_ref, v_ref = _reference(o, r, c, x, f"seed {seed} point {k}")
+        g, v = np.full(o.m, np.nan), np.full(len(r), np.nan)
+        err = C.create_string_buffer(256)
+        assert emu.emu_eval(C.byref(desc), x.ctypes.data_as(D), g.ctypes.data_as(D), v.ctypes.data_as(D), err, 256) == 0, err.value
+        assert_close(g_ref, g, r, v_ref, v, o.m, f"seed {seed} point {k}", cols_ref=c, floor_cols=fc)
+
+
+def test_gpu_seeds_cover_the_shapes():
+    """GPU_SEEDS must not collapse back to the default shape: conditions on the drawn values and on the launch paths
+    of the layout-only handles of exactly that list."""
+    assert len(GPU_SEEDS) == 32 and len(set(GPU_SEEDS)) == 32
+    infos, paths = [], []
+    for seed in GPU_SEEDS:
+        f, info = make(seed)
+        p = TowrGpuProblem(f.to_desc(), device=-1)
+        infos.append(info)
+        paths.append([p.kernel_path(k) for k in (DYN, ROM, FDISC, TQDISC)])
+    assert sum(i["optimize"] for i in infos) >= 12
+    assert sum(i["rotvec"] for i in infos) >= 8
+    assert {i["force_polys"] for i in infos} == set(FORCE_POLYS)
+    assert {i["swing_polys"] for i in infos} == set(SWING_POLYS)
+    assert sum(bool(i["starts_in_flight"]) for i in infos) >= 4
+    never = [i for i in infos if i["never_touches_down"]]
+    assert len(never) >= 2 and any(i["optimize"] for i in never)
+    assert sum(bool(i["single_stance"]) for i in infos) >= 2
+    assert {i["terrain"] for i in infos} == set(TERRAINS)
+    assert {i["robot"] for i in infos} == set(ROBOTS)
+    assert any(i["dt_force"] == 0.0 for i in infos), "node-based Force"
+    assert any(i["torque"] and i["dt_torque"] == 0.0 for i in infos), "node-based Torque"
+    gait = [pt for i, pt in zip(infos, paths) if i["optimize"]]
+    for k, name in ((DYN, "Dynamic"), (ROM, "RangeOfMotion"), (FDISC, "FDISC"), (TQDISC, "TQDISC")):
+        assert sum(pt[k] == 1 for pt in gait) >= 3, f"{name} on the record + compose path"
+    # fallbacks to the tile path on gait-optimising seeds (no Gap terrain here): a foot that never touches down has
+    # empty FDISC / TQDISC rows (build_fstream's and build_gstream_class's exits for a constraint without entries)
+    assert any(pt[FDISC] == 0 for pt in gait), "FDISC fallback to the tile path"
+    assert any(pt[TQDISC] == 0 for pt in gait), "TQDISC fallback to the tile path"
+    for i, pt in zip(infos, paths):   # and nothing else falls back in the table's range
+        if i["optimize"] and not i["never_touches_down"]:
+            assert all(k in (1, -1) for k in pt), i["seed"]
+    for i, pt in zip(infos, paths):   # the fixed-gait seeds never stream
+        if not i["optimize"]:
+            assert all(k in (0, -1) for k in pt), i["seed"]
+
+
+@pytest.mark.parametrize("name", sorted(refused_descs()))
+def test_swing_at_trajectory_boundary_is_refused(name):
+    """A foot in swing at a trajectory boundary with the Swing constraint: the oracle refuses it (the reference reads
+    out of range), and engine creation returns TOWR_ERR_INVALID with a message, neither crashing nor accepting."""
+    desc, foot = refused_descs()[name]
+    with pytest.raises(ValueError, match="swing node at trajectory boundary"):
+        Oracle(desc)
+    lib = capi.load_library()
+    h = C.c_void_p()
+    rc = lib.towr_gpu_create_ex(C.byref(desc), 0, None, -1, C.byref(h))
+    assert rc == capi.TOWR_ERR_INVALID and not h.value
+    msg = lib.towr_gpu_last_error(None).decode()
+    assert "swing node at trajectory boundary" in msg and f"endeffector {foot}" in msg, msg
+    with pytest.raises(TowrGpuError, match=r"\(-1\).*swing node at trajectory boundary"):
+        TowrGpuProblem(desc, device=-1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", GPU_SEEDS)
+def test_gpu_values_match_oracle(seed):
+    """Device 0: pattern against the oracle; eval_g + eval_jac_values, eval_g_jac bit-equal to them; a device batch
+    of 3 (x0 and two perturbations) into NaN-filled outputs with ldv rounded up to 16, each row bit-equal to the
+    single calls and the padding untouched; everything against the oracle under the gate."""
+    import torch
+    desc, info, o, x0, r, c = _case(seed)
+    p = TowrGpuProblem(desc, device=0)
+    _assert_pattern(p, o, x0, r, c, f"seed {seed}")
+    fc = residue_cols(desc, o.n)
+    X = np.stack(_points(seed, x0, 3))
+    single = []
+    for k, x in enumerate(X):
+        g_ref, v_ref = _reference(o, r, c, x, f"seed {seed} point {k}")
+        g, v = p.eval_g(x), p.eval_jac_values(x)
+        st = assert_close(g_ref, g, r, v_ref, v, o.m, f"seed {seed} point {k}", cols_ref=c, floor_cols=fc)
+        g2, v2 = p.eval_g_jac(x)
+        np.testing.assert_array_equal(g2.view(np.uint64), g.view(np.uint64), err_msg=f"seed {seed} point {k}: g of eval_g_jac")
+        np.testing.assert_array_equal(v2.view(np.uint64), v.view(np.uint64), err_msg=f"seed {seed} point {k}: J of eval_g_jac")
+        single.append((g, v))
+        print(f"seed {seed} point {k}: n={p.n} m={p.m} nnz={p.nnz} max relative error {st['max_rel']:.3e}, worst |err|/tol {st['worst']:.3f}")
+    dev = torch.device("cuda:0")
+    ldv = (p.nnz + 15) // 16 * 16
+    Gd = torch.full((3, p.m), np.nan, dtype=torch.float64, device=dev)
+    Vd = torch.full((3, ldv), np.nan, dtype=torch.float64, device=dev)
+    p.eval_batch_device(torch.from_numpy(X).to(dev), Gd, Vd)
+    torch.cuda.synchronize()
+    G, V = Gd.cpu().numpy(), Vd.cpu().numpy()
+    assert np.isnan(V[:, p.nnz:]).all(), f"seed {seed}: write past nnz"
+    for k, (g, v) in enumerate(single):
+        np.testing.assert_array_equal(G[k].view(np.uint64), g.view(np.uint64), err_msg=f"seed {seed}: g of batch row {k}")
+        np.testing.assert_array_equal(V[k, :p.nnz].view(np.uint64), v.view(np.uint64), err_msg=f"seed {seed}: J of batch row {k}")
+    p.close()

@@ -97,7 +97,16 @@ void set_linear(NodeSet& s, const double ini[3], const double fin[3], double T) 
     }
 }
 
-void rot(const double rpy[3], double R[3][3]) { euler_R(trig(rpy), R); }
+// The initial values are compared with the reference's bit for bit. An optimising gcc build of the reference (and of
+// the oracle) evaluates sin and cos of one angle as one glibc sincos, whose results are not always sin's and cos's
+// bits (about 1 argument in 1000 differs by an ulp): so sincos here too, not trig()'s separate host calls.
+void rot(const double rpy[3], double R[3][3]) {
+  Trig q;
+  sincos(rpy[0], &q.sx, &q.cx);
+  sincos(rpy[1], &q.sy, &q.cy);
+  sincos(rpy[2], &q.sz, &q.cz);
+  euler_R(q, R);
+}
 
 std::vector<double> get_values(const NodeSet& s) {   // nodes_variables.cc:56-66
   std::vector<double> x((size_t)s.n_rows);
@@ -616,6 +625,7 @@ int build_fstream(Layout& L, std::string& err) {
     if (si.col0 < 0 || m.ee != ee) return TOWR_OK;
     const int r0 = cs.row0, nrow = cs.rows, K = nrow / 5;
     const int64_t L0 = L.row_ptr[r0 + 1] - L.row_ptr[r0];
+    if (L0 == 0) return TOWR_OK;   // a foot that never touches down: no force node is optimised, its rows are empty
     for (int r = r0; r < r0 + nrow; ++r) {
       if (L.row_ptr[r + 1] - L.row_ptr[r] != L0) return TOWR_OK;
       if (!std::equal(L.col.begin() + L.row_ptr[r], L.col.begin() + L.row_ptr[r + 1], L.col.begin() + L.row_ptr[r0])) return TOWR_OK;
@@ -796,6 +806,9 @@ bool build_gstream_class(Layout& L, int cls, const std::vector<BaseDec>& bdec, c
       Lsum += (int)len; Psum += P;
       tmax = std::max(tmax, (int)tmpl.size() - toff);
     }
+    // rows without entries (TQDISC of a foot that never touches down: no force or torque node is optimised): the
+    // composer's block would have an empty CSR range, which its head / tail stores do not expect
+    if (Lsum == 0) { why = "a constraint without entries"; return false; }
     g.Li = Lsum; g.Psum = Psum; g.pc0 = (int32_t)pcode.size(); g.K = K;
     // instants per compose block: the composer finds an entry's instant by a float division of its position,
     // exact while the block's range stays below kFloatDivMax (layout.h)
@@ -1484,7 +1497,10 @@ int build_layout_ex(const towr_problem_desc_t& d, int n_data, const towr_data_t*
         int k = 0;
         for (int id = 0; id < mv.n_nodes; ++id)
           if (!mv.is_constant_node(id)) {
-            if (id == 0 || id == mv.n_nodes - 1) { err = "swing node at trajectory boundary (the reference indexes out of range)"; return TOWR_ERR_INVALID; }
+            if (id == 0 || id == mv.n_nodes - 1) {
+              err = "swing node at trajectory boundary of endeffector " + std::to_string(c.ee) + " (the reference indexes out of range)";
+              return TOWR_ERR_INVALID;
+            }
             add(IT_SWING, 0, c.ee, k, row + 4 * k, 0.0, id, 0, c.p[0] > 0 ? c.p[0] : 0.3); ++k; ++inst;
           }
         info.rows = 4 * k;
