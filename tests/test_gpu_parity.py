@@ -641,3 +641,50 @@ def test_keep_jacobian_pair(name):
     xc[7] = np.nextafter(xc[7], np.inf)                               # one ulp away: not the kept x
     np.testing.assert_array_equal(p.eval_g_keep_jac(xb), gb)
     np.testing.assert_array_equal(p.eval_jac_values_kept(xc), p.eval_jac_values(xc))
+
+
+@pytest.mark.parametrize("name", ["anymal_stairs_gaitopt", "anymal_trot_rotvec"])
+def test_handle_regrow_and_recreate(name):
+    """What a handle owns across calls: the per-problem scratch (the streaming path's records for the gait layout, the
+    coefficient pre-pass's for RotVec) grown from B = 2 to B = 65 (just above kSplitBatch = 64) and used again at
+    B = 2, the host staging grown from B = 1 to B = 5, and a second handle on the same description after the first
+    was closed. Every output equals, bit for bit, what a fresh handle gives for the same call."""
+    import torch
+    desc = CONFIGS[name]
+    dev = torch.device("cuda:0")
+
+    def device_call(p, X):
+        B, ldv = len(X), (p.nnz + 15) // 16 * 16
+        Gd = torch.full((B, p.m), np.nan, dtype=torch.float64, device=dev)
+        Vd = torch.full((B, ldv), np.nan, dtype=torch.float64, device=dev)
+        p.eval_batch_device(torch.from_numpy(X).to(dev), Gd, Vd)
+        torch.cuda.synchronize()
+        return Gd.cpu().numpy(), Vd.cpu().numpy()[:, :p.nnz]
+
+    def host_call(p, X):
+        return p.eval_batch(X)
+
+    def fresh(call, X):
+        q = TowrGpuProblem(desc, device=0)
+        try:
+            return call(q, X)
+        finally:
+            q.close()
+
+    def same(got, ref, what):
+        for a, b, out in zip(got, ref, ("g", "values")):
+            assert not np.isnan(a).any() and np.array_equal(a, b), f"{name} {what}: {out} differs from a fresh handle's"
+
+    p = TowrGpuProblem(desc, device=0)
+    x0 = p.initial_x()
+    X = np.stack([_perturb(x0, 700 + b) for b in range(65)])
+    ref2, ref65 = fresh(device_call, X[:2]), fresh(device_call, X)
+    same(device_call(p, X[:2]), ref2, "B = 2")
+    same(device_call(p, X), ref65, "B = 65 (scratch regrown)")
+    same(device_call(p, X[:2]), ref2, "B = 2 after B = 65")
+    same(host_call(p, X[3:4]), fresh(host_call, X[3:4]), "host B = 1")
+    same(host_call(p, X[5:10]), fresh(host_call, X[5:10]), "host B = 5 (staging regrown)")
+    p.close()
+    q = TowrGpuProblem(desc, device=0)
+    same(device_call(q, X), ref65, "B = 65 on a second handle")
+    q.close()

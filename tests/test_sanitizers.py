@@ -1,6 +1,8 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer runs of the CPU-side code (VERDICT r1 weak item 12,
 SURVEY §5): the oracle (oracle/sancheck.c) and the engine's host code — the layout builder and the host
-instantiation of engine_math.h through the emulation (tests/host_emu/sancheck.cc, built host-only) —
+instantiation of engine_math.h through the emulation (tests/host_emu/sancheck.cc, built host-only), and the
+library's own host code behind the C-ABI, the handle's lifetimes above all (tests/host_emu/handlecheck.cc:
+layout-only handles and the failure paths of creation, linked with the library's kernel objects) —
 over every parity configuration. GPU sanitizers are not available on this pool; these are host-only."""
 import os
 import struct
@@ -16,6 +18,7 @@ from towr2025_amd import _capi as capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE = os.path.join(ROOT, "oracle", "build", "sancheck")
 EMU = os.path.join(ROOT, "tests", "host_emu", "build", "sancheck")
+HANDLES = os.path.join(ROOT, "tests", "host_emu", "build", "handlecheck")
 
 
 def _cases():
@@ -32,10 +35,10 @@ CASES = _cases()
 
 @pytest.fixture(scope="module")
 def binaries():
-    for d, exe in ((os.path.join(ROOT, "oracle"), ORACLE), (os.path.join(ROOT, "tests", "host_emu"), EMU)):
+    for d, exes in ((os.path.join(ROOT, "oracle"), (ORACLE,)), (os.path.join(ROOT, "tests", "host_emu"), (EMU, HANDLES))):
         subprocess.check_call(["make", "-s", "-C", d, "sanitize"])
-        assert os.path.exists(exe)
-    return ORACLE, EMU
+        assert all(os.path.exists(exe) for exe in exes)
+    return ORACLE, EMU, HANDLES
 
 
 def _write(path, desc, data):

@@ -782,11 +782,12 @@ int ensure_stage(towr_gpu_handle h, int B) {
   if (h->d_x) { (void)hipFree(h->d_x); (void)hipFree(h->d_g); (void)hipFree(h->d_v); }
   if (h->h_x) { (void)hipHostFree(h->h_x); (void)hipHostFree(h->h_g); (void)hipHostFree(h->h_v); }
   h->d_x = h->d_g = h->d_v = h->h_x = h->h_g = h->h_v = nullptr;
+  h->stage_B = 0;   // nothing is staged until every buffer below exists: a call after a failed allocation comes back here
   HIPCHK(h, hipMalloc(&h->d_x, sizeof(double) * (size_t)B * L.n));
   HIPCHK(h, hipMalloc(&h->d_g, sizeof(double) * (size_t)B * std::max(1, L.m)));
   HIPCHK(h, hipMalloc(&h->d_v, sizeof(double) * (size_t)B * std::max<int64_t>(1, L.nnz)));
-  if (!h->d_f) {
-    HIPCHK(h, hipMalloc(&h->d_f, sizeof(double)));
+  if (!h->d_grad) {   // (both, also when an earlier attempt got d_f alone)
+    if (!h->d_f) HIPCHK(h, hipMalloc(&h->d_f, sizeof(double)));
     HIPCHK(h, hipMalloc(&h->d_grad, sizeof(double) * (size_t)std::max(1, L.n)));
   }
   HIPCHK(h, hipHostMalloc(&h->h_x, sizeof(double) * (size_t)B * L.n, hipHostMallocDefault));
