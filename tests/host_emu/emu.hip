@@ -377,6 +377,106 @@ extern "C" int emu_traj(const towr_problem_desc_t* d, const double* x, double dt
   return k;
 }
 
+// The product tables of build_jprod (Layout::jp_chunks, jp_rseg, jp_cseg, jp_cidx, jp_empty_rows, jp_row) as plain
+// arrays. sizes (9): chunks, row segments, column segments, empty rows, jp_long, kJpChunk, nnz, m, n. An output that
+// is null is skipped (a first call with all of them null gives the sizes to allocate). chunks: {rs0, rns, rnl, cs0,
+// cns, cnl} per chunk; rseg / cseg: {out, q0, len, flags} per segment; cidx: kJpChunk entries per chunk.
+extern "C" int emu_jp_tables(const towr_problem_desc_t* d, int64_t* sizes, int32_t* chunks, int32_t* rseg, int32_t* cseg,
+                             uint16_t* cidx, int32_t* empty_rows, int32_t* row) {
+  Layout L; std::string e;
+  if (build_layout(*d, L, e)) return -1;
+  const int64_t sz[9] = {(int64_t)L.jp_chunks.size(), (int64_t)L.jp_rseg.size(), (int64_t)L.jp_cseg.size(),
+                         (int64_t)L.jp_empty_rows.size(), L.jp_long, kJpChunk, L.nnz, L.m, L.n};
+  for (int i = 0; i < 9; ++i) sizes[i] = sz[i];
+  if (chunks)
+    for (size_t c = 0; c < L.jp_chunks.size(); ++c) {
+      const JpChunk& ch = L.jp_chunks[c];
+      const int32_t v[6] = {ch.rs0, ch.rns, ch.rnl, ch.cs0, ch.cns, ch.cnl};
+      for (int i = 0; i < 6; ++i) chunks[6 * c + i] = v[i];
+    }
+  auto segs = [](const std::vector<JpSeg>& from, int32_t* to) {
+    for (size_t k = 0; to && k < from.size(); ++k) {
+      to[4 * k] = from[k].out; to[4 * k + 1] = from[k].q0; to[4 * k + 2] = from[k].len; to[4 * k + 3] = from[k].flags;
+    }
+  };
+  segs(L.jp_rseg, rseg);
+  segs(L.jp_cseg, cseg);
+  if (cidx) std::copy(L.jp_cidx.begin(), L.jp_cidx.end(), cidx);
+  if (empty_rows) std::copy(L.jp_empty_rows.begin(), L.jp_empty_rows.end(), empty_rows);
+  if (row) std::copy(L.jp_row.begin(), L.jp_row.end(), row);
+  return 0;
+}
+
+// The two product kernels of jprod.hip for one problem, as a host walk of the same tables in the same order, so that
+// every output is the kernel's own tree of additions: the product is rounded into the chunk's tile before it is
+// summed; a short segment is summed by one lane in ascending order; a long one by 64 lanes (lane l: entries l,
+// l + 64, ... in order), then the __shfl_down tree with offsets 32..1 (lane 0's value); a row cut by a chunk boundary
+// goes through the two-slot carry picked by the chunk's parity; a column's chunk sums join its running sum in chunk
+// order; `accumulate` leaves a column without entries alone. V (nnz), P, Z0 (n), LAM (m) -> Y (m: J P), Z (n: J^T LAM),
+// Za (n: Z0 + J^T LAM). The tile starts as NaN and so do the carries: a segment that reads an entry its chunk did not
+// write, or a carry that was not handed on, shows in the output. No contraction anywhere below: the kernels cannot
+// fuse a product with the sum either, since the product goes through LDS.
+#pragma clang fp contract(off)
+namespace {
+double jp_seg_sum(const JpSeg& s, const double* tile, const uint16_t* cidx, bool wave) {
+  const int q0 = cidx ? (s.q0 & (kJpChunk - 1)) : s.q0;
+  double lane[64];
+  const int lanes = wave ? 64 : 1;
+  for (int l = 0; l < lanes; ++l) {
+    double acc = 0.0;
+    for (int i = l; i < s.len; i += lanes) acc += tile[cidx ? cidx[q0 + i] : q0 + i];
+    lane[l] = acc;
+  }
+  if (wave)
+    for (int o = 32; o > 0; o >>= 1)
+      for (int l = 0; l < o; ++l) lane[l] += lane[l + o];
+  return lane[0];
+}
+}
+extern "C" int emu_jac_products_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, const double* V,
+                                   const double* P, const double* LAM, const double* Z0, double* Y, double* Z, double* Za) {
+  Layout L; std::string e;
+  if (build_layout_ex(*d, n_data, data, L, e)) return -1;
+  const int n_chunks = (int)L.jp_chunks.size();
+  std::vector<double> tile((size_t)kJpChunk, std::nan("")), zacc((size_t)L.n, 0.0);
+  double carry[2] = {std::nan(""), std::nan("")};
+  for (int32_t r : L.jp_empty_rows) Y[r] = 0.0;
+  for (int ci = 0; ci < n_chunks; ++ci) {   // towr_jac_vec_kernel
+    const int64_t k0 = (int64_t)ci * kJpChunk, k1 = std::min<int64_t>(L.nnz, k0 + kJpChunk);
+    const JpChunk& ch = L.jp_chunks[ci];
+    for (int64_t k = k0; k < k1; ++k) tile[(size_t)(k - k0)] = V[k] * P[L.col[k]];
+    for (int q = 0; q < ch.rns + ch.rnl; ++q) {
+      const JpSeg& s = L.jp_rseg[ch.rs0 + q];
+      double sum = jp_seg_sum(s, tile.data(), nullptr, q >= ch.rns);
+      if (s.flags & 1) sum = carry[(ci & 1) ^ 1] + sum;
+      if (s.flags & 2) carry[ci & 1] = sum;
+      else Y[s.out] = sum;
+    }
+  }
+  std::fill(tile.begin(), tile.end(), std::nan(""));
+  for (int ci = 0; ci < n_chunks; ++ci) {   // towr_jac_tvec_kernel
+    const int64_t k0 = (int64_t)ci * kJpChunk, k1 = std::min<int64_t>(L.nnz, k0 + kJpChunk);
+    const JpChunk& ch = L.jp_chunks[ci];
+    for (int64_t k = k0; k < k1; ++k) tile[(size_t)(k - k0)] = V[k] * LAM[L.jp_row[k]];
+    const uint16_t* cidx = L.jp_cidx.data() + k0;
+    for (int q = 0; q < ch.cns + ch.cnl; ++q) {
+      const JpSeg& s = L.jp_cseg[ch.cs0 + q];
+      zacc[s.out] += jp_seg_sum(s, tile.data(), cidx, q >= ch.cns);
+    }
+  }
+  for (int j = 0; j < L.n; ++j) {
+    Z[j] = zacc[j];
+    Za[j] = Z0[j];
+    if (L.col_ptr[j + 1] != L.col_ptr[j]) Za[j] += zacc[j];
+  }
+  return 0;
+}
+extern "C" int emu_jac_products(const towr_problem_desc_t* d, const double* V, const double* P, const double* LAM,
+                                const double* Z0, double* Y, double* Z, double* Za) {
+  return emu_jac_products_ex(d, 0, nullptr, V, P, LAM, Z0, Y, Z, Za);
+}
+#pragma clang fp contract(fast)
+
 // whether every polynomial's active-window PhaseCols (pact window, then up to kGsAct entries: n, ids, derivs) coincide
 // over the three dimensions, per spline (experiment aid: the record composers' window sums per dimension)
 extern "C" int emu_window_dims(const towr_problem_desc_t* d) {

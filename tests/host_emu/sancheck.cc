@@ -15,6 +15,8 @@ extern "C" int emu_eval_ex(const towr_problem_desc_t* d, int n_data, const towr_
                            double* v, char* err, int errlen);
 extern "C" int emu_cost(const towr_problem_desc_t* d, const double* x, double* f, double* grad, char* err, int errlen);
 extern "C" int emu_traj(const towr_problem_desc_t* d, const double* x, double dt, double* out, int max_rows);
+extern "C" int emu_jac_products_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, const double* V,
+                                   const double* P, const double* LAM, const double* Z0, double* Y, double* Z, double* Za);
 
 int main(int argc, char** argv) {
   if (argc < 2) { std::fprintf(stderr, "usage: %s problem.bin\n", argv[0]); return 2; }
@@ -43,6 +45,14 @@ int main(int argc, char** argv) {
   const int rows = emu_traj(&d, x.data(), 0.05, nullptr, 0);
   std::vector<double> tr((size_t)(rows > 0 ? rows : 1) * (19 + 25 * d.robot.n_ee));
   emu_traj(&d, x.data(), 0.05, tr.data(), rows);
+  // the product tables' walk (build_jprod's chunks, segments and by-column lists) on the values above, in
+  // exactly-sized buffers: P = x, LAM = g, Z0 = x
+  std::vector<double> vx(v.begin(), v.begin() + (size_t)L.nnz), lam(g.begin(), g.begin() + (size_t)L.m);
+  std::vector<double> y((size_t)L.m), z((size_t)L.n), za((size_t)L.n);
+  if (emu_jac_products_ex(&d, nd, data.data(), vx.data(), x.data(), lam.data(), x.data(), y.data(), z.data(), za.data())) {
+    std::fprintf(stderr, "products: layout\n");
+    return 7;
+  }
   std::printf("ok n=%d m=%d nnz=%lld\n", L.n, L.m, (long long)L.nnz);
   return 0;
 }

@@ -8,7 +8,6 @@ gamma_k = k u / (1 - k u), u = 2^-53 — the bound of a length-k dot product in 
 FMA contraction; the factor 2 covers the reference's rounding to double. Outputs without terms must be exactly 0.0.
 Under `accumulate` the pre-filled Z is one more term. Every case uses padded leading dimensions with NaN padding."""
 import functools
-import math
 import os
 import subprocess
 
@@ -16,7 +15,7 @@ import numpy as np
 import pytest
 
 from tests.configs import config_descs
-from tests.gpu_helpers import _bits, _dev, _nan, _padded, _same_bits
+from tests.gpu_helpers import _bits, _check_products, _dev, _nan, _padded, _reference, _same_bits
 from towr2025_amd import TowrGpuProblem, _capi as capi
 from towr2025_amd.problem import TowrGpuError
 
@@ -24,46 +23,16 @@ pytestmark = pytest.mark.gpu
 
 CONFIGS = config_descs()
 # the smallest shapes at which each mechanism can fail: fewer columns than lanes; short rows over several chunks;
-# long schedule columns and rows with V_b larger than LDS; the largest pattern; a fusion-free launch list
+# long schedule columns and rows with V_b larger than LDS; the largest pattern; a fusion-free launch list; the two
+# smallest patterns with m + n > 5632, whose J^T lam launch needs more than 64 KiB of dynamic LDS (72,336 and 71,568
+# bytes: the hipFuncSetAttribute branch of products_ready, without which the launch is refused)
 CASES = [("monoped_procedural", 1), ("monoped_procedural", 3), ("anymal_trot_2p4s", 1), ("anymal_trot_2p4s", 37),
-         ("anymal_stairs_gaitopt", 3), ("hopper_gait_torque", 2), ("anymal_trot_rotvec", 3)]
-U = 2.0 ** -53
-EXT = np.finfo(np.longdouble).nmant > 52
+         ("anymal_stairs_gaitopt", 3), ("hopper_gait_torque", 2), ("anymal_trot_rotvec", 3), ("hyq_gap_torque", 2),
+         ("anymal_gait_torque", 2)]
 
 
 def _lds(p):
     return (p.nnz + 15) // 16 * 16 + 16, p.m + 5, p.n + 3   # ldv, ldy, ldz
-
-
-def _segment_sums(terms, ptr):
-    """Sums of terms[ptr[i]:ptr[i+1]]: in extended precision where long double has more than 53 bits (not yet
-    rounded to double), else math.fsum per segment; empty segments give 0."""
-    out = np.zeros(len(ptr) - 1, dtype=np.longdouble if EXT else np.float64)
-    nz = np.flatnonzero(np.diff(ptr) > 0)
-    if nz.size and EXT:
-        out[nz] = np.add.reduceat(terms, ptr[:-1][nz])
-    for i in (() if EXT else nz):
-        out[i] = math.fsum(terms[ptr[i]:ptr[i + 1]])
-    return out
-
-
-def _reference(p, V, P, LAM):
-    """Per output of host arrays V (B, nnz), P (B, n), LAM (B, m): (Y_ref, tol_Y, Z_ref before rounding, S_Z, k_Z,
-    gamma) from the engine's own V, jac_csr() and the vectors."""
-    rp, col = p.jac_csr()
-    cp, row, idx = p.jac_csc()
-    B = V.shape[0]
-    ft = np.longdouble if EXT else np.float64
-    kY, kZ = np.diff(rp).astype(np.float64), np.diff(cp).astype(np.float64)
-    Y, SY, Z, SZ = (np.zeros((B, p.m), ft), np.zeros((B, p.m), ft), np.zeros((B, p.n), ft), np.zeros((B, p.n), ft))
-    for b in range(B):
-        ty = V[b].astype(ft) * P[b][col].astype(ft)
-        tz = (V[b].astype(ft) * LAM[b][np.repeat(np.arange(p.m), np.diff(rp))].astype(ft))[idx]
-        assert np.array_equal(row, np.repeat(np.arange(p.m), np.diff(rp))[idx])
-        Y[b], SY[b] = _segment_sums(ty, rp), _segment_sums(np.abs(ty), rp)
-        Z[b], SZ[b] = _segment_sums(tz, cp), _segment_sums(np.abs(tz), cp)
-    gam = lambda k: k * U / (1 - k * U)
-    return Y.astype(np.float64), 2 * gam(kY) * SY.astype(np.float64), Z, SZ.astype(np.float64), kZ, gam
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,34 +60,20 @@ def _case(name, B):
                 ref=_reference(p, V, P, LAM))
 
 
-def _check_products(tag, p, Yd, Zd, Zad, Z0, ref):
-    Y_ref, tolY, Z_ref, SZ, kZ, gam = ref
-    Y, Z, Za = Yd.cpu().numpy(), Zd.cpu().numpy(), Zad.cpu().numpy()
-    assert np.isnan(Y[:, p.m:]).all() and np.isnan(Z[:, p.n:]).all() and np.isnan(Za[:, p.n:]).all(), f"{tag}: padding written"
-    Y, Z, Za = Y[:, :p.m], Z[:, :p.n], Za[:, :p.n]
-    tolZ = 2 * gam(kZ) * SZ
-    tolZa = 2 * gam(kZ + 1) * (SZ + np.abs(Z0))
-    eY, eZ = np.abs(Y - Y_ref), np.abs(Z - Z_ref.astype(np.float64))
-    eZa = np.abs(Za - (Z_ref + Z0).astype(np.float64))   # (the pre-filled Z joins the sum before the one rounding)
-    worst = max(np.max(np.where(tolY > 0, eY / np.where(tolY > 0, tolY, 1), 0), initial=0.0),
-                np.max(np.where(tolZ > 0, eZ / np.where(tolZ > 0, tolZ, 1), 0), initial=0.0),
-                np.max(np.where(kZ > 0, eZa / np.where(tolZa > 0, tolZa, 1), 0), initial=0.0))
-    print(f"{tag}: largest |err| / bound {worst:.3f}")
-    assert (eY <= tolY).all() and (eZ <= tolZ).all(), f"{tag}: outside the dot-product bound ({worst:.3f})"
-    assert (eZa <= tolZa)[:, kZ > 0].all(), f"{tag}: accumulate outside the bound ({worst:.3f})"
-    rp, _ = p.jac_csr()
-    empty_r, empty_c = np.diff(rp) == 0, kZ == 0
-    assert (Y[:, empty_r] == 0.0).all() and not np.signbit(Y[:, empty_r]).any(), f"{tag}: empty rows are not 0.0"
-    assert (Z[:, empty_c] == 0.0).all(), f"{tag}: empty columns are not 0.0"
-    assert np.array_equal(Za[:, empty_c].view(np.int64), Z0[:, empty_c].view(np.int64)), f"{tag}: accumulate touched an empty column"
-
-
 @pytest.mark.parametrize("name,B", CASES)
 def test_products_within_bound_and_padding_untouched(name, B):
     c = _case(name, B)
     p = c["p"]
     _check_products(f"{name} B={B}", p, c["Yd"], c["Zd"], c["Zad"], c["Z0"], c["ref"])
     assert np.isnan(c["Vd"].cpu().numpy()[:, p.nnz:]).all()   # (never read is not observable; never written is)
+
+
+def test_cases_reach_the_large_lds_launch():
+    for name in ("hyq_gap_torque", "anymal_gait_torque"):
+        p = _case(name, 2)["p"]
+        lds = 8 * (((p.m + 1) & ~1) + ((p.n + 1) & ~1) + 2048) + 2 * 2048   # jprod.hip jp_tvec_lds
+        assert lds > 64 * 1024 and lds <= 160 * 1024, (name, lds)
+    assert all(_case(name, B)["p"].m + _case(name, B)["p"].n <= 5632 for name, B in CASES[:7])
 
 
 @pytest.mark.parametrize("name,B", CASES)

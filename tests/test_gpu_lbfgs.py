@@ -52,6 +52,15 @@ def _ints(a):
 
 @functools.lru_cache(maxsize=None)
 def _problem(name):
+    """The handle of a configuration of tests/configs.py, or of shape N of the seeded sweep ("sweep_seed_N":
+    tests/test_gpu_sweep_consumers.py), with its variable bounds."""
+    if name.startswith("sweep_seed_"):
+        from tests.shape_sweep import make
+        f = make(int(name[len("sweep_seed_"):]))[0]
+        f.params_.enable_stance_tracking = False   # (as gpu_helpers._formulation: no stance positions are given)
+        vb = f.var_bounds_data()
+        p = TowrGpuProblem(f.to_desc(), device=0, data=vb)
+        return (p,) + p.variable_bounds() + (vb,)
     f, kw = _formulation(name)
     vb = f.var_bounds_data(**kw)
     p = TowrGpuProblem(config_descs()[name], device=0, data=vb)
@@ -111,6 +120,10 @@ def _update_sequence(name, B, mem):
 @pytest.mark.parametrize("mem", MEMS)
 @pytest.mark.parametrize("name,B", CASES)
 def test_update_against_numpy(name, B, mem):
+    check_update(name, B, mem)
+
+
+def check_update(name, B, mem):
     import torch
     p, steps = _update_sequence(name, B, mem)
     n = p.n
@@ -291,6 +304,10 @@ def _upload(c, it):
 @pytest.mark.parametrize("mem", MEMS)
 @pytest.mark.parametrize("name,B", CASES)
 def test_direction_against_numpy(name, B, mem):
+    check_direction(name, B, mem)
+
+
+def check_direction(name, B, mem):
     import torch
     c = _direction_case(name, B, mem)
     _assert_direction_inputs(c, name, B, mem)

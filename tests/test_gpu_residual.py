@@ -288,6 +288,30 @@ def test_fused_entry_is_bit_identical_for_every_chunk(name, B):
         p.set_products_chunk(0)
 
 
+def test_fused_entry_with_more_than_64k_of_lds():
+    """hyq_gap_torque (m + n > 5632): the J^T lam launch inside the fused entry needs 72,336 bytes of dynamic LDS. Its
+    EELinear set takes its bounds from side data, so the call uploads shared bounds drawn here (a third of the rows
+    lower-only, a third upper-only, the others two-sided)."""
+    import torch
+    B, rho = 2, 1e3
+    p = TowrGpuProblem(config_descs()["hyq_gap_torque"], device=0)
+    ns = p.desc.n_constraints
+    assert p.m + p.n > 5632
+    rng = np.random.default_rng(11)
+    x0 = p.initial_x()
+    Xd = _padded(np.stack([x0 + 0.05 * np.random.default_rng(700 + b).standard_normal(p.n) for b in range(B)]), p.n + 1)
+    LAMd = _padded(rng.standard_normal((B, p.m)), p.m + 9)
+    side = rng.integers(0, 3, p.m)
+    GL, GU = _vec(np.where(side == 1, -1e20, -rng.random(p.m))), _vec(np.where(side == 0, 1e20, rng.random(p.m)))
+    G0, SUM0, LAMP0, Z0 = _separate(p, Xd, ns, LAMd, rho, GL=GL, GU=GU)
+    G, SUM, LAMP, Z = _nan(B, p.m + 2), _nan(B, 4 + ns + 3), _nan(B, p.m + 5), _nan(B, p.n + 3)
+    p.eval_auglag_batch_device(Xd, SUM, Z, GL=GL, GU=GU, LAM=LAMd, rho=rho, G=G, LAMP=LAMP)
+    torch.cuda.synchronize()
+    Zh = Z0.cpu().numpy()
+    assert np.isfinite(Zh[:, :p.n]).all() and (Zh[:, :p.n] != 0).any() and np.isnan(Zh[:, p.n:]).all()
+    assert _same_bits(G, G0) and _same_bits(SUM, SUM0) and _same_bits(LAMP, LAMP0) and _same_bits(Z, Z0)
+
+
 def test_fused_entry_with_per_problem_terrain_and_bounds():
     import torch
     from towr2025_amd import formulation as F
