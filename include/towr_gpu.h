@@ -577,6 +577,130 @@ int towr_gpu_auglag_lbfgs_step_batch_device(towr_gpu_handle h, int32_t B, int32_
                                             double* USUM, int64_t ldus, double* DSUM, int64_t ldds,
                                             double* XP, int64_t ldxp, double* SSUM, int64_t ldss, void* stream);
 
+/* ---- a resident solve loop: line search, multiplier / penalty update and whole iterations on the stream -------- */
+/* The parameters of the loop (host memory, read at the call). TOWR_ERR_INVALID before anything runs for a NaN or
+ * out-of-range field: mem in 1..TOWR_LBFGS_MAX_MEM; max_inner >= 1 (trials per outer iteration before the outer
+ * update is forced); max_outer >= 1; c1 and shrink in (0, 1); alpha0 >= alpha_min > 0; curv_eps >= 0; rho0 > 0,
+ * rho_grow >= 1, rho_max >= rho0; eta0, eta_shrink in (0, 1], eta_star > 0 (the feasibility tolerance schedule);
+ * omega0, omega_shrink in (0, 1], omega_star > 0 (the stationarity tolerance schedule).                          */
+typedef struct {
+  int32_t mem, max_inner, max_outer, reserved;
+  double c1, shrink, alpha0, alpha_min, curv_eps;
+  double rho0, rho_grow, rho_max;
+  double eta0, eta_shrink, eta_star;
+  double omega0, omega_shrink, omega_star;
+} towr_alsolve_params_t;
+
+/* The per-problem state: caller-owned DEVICE memory for B problems; the struct itself is host memory, read at the
+ * call. Row b of a matrix starts at b*ld.
+ *   X, GR, XC, GRC, D (ldx >= n): the base iterate, the augmented Lagrangian's gradient there, the candidate, the
+ *     gradient at the candidate, the direction at the base;
+ *   LAM, LAMP (ldl >= m): the multipliers, lam+ at the candidate;
+ *   HS, HY, ldh, HMETA: the L-BFGS history, as above (`mem` pairs per problem);
+ *   ALPHA, RHO, FC (B doubles each, contiguous): the next trial length, the penalty parameter, f at the candidate;
+ *   SCAL (ldsc >= 8): [0] M0, the merit at the base; [1] pg at the base; [2] eta; [3] omega; [4] the max violation
+ *     at the base; [5] f at the base; [6..7] 0;
+ *   ISTATE (int32_t[4*B]): {phase, flags, inner, outer} per problem;
+ *   RSUM (ldrs), SSUM (ldss), DSUM (ldds), USUM (ldus >= 6), LSUM (ldls >= 8): the summaries of the residual, step,
+ *     direction and update stages (their widths as stated there) and of the line search.
+ * Phases: 0 RESTART (the next evaluation defines the base), 1 SEARCH, 2 CONVERGED, 3 STALLED (the trial length fell
+ * below alpha_min with an empty history), 4 MAXED (max_outer reached). Any other value counts as frozen, like 2..4;
+ * the kernels never index from it. Flags (written by the line search): bit 0 a base was accepted in this iteration,
+ * bit 1 the direction must be recomputed, bit 2 the history was reset.                                           */
+typedef struct {
+  double *X, *GR, *XC, *GRC, *D; int64_t ldx;
+  double *LAM, *LAMP; int64_t ldl;
+  double *HS, *HY; int64_t ldh; int32_t* HMETA;
+  double *ALPHA, *RHO, *FC;
+  double* SCAL; int64_t ldsc;
+  int32_t* ISTATE;
+  double* RSUM; int64_t ldrs;
+  double* SSUM; int64_t ldss;
+  double* DSUM; int64_t ldds;
+  double* USUM; int64_t ldus;
+  double* LSUM; int64_t ldls;
+} towr_alsolve_state_t;
+#define TOWR_AL_RESTART 0
+#define TOWR_AL_SEARCH 1
+#define TOWR_AL_CONVERGED 2
+#define TOWR_AL_STALLED 3
+#define TOWR_AL_MAXED 4
+
+/* The line search: keeps or rejects the candidate XC of every problem, behind an evaluation that left FC, GRC and
+ * RSUM ([0] max violation, [3] phi). MC = FC[b] + RSUM[b][3], one rounded addition. By the phase read at entry:
+ *   frozen (>= 2 or invalid): flags = 0, LSUM[0] = 0; no other byte of the problem changes (LSUM[1..7] included).
+ *   RESTART: X <- XC, GR <- GRC, SCAL[0] = MC, SCAL[4] = RSUM[b][0], SCAL[5] = FC[b], HMETA = {0, 0},
+ *     ALPHA[b] = alpha0, phase = SEARCH, flags = 1|2|4, inner += 1, LSUM[0] = 1. No pair is offered.
+ *   SEARCH: s = XC - X (one rounded subtraction per column), gs = sum_j GR_j s_j. Accepted iff gs <= 0 and
+ *     MC <= M0 + c1*gs (a rounded product, a rounded addition; a NaN anywhere makes the test false).
+ *     accepted: the pair (XC - X, GRC - GR) is offered exactly as towr_gpu_lbfgs_update_batch_device offers it (the
+ *       same sums on the same tree, the same test sy > curv_eps*yy, the same slot rules: HS, HY and HMETA end up
+ *       bit for bit as that call leaves them; its six summary values go to USUM); then the base is updated as in
+ *       RESTART, except that HMETA keeps what the offer left; flags = 1|2, inner += 1, LSUM[0] = 2.
+ *     rejected: a = ALPHA[b]*shrink. a >= alpha_min: ALPHA[b] = a, flags = 0, LSUM[0] = 3 (X, GR, D and the history
+ *       untouched). Else, with a pair in the history: HMETA = {0, 0}, ALPHA[b] = alpha0, flags = 2|4, LSUM[0] = 4
+ *       (the next direction is GR bit for bit). Else: phase = STALLED, ALPHA[b] = 0, flags = 0, LSUM[0] = 5.
+ *       inner += 1 in each case. USUM is not written.
+ * When a base was accepted, SCAL[1] = pg = max_j |clamp(x_j - g_j) - x_j| over the new base: the expression of
+ * towr_gpu_step_batch_device with a = 1 (sides count within +-1e19), an integer maximum of the bit patterns, NaN on
+ * top. XL, XU, ldb as there (NULL: the handle's; ldb = 0: one shared row).
+ * LSUM[1..7] (every phase but frozen) = gs, MC, the M0 before, sy, yy, pair stored 1 / 0, pg (gs, sy and yy are 0
+ * at a RESTART; pg is SCAL[1] after the call). Fixed-tree sums, decisions on broadcast scalars: problem b's outputs
+ * are a function of its own operands alone. Nothing beyond n (rows), 8 (SCAL, LSUM), 6 (USUM) is read or written;
+ * of RSUM only [0] and [3] are read. Fields used: X, GR, XC, GRC, ldx, HS, HY, ldh, HMETA, ALPHA, FC, SCAL, ISTATE,
+ * RSUM, USUM, LSUM. No handle scratch; the kept Jacobian is not dropped. TOWR_ERR_INVALID before anything runs
+ * for: NULL params or state, an invalid params field, a NULL used field, ldx / ldh < n, ldsc < 8, ldrs < 4,
+ * ldus < 6, ldls < 8, only one of XL / XU, 0 < ldxb < n. TOWR_ERR_UNSUPPORTED as for the L-BFGS update.          */
+int towr_gpu_linesearch_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                     const towr_alsolve_state_t* state, const double* XL, const double* XU,
+                                     int64_t ldxb, void* stream);
+
+/* The outer update. It acts on problem b only if phase == SEARCH, flag bit 0 is set and (pg <= omega or
+ * inner >= max_inner), with pg = SCAL[1], omega = SCAL[3]; otherwise not one byte of the problem changes. With
+ * viol = SCAL[4], eta = SCAL[2]:
+ *   viol <= eta and viol <= eta_star and pg <= omega_star: phase = CONVERGED, ALPHA[b] = 0, flags = 0;
+ *   else viol <= eta: LAM <- LAMP (m values), eta = max(eta*eta_shrink, eta_star),
+ *     omega = max(omega*omega_shrink, omega_star) (t = the rounded product; t > star ? t : star);
+ *   else (also a NaN viol): RHO[b] = min(RHO[b]*rho_grow, rho_max) (t < rho_max ? t : rho_max); LAM, eta and omega
+ *     unchanged;
+ *   in the two non-converged cases: outer += 1, inner = 0, HMETA = {0, 0}, ALPHA[b] = 0, flags = 0, phase = MAXED
+ *     if outer >= max_outer, else RESTART. With ALPHA[b] = 0 the next step gives XC = X and the next evaluation
+ *     defines M0 and GR for the new lam / rho.
+ * Everything is a copy, one rounded product or a comparison. Fields used: LAM, LAMP, ldl, HMETA, ALPHA, RHO, SCAL,
+ * ISTATE. TOWR_ERR_INVALID before anything runs for: NULL params or state, an invalid params field, a NULL used
+ * field, ldl < m, ldsc < 8.                                                                                      */
+int towr_gpu_auglag_outer_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                       const towr_alsolve_state_t* state, void* stream);
+
+/* Starts a solve: ISTATE = {RESTART, 0, 0, 0}, HMETA = 0, RHO = rho0, ALPHA = 0, SCAL = {0, 0, eta0, omega0, 0, 0,
+ * 0, 0}, XC = the caller's X clamped to the sides of (XL, XU) that count, D = 0 (the first step runs with
+ * ALPHA = 0 and must not meet a NaN there). LAM holds the caller's starting multipliers and is not touched.
+ * Fields used: X, XC, D, ldx, HMETA, ALPHA, RHO, SCAL, ISTATE. Checks as towr_gpu_alsolve_iterate_batch_device's. */
+int towr_gpu_alsolve_init_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                       const towr_alsolve_state_t* state, const double* XL, const double* XU,
+                                       int64_t ldxb, void* stream);
+
+/* `iters` complete iterations on `stream`, with no host synchronisation. One iteration:
+ *   1. towr_gpu_eval_cost_batch_device at XC, F = FC and GRAD = GRC;
+ *   2. towr_gpu_eval_auglag_batch_device at XC with LAM and problem b's own rho = RHO[b], accumulated onto GRC; its
+ *      LAMP and SUM are LAMP and RSUM (g stays in handle scratch);
+ *   3. towr_gpu_linesearch_batch_device;
+ *   4. towr_gpu_auglag_outer_batch_device;
+ *   5. towr_gpu_lbfgs_direction_batch_device at (X, GR) into D, DSUM its SUM — only for the problems whose flag bit 1
+ *      is set; the D and DSUM rows of the others are untouched (a rejected trial keeps its direction);
+ *   6. towr_gpu_step_batch_device, XC = P(X - ALPHA D), SSUM its SUM.
+ * Bit-identical to those calls in sequence (step 2 as B = 1 calls with the scalar rho = RHO[b] where the RHO differ),
+ * whatever the products chunk. The batch is not compacted: a frozen problem is still evaluated in every iteration
+ * (its ALPHA is 0, so XC = X), but its X, GR, LAM, RHO, SCAL, ISTATE and history never change again. Batch terrains,
+ * the cross-stream scratch rule and the kept Jacobian as for towr_gpu_eval_products_batch_device. Every field of
+ * `state` is used. TOWR_ERR_INVALID before anything runs for: iters < 0, what the two calls above refuse, a NULL
+ * field, ldrs < 4 + n_constraints, ldss < 5 + n_varsets, ldds < 5, only one of GL / GU, 0 < ldgb < m, bounds the
+ * description cannot give (GL NULL). TOWR_ERR_UNSUPPORTED as for the L-BFGS kernels.                             */
+int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters,
+                                          const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                          const double* GL, const double* GU, int64_t ldgb,
+                                          const double* XL, const double* XU, int64_t ldxb, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

@@ -16,6 +16,13 @@
       pass were served by a cache);
   (o) auglag_lbfgs_step_batch_device (one inner iteration, mem = MEM) beside the sum of its parts from the same
       session (cost gradient + g auglag + j + l + h) and the share of j + l in it,
+  (q) linesearch_batch_device with every problem in SEARCH, its base accepted and its pair stored: rate = 8 (10 n + 30) B /
+      time — X, XC, GR, GRC read, the slot of HS and HY written, XC and GRC read again and X, GR written, the scalars —
+      beside (r) a copy of the same bytes. The call consumes its operands (X <- XC), so every call is preceded by two
+      device copies that restore X and GR; (q0) times those alone and q - q0 is printed;
+  (s) auglag_outer_batch_device with every problem's multipliers updated (LAM <- LAMP, 16 m B bytes; ISTATE restored
+      before every call: (s0) times that copy alone and s - s0 is printed) beside (u) a copy of the same bytes;
+  (t) alsolve_iterate(iters = 1) in a running solve from X (mem = MEM), beside row (o) + (q - q0) + s,
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -29,7 +36,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from towr2025_amd import TowrGpuProblem, _capi as capi  # noqa: E402
+from towr2025_amd import AlSolveState, TowrGpuProblem, _capi as capi, alsolve_params  # noqa: E402
 from towr2025_amd import formulation as F  # noqa: E402
 
 REPS = int(os.environ.get("REPS", "20"))
@@ -104,6 +111,47 @@ def run(name, f, B):
         a = torch.randn(nb // 16, dtype=torch.float64, device=dev)
         copies[key] = (a, torch.empty_like(a))
 
+    # the resident loop: (q) a state whose every problem accepts and stores its pair (MC = -1e300 <= M0 + c1 gs whenever
+    # gs <= 0; XC = X - 0.01 GR), X and GR restored before every call; (s) every problem forced into the multiplier
+    # update; (t) a running solve of its own
+    par = alsolve_params(mem=mem, shrink=0.1, curv_eps=1e-14, alpha_min=1e-16, max_inner=5)
+    sq = AlSolveState.allocate(p, B, mem)
+    Xq, GRq = Xs[:, :p.n].contiguous(), GR[:, :p.n].contiguous()
+    sq.XC.copy_(Xq - 0.01 * GRq)
+    sq.GRC.copy_(GRq + 1.3 * (sq.XC - Xq))
+    sq.HS.copy_(HS[:, :p.n]); sq.HY.copy_(HY[:, :p.n]); sq.HMETA.copy_(HMETA.flatten())
+    sq.FC.fill_(-1e300); sq.ALPHA.fill_(1.0); sq.RHO.fill_(rho)
+    sq.SCAL[:, 0] = 1e300
+    sq.ISTATE.copy_(torch.tensor([[1, 0, 0, 0]] * B, dtype=torch.int32, device=dev).flatten())
+    IS_outer = torch.tensor([[1, 1, 5, 0]] * B, dtype=torch.int32, device=dev).flatten()
+    so = AlSolveState.allocate(p, B, mem)
+    so.LAMP.copy_(LAM[:, :p.m]); so.RHO.fill_(rho)
+    so.SCAL.copy_(torch.tensor([[0.0, 0.5, 0.1, 0.1, 0.0, 0.0, 0.0, 0.0]] * B, dtype=torch.float64, device=dev))
+    stt = AlSolveState.allocate(p, B, mem)
+    stt.X.copy_(Xs[:, :p.n])
+    part = alsolve_params(mem=mem, shrink=0.1, curv_eps=1e-14, alpha_min=1e-16, max_inner=100, max_outer=1000)
+    p.alsolve_init(part, stt, stream=stream)
+    codes = []
+    bytes_ls = 8 * (10 * p.n + 30) * B
+    bytes_out = 8 * 2 * p.m * B
+    for key, nb in (("r", bytes_ls), ("u", bytes_out)):
+        a = torch.randn(nb // 16, dtype=torch.float64, device=dev)
+        copies[key] = (a, torch.empty_like(a))
+
+    # the three calls go to the C-ABI directly with their state structs built once: the Python methods' operand checks
+    # (some 20 tensors per call) would otherwise be what a 40 us kernel is timed against
+    import ctypes as C
+    sp = C.c_void_p(stream.cuda_stream)
+    cq, co, ct = p._alsolve_state(sq, par), p._alsolve_state(so, par), p._alsolve_state(stt, part)
+    ls_call = lambda: p._check(p._lib.towr_gpu_linesearch_batch_device(p._h, B, C.byref(par), C.byref(cq), None, None, 0, sp))
+    outer_call = lambda: p._check(p._lib.towr_gpu_auglag_outer_batch_device(p._h, B, C.byref(par), C.byref(co), sp))
+    iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_iterate_batch_device(p._h, B, 1, C.byref(part), C.byref(ct), None, None, 0,
+                                                                              None, None, 0, sp))
+
+    def restore_q():
+        sq.X.copy_(Xq)
+        sq.GR.copy_(GRq)
+
     def fused(chunk):
         def f():
             p.set_products_chunk(chunk)
@@ -128,7 +176,15 @@ def run(name, f, B):
                 ("p cost gradient", lambda: p.eval_cost_batch_device(Xs, Fv, GRAD=GRo, stream=stream)),
                 (f"o auglag lbfgs step mem={mem}", lambda: (p.set_products_chunk(0), p.auglag_lbfgs_step_batch_device(
                     XN2, GRo, XP, SSUM, RSUM, DSUM, HS2, HY2, HMETA2, mem, XPREV=Xs, GRPREV=GRP, USUM=USUM2, LAM=LAM, rho=rho,
-                    alpha=1e-6, F=Fv, stream=stream)))]
+                    alpha=1e-6, F=Fv, stream=stream))),
+                ("q linesearch + restore", lambda: (restore_q(), ls_call())),
+                ("q0 restore alone", restore_q),
+                ("r copy, linesearch's bytes", lambda: copies["r"][1].copy_(copies["r"][0])),
+                ("s outer (lam update)", lambda: (so.ISTATE.copy_(IS_outer), outer_call())),
+                ("s0 ISTATE restore alone", lambda: so.ISTATE.copy_(IS_outer)),
+                ("u copy, outer's bytes", lambda: copies["u"][1].copy_(copies["u"][0])),
+                (f"t alsolve iterate mem={mem}", lambda: (p.set_products_chunk(0), iter_call(),
+                                                         codes.append(stt.LSUM[:, 0].clone())))]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
         for _ in range(3):
             fn()
@@ -149,7 +205,8 @@ def run(name, f, B):
         t = times[k]
         med = statistics.median(t)
         nbytes = (bytes_prod if k[0] in "bc" else bytes_res if k[0] in "ef" else bytes_step if k[0] in "hi" else
-                  bytes_upd if k[0] in "jk" else bytes_dir if k[0] in "lm" else bytes_dir1 if k[0] == "n" else 0)
+                  bytes_upd if k[0] in "jk" else bytes_dir if k[0] in "lm" else bytes_dir1 if k[0] == "n" else
+                  bytes_ls if k[:2] in ("q ", "r ") else bytes_out if k[0] in "su" else 0)
         rate = f"  {nbytes / (med * 1e-3) / 1e12:.2f} TB/s = {100 * nbytes / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if nbytes else ""
         print(f"  {k:22s} {med:.4f} ms  (min {min(t):.4f} max {max(t):.4f}){rate}", flush=True)
     parts = sum(statistics.median(times[k]) for k in ("a eval_batch_device", "e residual", "c jac_tvec"))
@@ -162,6 +219,17 @@ def run(name, f, B):
           f"update + direction {med['j'] + med['l']:.4f} ms = {100 * (med['j'] + med['l']) / med['o']:.1f} % of the fused iteration; "
           f"accepted: update {USUM[:, 3].mean().item():.2f}, fused {USUM2[:, 3].mean().item():.2f}; pairs used: direction "
           f"{DSUM[:, 0].mean().item():.2f}", flush=True)
+    mq = {k.split()[0]: statistics.median(times[k]) for k, _ in variants if k.split()[0] in ("q", "q0", "r", "s", "s0", "u", "t")}
+    ls = mq["q"] - mq["q0"]
+    mq["s"] -= mq["s0"]
+    so.ISTATE.copy_(IS_outer)
+    outer_call()   # (the phases printed below are an outer update's)
+    hist = torch.bincount(torch.stack(codes).flatten().to(torch.int64), minlength=6).tolist()
+    print(f"  linesearch bytes {bytes_ls / 1e9:.3f} GB: q - q0 {ls:.4f} ms = {bytes_ls / (ls * 1e-3) / 1e12:.2f} TB/s, copy / (q - q0) "
+          f"{mq['r'] / ls:.2f}; stored {sq.LSUM[:, 6].mean().item():.2f}; outer: s - s0 {mq['s']:.4f} ms, copy / (s - s0) {mq['u'] / mq['s']:.2f}, phases after "
+          f"{torch.bincount(so.ISTATE.view(B, 4)[:, 0].to(torch.int64), minlength=5).tolist()}; iteration t {mq['t']:.4f} ms vs "
+          f"o + (q - q0) + (s - s0) {med['o'] + ls + mq['s']:.4f} ms, ratio {mq['t'] / (med['o'] + ls + mq['s']):.3f}; LSUM[0] codes 0..5 over the "
+          f"timed iterations {hist}", flush=True)
     p.set_products_chunk(0)
 
 

@@ -76,6 +76,28 @@ MAX_COSTS = 128
 LBFGS_MAX_MEM = 16   # TOWR_LBFGS_MAX_MEM
 
 
+AL_RESTART, AL_SEARCH, AL_CONVERGED, AL_STALLED, AL_MAXED = range(5)   # TOWR_AL_*: the phases of the resident loop
+
+
+class AlSolveParams(C.Structure):   # towr_alsolve_params_t
+    _fields_ = [("mem", C.c_int32), ("max_inner", C.c_int32), ("max_outer", C.c_int32), ("reserved", C.c_int32),
+                ("c1", C.c_double), ("shrink", C.c_double), ("alpha0", C.c_double), ("alpha_min", C.c_double),
+                ("curv_eps", C.c_double), ("rho0", C.c_double), ("rho_grow", C.c_double), ("rho_max", C.c_double),
+                ("eta0", C.c_double), ("eta_shrink", C.c_double), ("eta_star", C.c_double),
+                ("omega0", C.c_double), ("omega_shrink", C.c_double), ("omega_star", C.c_double)]
+
+
+class AlSolveStateC(C.Structure):   # towr_alsolve_state_t
+    _fields_ = [("X", C.c_void_p), ("GR", C.c_void_p), ("XC", C.c_void_p), ("GRC", C.c_void_p), ("D", C.c_void_p),
+                ("ldx", C.c_int64), ("LAM", C.c_void_p), ("LAMP", C.c_void_p), ("ldl", C.c_int64),
+                ("HS", C.c_void_p), ("HY", C.c_void_p), ("ldh", C.c_int64), ("HMETA", C.c_void_p),
+                ("ALPHA", C.c_void_p), ("RHO", C.c_void_p), ("FC", C.c_void_p),
+                ("SCAL", C.c_void_p), ("ldsc", C.c_int64), ("ISTATE", C.c_void_p),
+                ("RSUM", C.c_void_p), ("ldrs", C.c_int64), ("SSUM", C.c_void_p), ("ldss", C.c_int64),
+                ("DSUM", C.c_void_p), ("ldds", C.c_int64), ("USUM", C.c_void_p), ("ldus", C.c_int64),
+                ("LSUM", C.c_void_p), ("ldls", C.c_int64)]
+
+
 class CostDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("ee", C.c_int32), ("weight", C.c_double), ("dt", C.c_double),
                 ("p", C.c_double * 4), ("ip", C.c_int32 * 4)]
@@ -187,6 +209,15 @@ SYMBOLS = {
                                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_linesearch_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(AlSolveParams), C.POINTER(AlSolveStateC),
+                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_auglag_outer_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(AlSolveParams), C.POINTER(AlSolveStateC),
+                                                      C.c_void_p]),
+    "towr_gpu_alsolve_init_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(AlSolveParams), C.POINTER(AlSolveStateC),
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_alsolve_iterate_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.POINTER(AlSolveParams),
+                                                         C.POINTER(AlSolveStateC), C.c_void_p, C.c_void_p, C.c_int64,
+                                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

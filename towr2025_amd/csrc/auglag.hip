@@ -140,7 +140,7 @@ int residual_args(towr_gpu_handle h, const ResArgs& a, bool lamp) {
   if (a.lds < 4 + (int64_t)L.cons.size()) return fail(h, TOWR_ERR_INVALID, "lds smaller than 4 + n_constraints");
   if (int rc = box_args(h, a.GL, a.GU, a.ldb, L.m, "GL / GU", "m")) return rc;
   if (!a.GL && !L.bounds_err.empty()) return fail(h, TOWR_ERR_INVALID, L.bounds_err);
-  if (lamp && !(a.rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 with LAMP");
+  if (lamp && !a.RHO && !(a.rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 with LAMP");
   if (a.LAMP && a.ldlp < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAMP smaller than m");
   if (lamp && a.LAM && a.ldl < L.m) return fail(h, TOWR_ERR_INVALID, "leading dimension of LAM smaller than m");
   return TOWR_OK;
@@ -174,6 +174,56 @@ int lbfgs_fits(towr_gpu_handle h) {
   return TOWR_OK;
 }
 
+// ---- the resident loop's parameters and state (towr_alsolve_params_t / towr_alsolve_state_t) ---------------------------
+int alsolve_params(towr_gpu_handle h, const towr_alsolve_params_t* p) {
+  if (!p) return fail(h, TOWR_ERR_INVALID, "null params");
+  auto in01 = [](double v) { return v > 0 && v < 1; };     // (a NaN fails every test below)
+  auto in0c1 = [](double v) { return v > 0 && v <= 1; };
+  if (p->mem < 1 || p->mem > TOWR_LBFGS_MAX_MEM) return fail(h, TOWR_ERR_INVALID, "params: mem outside 1..TOWR_LBFGS_MAX_MEM");
+  if (p->max_inner < 1 || p->max_outer < 1) return fail(h, TOWR_ERR_INVALID, "params: max_inner and max_outer must be >= 1");
+  if (!in01(p->c1) || !in01(p->shrink)) return fail(h, TOWR_ERR_INVALID, "params: c1 and shrink must lie in (0, 1)");
+  if (!(p->alpha_min > 0) || !(p->alpha0 >= p->alpha_min)) return fail(h, TOWR_ERR_INVALID, "params: alpha0 >= alpha_min > 0 required");
+  if (!(p->curv_eps >= 0)) return fail(h, TOWR_ERR_INVALID, "params: curv_eps is negative or NaN");
+  if (!(p->rho0 > 0) || !(p->rho_grow >= 1) || !(p->rho_max >= p->rho0))
+    return fail(h, TOWR_ERR_INVALID, "params: rho0 > 0, rho_grow >= 1 and rho_max >= rho0 required");
+  if (!in0c1(p->eta0) || !in0c1(p->eta_shrink) || !(p->eta_star > 0))
+    return fail(h, TOWR_ERR_INVALID, "params: eta0 and eta_shrink in (0, 1] and eta_star > 0 required");
+  if (!in0c1(p->omega0) || !in0c1(p->omega_shrink) || !(p->omega_star > 0))
+    return fail(h, TOWR_ERR_INVALID, "params: omega0 and omega_shrink in (0, 1] and omega_star > 0 required");
+  return TOWR_OK;
+}
+
+// the state fields an entry uses: kAlLs the line search's, kAlOuter the outer update's, kAlInit the initialisation's;
+// the iteration uses every field
+enum : unsigned { kAlLs = 1, kAlOuter = 2, kAlInit = 4, kAlAll = 8 };
+int alsolve_state(towr_gpu_handle h, const towr_alsolve_state_t* s, unsigned use) {
+  if (!s) return fail(h, TOWR_ERR_INVALID, "null state");
+  const Layout& L = h->L;
+  const bool all = use & kAlAll, ls = all || (use & kAlLs), ou = all || (use & kAlOuter), in = all || (use & kAlInit);
+  if (!s->ISTATE || !s->SCAL || !s->HMETA || !s->ALPHA) return fail(h, TOWR_ERR_INVALID, "state: null ISTATE, SCAL, HMETA or ALPHA");
+  if (s->ldsc < 8) return fail(h, TOWR_ERR_INVALID, "state: ldsc smaller than 8");
+  if ((ls || in) && (!s->X || !s->XC)) return fail(h, TOWR_ERR_INVALID, "state: null X or XC");
+  if (ls && (!s->GR || !s->GRC)) return fail(h, TOWR_ERR_INVALID, "state: null GR or GRC");
+  if ((in || all) && !s->D) return fail(h, TOWR_ERR_INVALID, "state: null D");
+  if ((ls || in) && s->ldx < L.n) return fail(h, TOWR_ERR_INVALID, "state: ldx smaller than n");
+  if ((ou || in) && !s->RHO) return fail(h, TOWR_ERR_INVALID, "state: null RHO");
+  if (ou && (!s->LAM || !s->LAMP)) return fail(h, TOWR_ERR_INVALID, "state: null LAM or LAMP");
+  if (ou && s->ldl < L.m) return fail(h, TOWR_ERR_INVALID, "state: ldl smaller than m");
+  if (ls) {
+    if (!s->HS || !s->HY) return fail(h, TOWR_ERR_INVALID, "state: null HS or HY");
+    if (s->ldh < L.n) return fail(h, TOWR_ERR_INVALID, "state: ldh smaller than n");
+    if (!s->FC || !s->RSUM || !s->USUM || !s->LSUM) return fail(h, TOWR_ERR_INVALID, "state: null FC, RSUM, USUM or LSUM");
+    if (s->ldrs < 4 || s->ldus < 6 || s->ldls < 8) return fail(h, TOWR_ERR_INVALID, "state: ldrs < 4, ldus < 6 or ldls < 8");
+  }
+  if (all) {
+    if (!s->SSUM || !s->DSUM) return fail(h, TOWR_ERR_INVALID, "state: null SSUM or DSUM");
+    if (s->ldrs < 4 + (int64_t)L.cons.size()) return fail(h, TOWR_ERR_INVALID, "state: ldrs smaller than 4 + n_constraints");
+    if (s->ldss < 5 + (int64_t)L.varsets.size()) return fail(h, TOWR_ERR_INVALID, "state: ldss smaller than 5 + n_varsets");
+    if (s->ldds < 5) return fail(h, TOWR_ERR_INVALID, "state: ldds smaller than 5");
+  }
+  return TOWR_OK;
+}
+
 // ---- launchers: one block per problem; the caller's operands in `a`, the handle's tables and sizes added here ----------
 // one product's operands: Y = J p (Vec = P, Out = Y) or Z (+)= J^T lam (Vec = LAM, Out = Z)
 JpArgs product(const double* V, int64_t ldv, const double* vec, int64_t ldvec, double* out, int64_t ldo, int accumulate) {
@@ -194,7 +244,7 @@ int launch_product(towr_gpu_handle h, bool tvec, int B, const JpArgs& call, hipS
 // (GL NULL: the handle's bounds, one row; without LAMP only the violation summary: LAM and rho are not used)
 int launch_residual(towr_gpu_handle h, int B, ResArgs a, hipStream_t s) {
   if (!a.GL) { a.GL = h->al.d_blo; a.GU = h->al.d_bup; a.ldb = 0; }
-  if (!a.LAMP) { a.LAM = nullptr; a.rho = 1.0; }
+  if (!a.LAMP) { a.LAM = nullptr; a.rho = 1.0; a.RHO = nullptr; }
   a.set_row0 = h->al.d_set_row0; a.m = h->L.m; a.n_sets = (int32_t)h->L.cons.size();
   void* args[] = {&a};
   HIPCHK(h, launch_kernel(res_kernel(), dim3((unsigned)B), dim3(kResBlock), args, 0, s));
@@ -223,6 +273,23 @@ int launch_lbfgs_direction(towr_gpu_handle h, int B, LbfgsDirArgs a, hipStream_t
   a.n = h->L.n;
   void* args[] = {&a};
   HIPCHK(h, launch_kernel(lbfgs_direction_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_direction_lds(a.n), s));
+  return TOWR_OK;
+}
+
+// (XL NULL: the handle's bounds, one row — after step_ready)
+int launch_linesearch(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const towr_alsolve_state_t& st, const double* XL,
+                      const double* XU, int64_t ldb, hipStream_t s) {
+  LineSearchArgs a{st, XL, XU, ldb, p.c1, p.shrink, p.alpha0, p.alpha_min, p.curv_eps, h->L.n, p.mem};
+  if (!a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(linesearch_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, (size_t)lbfgs_update_lds(a.n), s));
+  return TOWR_OK;
+}
+
+int launch_outer(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const towr_alsolve_state_t& st, hipStream_t s) {
+  OuterArgs a{st, p, h->L.m};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_outer_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, s));
   return TOWR_OK;
 }
 
@@ -275,6 +342,7 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
     if (r.LAMP) a.LAMP = r.LAMP + (int64_t)c0 * r.ldlp; else { a.LAMP = al.d_rl; a.ldlp = ldr; }
     a.GL = row_at(r.GL, c0, r.ldb); a.GU = row_at(r.GU, c0, r.ldb); a.LAM = row_at(r.LAM, c0, r.ldl);
     a.SUM = r.SUM + (int64_t)c0 * r.lds;
+    a.RHO = row_at(r.RHO, c0, 1);
     rc = launch(h, cb, e.X + (int64_t)c0 * e.ldx, e.ldx, g, a.ldg, al.d_pv, ldv, 1, 1, b.s, b.terrain_at(c0), b.per, -1);
     if (rc == TOWR_OK) rc = launch_residual(h, cb, a, b.s);
     if (rc == TOWR_OK)
@@ -520,6 +588,94 @@ int towr_gpu_auglag_lbfgs_step_batch_device(towr_gpu_handle h, int32_t B, int32_
     if (rc == TOWR_OK) rc = launch_lbfgs_direction(h, B, dir, b.s);
     st.D = al.d_sd; st.ldd = ldn;
     if (rc == TOWR_OK) rc = launch_step(h, B, st, b.s);
+    return rc;
+  });
+}
+
+// ---- the resident loop (lbfgs.hip: the line search, the outer update, the initialisation) ---------------------------
+int towr_gpu_linesearch_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                     const towr_alsolve_state_t* state, const double* XL, const double* XU, int64_t ldxb,
+                                     void* stream) {
+  if (!h || B < 0) return fail(h, TOWR_ERR_INVALID, "bad argument (B < 0)");
+  if (int rc = alsolve_params(h, params)) return rc;
+  if (int rc = alsolve_state(h, state, kAlLs)) return rc;
+  if (int rc = box_args(h, XL, XU, ldxb, h->L.n, "XL / XU", "n")) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (!XL)
+    if (int rc = step_ready(h)) return rc;
+  return launch_linesearch(h, B, *params, *state, XL, XU, ldxb, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_auglag_outer_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                       const towr_alsolve_state_t* state, void* stream) {
+  if (!h || B < 0) return fail(h, TOWR_ERR_INVALID, "bad argument (B < 0)");
+  if (int rc = alsolve_params(h, params)) return rc;
+  if (int rc = alsolve_state(h, state, kAlOuter)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  return launch_outer(h, B, *params, *state, reinterpret_cast<hipStream_t>(stream));
+}
+
+// what the iteration refuses (the initialisation answers the same arguments, so a loop fails at its first call)
+static int alsolve_args(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                        const double* GL, const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb) {
+  if (!h || B < 0) return fail(h, TOWR_ERR_INVALID, "bad argument (B < 0)");
+  if (int rc = alsolve_params(h, params)) return rc;
+  if (int rc = alsolve_state(h, state, kAlAll)) return rc;
+  if (int rc = box_args(h, GL, GU, ldgb, h->L.m, "GL / GU", "m")) return rc;
+  if (!GL && !h->L.bounds_err.empty()) return fail(h, TOWR_ERR_INVALID, h->L.bounds_err);
+  return box_args(h, XL, XU, ldxb, h->L.n, "XL / XU", "n");
+}
+
+int towr_gpu_alsolve_init_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                       const towr_alsolve_state_t* state, const double* XL, const double* XU, int64_t ldxb,
+                                       void* stream) {
+  if (int rc = alsolve_args(h, B, params, state, nullptr, nullptr, 0, XL, XU, ldxb)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (!XL)
+    if (int rc = step_ready(h)) return rc;
+  AlInitArgs a{*state, XL, XU, ldxb, params->rho0, params->eta0, params->omega0, h->L.n};
+  if (!a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_init_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, reinterpret_cast<hipStream_t>(stream)));
+  return TOWR_OK;
+}
+
+// Per iteration what the six public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag
+// chunks with the per-problem RHO accumulated onto GRC (g in handle scratch), the line search, the outer update, the
+// direction of the problems whose flag bit 1 is set (RUN = the flags) and the step.
+int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                          const towr_alsolve_state_t* state, const double* GL, const double* GU, int64_t ldgb,
+                                          const double* XL, const double* XU, int64_t ldxb, void* stream) {
+  if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
+  if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
+  const towr_alsolve_state_t& st = *state;
+  ResArgs r{nullptr, 0, GL, GU, ldgb, st.LAM, st.ldl, st.LAMP, st.ldl, st.RSUM, st.ldrs};
+  r.rho = 1.0;
+  r.RHO = st.RHO;
+  LbfgsDirArgs dir{st.X, st.ldx, st.GR, st.ldx, XL, XU, ldxb, st.HS, st.HY, st.ldh, st.HMETA, st.D, st.ldx, st.DSUM, st.ldds, 0,
+                   params->mem};
+  dir.RUN = st.ISTATE + 1;
+  dir.run_stride = 4;
+  const StepArgs step{st.X, st.ldx, st.D, st.ldx, st.ALPHA, 0.0, XL, XU, ldxb, st.XC, st.ldx, st.SSUM, st.ldss};
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (iters == 0) return TOWR_OK;
+  return fused(h, B, stream, {products_ready, residual_ready, step_ready}, [&](const Batch& b) {
+    int rc = TOWR_OK;
+    for (int it = 0; it < iters && rc == TOWR_OK; ++it) {
+      rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
+      if (rc == TOWR_OK)
+        rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b);
+      if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
+      if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
+      if (rc == TOWR_OK) rc = launch_lbfgs_direction(h, B, dir, b.s);
+      if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
+    }
     return rc;
   });
 }

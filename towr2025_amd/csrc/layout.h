@@ -242,6 +242,7 @@ struct ResArgs {
   const int32_t* set_row0;   // n_sets + 1
   double rho;
   int32_t m, n_sets;
+  const double* RHO;         // internal: one rho per problem (RHO[b]) instead of the scalar; NULL in every public entry
 };
 const void* res_kernel();
 
@@ -289,9 +290,36 @@ struct LbfgsDirArgs {
   double* D; int64_t ldd;
   double* SUM; int64_t lds;
   int32_t n, mem;
+  const int32_t* RUN; int64_t run_stride;   // internal: a block whose RUN[b*run_stride] & 2 is zero returns at once (D and
+                                            // SUM rows untouched); NULL in every public entry
 };
 const void* lbfgs_update_kernel();
 const void* lbfgs_direction_kernel();
+
+// The resident AL loop's kernels (towr_gpu.h, towr_alsolve_state_t; all in lbfgs.hip): the line search (it offers the
+// accepted pair with the update kernel's own device code and needs its lbfgs_update_lds(n) bytes), the outer update and
+// the state initialisation; one block of kLbfgsBlock threads per problem. XL / XU / ldb as in StepArgs.
+enum AlPhase : int32_t { kAlRestart = 0, kAlSearch = 1, kAlConverged = 2, kAlStalled = 3, kAlMaxed = 4 };
+struct LineSearchArgs {
+  towr_alsolve_state_t st;
+  const double *XL, *XU; int64_t ldb;
+  double c1, shrink, alpha0, alpha_min, curv_eps;
+  int32_t n, mem;
+};
+struct OuterArgs {
+  towr_alsolve_state_t st;
+  towr_alsolve_params_t pr;
+  int32_t m;
+};
+struct AlInitArgs {
+  towr_alsolve_state_t st;
+  const double *XL, *XU; int64_t ldb;
+  double rho0, eta0, omega0;
+  int32_t n;
+};
+const void* linesearch_kernel();
+const void* alsolve_outer_kernel();
+const void* alsolve_init_kernel();
 
 struct Layout {
   int n = 0, m = 0;

@@ -1,5 +1,6 @@
 // lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
-// and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device).
+// and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device); and the kernels of the
+// resident AL loop built on them (the line search, the outer update, the state's initialisation; at the end).
 //
 // The shape of resid.hip and step.hip. One block of kLbfgsBlock threads per problem. Lane l takes columns l,
 // l + kLbfgsBlock, ... in ascending order in every pass, so a column belongs to one lane for the whole kernel: the
@@ -106,6 +107,159 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_update_kernel(LbfgsUpd
   }
 }
 
+// The line search of the resident AL loop (towr_gpu.h): the update kernel's pass with one more sum (gs = sum GR s), the
+// accept test on the broadcast sums, the pair offered from LDS as above, then — when a base is accepted — one pass
+// that copies XC / GRC over X / GR and takes pg on the new base. The phase, the meta and the scalars are read by every
+// lane at entry; lane 0 writes them behind the last barrier of the path taken.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_linesearch_kernel(LineSearchArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_dyn[];
+  __shared__ double s_part[4][kLbfgsWaves], s_bc[4];
+  __shared__ unsigned long long s_pg[kLbfgsWaves];
+  const towr_alsolve_state_t& st = a.st;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int n = a.n, mem = a.mem;
+  int32_t* IS = st.ISTATE + 4 * b;
+  double* Lb = st.LSUM + b * st.ldls;
+  const int phase = IS[0];
+  if (phase != kAlRestart && phase != kAlSearch) {   // frozen (or garbage): nothing but the flags and the code
+    if (tid == 0) {
+      IS[1] = 0;
+      Lb[0] = 0.0;
+    }
+    return;
+  }
+  double* s_s = s_dyn;
+  double* s_y = s_dyn + n;
+  double* Xb = st.X + b * st.ldx;
+  double* Gb = st.GR + b * st.ldx;
+  const double* XCb = st.XC + b * st.ldx;
+  const double* GCb = st.GRC + b * st.ldx;
+  double* Sc = st.SCAL + b * st.ldsc;
+  int count = st.HMETA[2 * b], next = st.HMETA[2 * b + 1];
+  if (count < 0 || count > mem || next < 0 || next >= mem) count = next = 0;
+  const int inner = IS[2];
+  const double fc = st.FC[b], viol = st.RSUM[b * st.ldrs];
+  const double mc = fc + st.RSUM[b * st.ldrs + 3];
+  const double m0 = Sc[0], pg_old = Sc[1], alpha = st.ALPHA[b];
+
+  double v[4] = {0.0, 0.0, 0.0, 0.0};   // sum s y, sum s s, sum y y, sum gr s
+  bool take = true, store = false;      // a base is accepted; the pair goes to its slot
+  if (phase == kAlSearch) {
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock) {
+      const double g = Gb[j];
+      const double s = XCb[j] - Xb[j];
+      const double y = GCb[j] - g;
+      s_s[j] = s;
+      s_y[j] = y;
+      v[0] += s * y;
+      v[1] += s * s;
+      v[2] += y * y;
+      v[3] += g * s;
+    }
+    block_sums<4>(v, s_part, s_bc, tid);
+    const double c1gs = a.c1 * v[3];
+    take = v[3] <= 0.0 && mc <= m0 + c1gs;   // (a NaN anywhere: false)
+    store = take && v[0] > a.curv_eps * v[2];
+    if (store) {
+      double* S = st.HS + (b * mem + next) * st.ldh;
+      double* Y = st.HY + (b * mem + next) * st.ldh;
+#pragma unroll 4
+      for (int j = tid; j < n; j += kLbfgsBlock) {
+        S[j] = s_s[j];
+        Y[j] = s_y[j];
+      }
+    }
+  }
+
+  unsigned long long pg = 0ull;
+  if (take) {   // X <- XC, GR <- GRC and pg there (the step kernel's expression with a = 1)
+    const double* Lo = a.XL + b * a.ldb;
+    const double* Up = a.XU + b * a.ldb;
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock) {
+      const double x = XCb[j], g = GCb[j], l = Lo[j], u = Up[j];
+      Xb[j] = x;
+      Gb[j] = g;
+      const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+      const double ad = 1.0 * g;
+      double xp = x - ad;
+      if (has_l && xp < l) xp = l;
+      if (has_u && xp > u) xp = u;
+      const unsigned long long sb = v_bits(fabs(xp - x));
+      if (sb > pg) pg = sb;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long om = __shfl_down(pg, o, 64);
+      if (om > pg) pg = om;
+    }
+    if ((tid & 63) == 0) s_pg[tid >> 6] = pg;
+    __syncthreads();
+  }
+  if (tid != 0) return;
+
+  int code, flags = 0;
+  if (take) {
+    for (int w = 1; w < kLbfgsWaves; ++w)
+      if (s_pg[w] > pg) pg = s_pg[w];
+    if (phase == kAlRestart) {
+      st.HMETA[2 * b] = 0;
+      st.HMETA[2 * b + 1] = 0;
+      IS[0] = kAlSearch;
+      code = 1;
+      flags = 1 | 2 | 4;
+    } else {
+      const int cnt = store ? (count < mem ? count + 1 : mem) : count;
+      if (store) {
+        st.HMETA[2 * b] = cnt;
+        st.HMETA[2 * b + 1] = next + 1 < mem ? next + 1 : 0;
+      }
+      double* Ub = st.USUM + b * st.ldus;
+      Ub[0] = v[0];
+      Ub[1] = v[1];
+      Ub[2] = v[2];
+      Ub[3] = store ? 1.0 : 0.0;
+      Ub[4] = (double)cnt;
+      Ub[5] = store ? (double)next : -1.0;
+      code = 2;
+      flags = 1 | 2;
+    }
+    Sc[0] = mc;
+    Sc[1] = __longlong_as_double((long long)pg);
+    Sc[4] = viol;
+    Sc[5] = fc;
+    st.ALPHA[b] = a.alpha0;
+  } else {
+    const double t = alpha * a.shrink;
+    if (t >= a.alpha_min) {
+      st.ALPHA[b] = t;
+      code = 3;
+    } else if (count > 0) {
+      st.HMETA[2 * b] = 0;
+      st.HMETA[2 * b + 1] = 0;
+      st.ALPHA[b] = a.alpha0;
+      flags = 2 | 4;
+      code = 4;
+    } else {
+      IS[0] = kAlStalled;
+      st.ALPHA[b] = 0.0;
+      code = 5;
+    }
+  }
+  IS[1] = flags;
+  IS[2] = inner + 1;
+  Lb[0] = (double)code;
+  Lb[1] = v[3];
+  Lb[2] = mc;
+  Lb[3] = m0;
+  Lb[4] = v[0];
+  Lb[5] = v[2];
+  Lb[6] = store ? 1.0 : 0.0;
+  Lb[7] = take ? __longlong_as_double((long long)pg) : pg_old;
+}
+
 __global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_direction_kernel(LbfgsDirArgs a) {
 #pragma clang fp contract(off)
   extern __shared__ double s_dyn[];
@@ -113,6 +267,7 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_direction_kernel(Lbfgs
   __shared__ double s_alpha[TOWR_LBFGS_MAX_MEM], s_c[TOWR_LBFGS_MAX_MEM];   // a_i and c_i of the used pairs, by i - 1
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x;
+  if (a.RUN && !(a.RUN[b * a.run_stride] & 2)) return;   // (block-uniform: before any barrier)
   const int n = a.n, mem = a.mem;
   double* s_q = s_dyn;       // q, then r; a held column keeps g
   double* s_v = s_dyn + n;   // the pair's y (first loop) or s (second loop)
@@ -237,9 +392,96 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_direction_kernel(Lbfgs
   }
 }
 
+// The outer update and the initialisation of the resident AL loop (towr_gpu.h). One block per problem, lane l on rows /
+// columns l, l + kLbfgsBlock, ..., the rows streamed once (non-temporal). There are no sums: every output is a copy, one
+// rounded product or a comparison.
+//   outer: every lane reads the problem's phase, flags, counter and scalars and takes the same decisions on them; a
+//          problem the update does not act on returns before anything is written. Only the multiplier update moves a
+//          row (LAM <- LAMP); the scalars are written by lane 0 behind a barrier, once every lane has read them.
+//   init:  XC = the caller's X clamped to the sides that count, D = 0, the scalars by lane 0.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_outer_kernel(OuterArgs a) {
+#pragma clang fp contract(off)
+  const towr_alsolve_state_t& st = a.st;
+  const towr_alsolve_params_t& pr = a.pr;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  int32_t* IS = st.ISTATE + 4 * b;
+  double* Sc = st.SCAL + b * st.ldsc;
+  const int phase = IS[0], flags = IS[1], inner = IS[2], outer = IS[3];
+  const double pg = Sc[1], eta = Sc[2], omega = Sc[3], viol = Sc[4];
+  if (phase != kAlSearch || !(flags & 1) || !(pg <= omega || inner >= pr.max_inner)) return;
+  const bool converged = viol <= eta && viol <= pr.eta_star && pg <= pr.omega_star;
+  const bool feasible = viol <= eta;   // (a NaN viol: the penalty grows)
+  if (!converged && feasible) {
+    const double* LPb = st.LAMP + b * st.ldl;
+    double* LAMb = st.LAM + b * st.ldl;
+#pragma unroll 4
+    for (int i = tid; i < a.m; i += kLbfgsBlock) __builtin_nontemporal_store(__builtin_nontemporal_load(LPb + i), LAMb + i);
+  }
+  __syncthreads();   // every lane has read the scalars
+  if (tid != 0) return;
+  st.ALPHA[b] = 0.0;
+  IS[1] = 0;
+  if (converged) {
+    IS[0] = kAlConverged;
+    return;
+  }
+  if (feasible) {
+    const double te = eta * pr.eta_shrink, to = omega * pr.omega_shrink;
+    Sc[2] = te > pr.eta_star ? te : pr.eta_star;
+    Sc[3] = to > pr.omega_star ? to : pr.omega_star;
+  } else {
+    const double tr = st.RHO[b] * pr.rho_grow;
+    st.RHO[b] = tr < pr.rho_max ? tr : pr.rho_max;
+  }
+  IS[3] = outer + 1;
+  IS[2] = 0;
+  st.HMETA[2 * b] = 0;
+  st.HMETA[2 * b + 1] = 0;
+  IS[0] = outer + 1 >= pr.max_outer ? kAlMaxed : kAlRestart;
+}
+
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_init_kernel(AlInitArgs a) {
+#pragma clang fp contract(off)
+  const towr_alsolve_state_t& st = a.st;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const double* Xb = st.X + b * st.ldx;
+  const double* Lo = a.XL + b * a.ldb;
+  const double* Up = a.XU + b * a.ldb;
+  double* XCb = st.XC + b * st.ldx;
+  double* Db = st.D + b * st.ldx;
+#pragma unroll 4
+  for (int j = tid; j < a.n; j += kLbfgsBlock) {
+    const double l = Lo[j], u = Up[j];
+    double x = __builtin_nontemporal_load(Xb + j);
+    if (l > -kSideInf && x < l) x = l;   // (the comparisons drop a NaN: x stays NaN)
+    if (u < kSideInf && x > u) x = u;
+    __builtin_nontemporal_store(x, XCb + j);
+    __builtin_nontemporal_store(0.0, Db + j);
+  }
+  if (tid != 0) return;
+  int32_t* IS = st.ISTATE + 4 * b;
+  IS[0] = kAlRestart;
+  IS[1] = 0;
+  IS[2] = 0;
+  IS[3] = 0;
+  st.HMETA[2 * b] = 0;
+  st.HMETA[2 * b + 1] = 0;
+  st.RHO[b] = a.rho0;
+  st.ALPHA[b] = 0.0;
+  double* Sc = st.SCAL + b * st.ldsc;
+  for (int k = 0; k < 8; ++k) Sc[k] = 0.0;
+  Sc[2] = a.eta0;
+  Sc[3] = a.omega0;
+}
+
 }  // namespace
 
 const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }
+const void* linesearch_kernel() { return reinterpret_cast<const void*>(&towr_linesearch_kernel); }
+const void* alsolve_outer_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_outer_kernel); }
+const void* alsolve_init_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_init_kernel); }
 
 }  // namespace tg

@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(kResBlock) towr_residual_kernel(ResArgs a) {
   const double* Ub = a.GU + b * a.ldb;
   const double* LAMb = a.LAM ? a.LAM + b * a.ldl : nullptr;
   double* LPb = a.LAMP ? a.LAMP + b * a.ldlp : nullptr;
-  const double rho = a.rho;
+  const double rho = a.RHO ? a.RHO[b] : a.rho;   // (RHO: the resident loop's per-problem penalty, auglag.hip)
   for (int s = tid; s <= a.n_sets; s += kResBlock) s_row0[s] = a.set_row0[s];
   for (int s = tid; s < a.n_sets; s += kResBlock) s_setmax[s] = 0ull;
   __syncthreads();

@@ -165,6 +165,23 @@ class Engine {
                                                    ALPHA, alpha, XL, XU, ldxb, curv_eps, HS, HY, ldh, HMETA, F, GR, ldgr, RSUM, ldrs,
                                                    USUM, ldus, DSUM, ldds, XP, ldxp, SSUM, ldss, stream);
   }
+  // the resident solve loop: the line search, the outer (multiplier / penalty) update, the state's initialisation and
+  // `iters` whole iterations on the stream (include/towr_gpu.h); they return the status
+  int LinesearchBatchDevice(int B, const towr_alsolve_params_t& params, const towr_alsolve_state_t& state, const double* XL,
+                            const double* XU, int64_t ldxb, void* stream) const {
+    return towr_gpu_linesearch_batch_device(h_, B, &params, &state, XL, XU, ldxb, stream);
+  }
+  int AuglagOuterBatchDevice(int B, const towr_alsolve_params_t& params, const towr_alsolve_state_t& state, void* stream) const {
+    return towr_gpu_auglag_outer_batch_device(h_, B, &params, &state, stream);
+  }
+  int AlsolveInit(int B, const towr_alsolve_params_t& params, const towr_alsolve_state_t& state, const double* XL,
+                  const double* XU, int64_t ldxb, void* stream) const {
+    return towr_gpu_alsolve_init_batch_device(h_, B, &params, &state, XL, XU, ldxb, stream);
+  }
+  int AlsolveIterate(int B, int iters, const towr_alsolve_params_t& params, const towr_alsolve_state_t& state, const double* GL,
+                     const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb, void* stream) const {
+    return towr_gpu_alsolve_iterate_batch_device(h_, B, iters, &params, &state, GL, GU, ldgb, XL, XU, ldxb, stream);
+  }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // page-lock caller memory for in-place host transfers (towr_gpu_register_host); returns the status
   int RegisterHost(void* p, size_t bytes) const { return towr_gpu_register_host(h_, p, (int64_t)bytes); }

@@ -63,6 +63,55 @@ def _check_per_problem(t, what, B, device):
         raise TowrGpuError(f"{what}: expected a contiguous 1-D tensor of >= B entries")
 
 
+AL_PARAM_DEFAULTS = dict(mem=5, max_inner=50, max_outer=20, c1=1e-4, shrink=0.5, alpha0=1.0, alpha_min=1e-10, curv_eps=1e-8,
+                         rho0=10.0, rho_grow=10.0, rho_max=1e8, eta0=0.1, eta_shrink=0.1, eta_star=1e-6,
+                         omega0=0.1, omega_shrink=0.1, omega_star=1e-6)
+
+
+def alsolve_params(**kw) -> capi.AlSolveParams:
+    """towr_alsolve_params_t from keywords (AL_PARAM_DEFAULTS for the rest); the C-ABI checks the ranges."""
+    unknown = set(kw) - set(AL_PARAM_DEFAULTS)
+    if unknown:
+        raise TowrGpuError(f"alsolve_params: unknown field(s) {sorted(unknown)}")
+    return capi.AlSolveParams(**{**AL_PARAM_DEFAULTS, **kw})
+
+
+class AlSolveState:
+    """The tensors of towr_alsolve_state_t (towr_gpu.h) for B problems and `mem` pairs; allocate() makes them (zeros) on
+    the problem's device. X holds the starting points and LAM the starting multipliers before alsolve_init."""
+    _ROWS = ("X", "GR", "XC", "GRC", "D", "LAM", "LAMP", "HS", "HY", "SCAL", "RSUM", "SSUM", "DSUM", "USUM", "LSUM")
+    _VECS = ("ALPHA", "RHO", "FC")
+
+    @classmethod
+    def allocate(cls, p, B, mem):
+        import torch
+        dev = torch.device("cuda", p.device)
+        z = lambda r, c: torch.zeros((r, c), dtype=torch.float64, device=dev)
+        s = cls()
+        s.B, s.mem = B, mem
+        for k in ("X", "GR", "XC", "GRC", "D"):
+            setattr(s, k, z(B, p.n))
+        s.LAM, s.LAMP = z(B, p.m), z(B, p.m)
+        s.HS, s.HY = z(B * mem, p.n), z(B * mem, p.n)
+        s.HMETA = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+        s.ISTATE = torch.zeros(4 * B, dtype=torch.int32, device=dev)
+        for k in cls._VECS:
+            setattr(s, k, torch.zeros(B, dtype=torch.float64, device=dev))
+        s.SCAL, s.LSUM, s.USUM, s.DSUM = z(B, 8), z(B, 8), z(B, 6), z(B, 5)
+        s.RSUM, s.SSUM = z(B, 4 + p.desc.n_constraints), z(B, 5 + p.desc.n_varsets)
+        return s
+
+    def tensors(self):
+        return {k: getattr(self, k) for k in self._ROWS + self._VECS + ("HMETA", "ISTATE")}
+
+    def clone(self):
+        s = type(self)()
+        s.B, s.mem = self.B, self.mem
+        for k, t in self.tensors().items():
+            setattr(s, k, t.clone())
+        return s
+
+
 class TowrGpuProblem:
     """`data`: side data of towr_gpu_create_ex, [(towr_data_kind, index, float64 array)]: the matrix M of
     each LinearEqualityConstraint (capi.DATA_LINEAR_M, constraint index, rows x n_set row-major) and the
@@ -551,6 +600,68 @@ class TowrGpuProblem:
             self._h, B, mem, *_opt(X), *_opt(XPREV), *_opt(GRPREV), gl, gu, ldgb, *_opt(LAM), float(rho), ap, a, xl, xu, ldxb,
             float(curv_eps), hs, hy, ldh, hm, _opt(F)[0], *_opt(GR), *_opt(RSUM), *_opt(USUM if XPREV is not None else None),
             *_opt(DSUM), *_opt(XP), *_opt(SSUM), self._stream(stream, X)))
+
+    # -------------------------------------------------------------------- resident loop -------
+    def _alsolve_state(self, st, params):
+        """towr_alsolve_state_t of an AlSolveState, after the checks the C-ABI cannot make (dtypes, devices, rows)."""
+        import torch
+        B, mem = st.B, st.mem
+        if mem != params.mem:
+            raise TowrGpuError(f"state allocated for mem = {mem}, params.mem = {params.mem}")
+        n, m = self.n, self.m
+        self._check_rows(B, *[(getattr(st, k), k, n) for k in ("X", "GR", "XC", "GRC", "D")],
+                         (st.LAM, "LAM", m), (st.LAMP, "LAMP", m), (st.SCAL, "SCAL", 8), (st.LSUM, "LSUM", 8), (st.USUM, "USUM", 6),
+                         (st.DSUM, "DSUM", 5), (st.RSUM, "RSUM", 4 + self.desc.n_constraints),
+                         (st.SSUM, "SSUM", 5 + self.desc.n_varsets))
+        for a, b in (("X", "GR"), ("X", "XC"), ("X", "GRC"), ("X", "D"), ("LAM", "LAMP")):
+            if getattr(st, a).stride(0) != getattr(st, b).stride(0):
+                raise TowrGpuError(f"{a} and {b}: they share one leading dimension")
+        hs, hy, ldh, hm = self._history_operands(B, mem, st.HS, st.HY, st.HMETA)
+        for k in ("ALPHA", "RHO", "FC"):
+            _check_per_problem(getattr(st, k), k, B, self.device)
+        t = st.ISTATE
+        if t.dtype != torch.int32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() \
+                or t.numel() < 4 * B:
+            raise TowrGpuError("ISTATE: expected a contiguous int32 tensor of >= 4 B entries on the handle's device")
+        c = capi.AlSolveStateC()
+        for k in ("X", "GR", "XC", "GRC", "D", "LAM", "LAMP", "HS", "HY", "HMETA", "ALPHA", "RHO", "FC", "SCAL", "ISTATE",
+                  "RSUM", "SSUM", "DSUM", "USUM", "LSUM"):
+            setattr(c, k, getattr(st, k).data_ptr())
+        c.ldx, c.ldl, c.ldh, c.ldsc = st.X.stride(0), st.LAM.stride(0), ldh, st.SCAL.stride(0)
+        c.ldrs, c.ldss, c.ldds, c.ldus, c.ldls = (st.RSUM.stride(0), st.SSUM.stride(0), st.DSUM.stride(0), st.USUM.stride(0),
+                                                  st.LSUM.stride(0))
+        return c
+
+    def linesearch_batch_device(self, params, st, XL=None, XU=None, stream=None):
+        """Keep or reject every problem's candidate st.XC behind an evaluation (st.FC, st.GRC, st.RSUM): the Armijo
+        test, the pair offered to the history, the base, ALPHA, the phase and flags, LSUM (towr_gpu.h)."""
+        c = self._alsolve_state(st, params)
+        xl, xu, ldb = self._var_bounds_operands(st.B, XL, XU)
+        self._check(self._lib.towr_gpu_linesearch_batch_device(self._h, st.B, C.byref(params), C.byref(c), xl, xu, ldb,
+                                                               self._stream(stream, st.X)))
+
+    def auglag_outer_batch_device(self, params, st, stream=None):
+        """The outer update of the problems whose inner loop is done: converged, LAM <- LAMP with tighter tolerances,
+        or a larger RHO (towr_gpu.h)."""
+        c = self._alsolve_state(st, params)
+        self._check(self._lib.towr_gpu_auglag_outer_batch_device(self._h, st.B, C.byref(params), C.byref(c),
+                                                                 self._stream(stream, st.X)))
+
+    def alsolve_init(self, params, st, XL=None, XU=None, stream=None):
+        """Start a solve from st.X (clamped into st.XC) and st.LAM: phases, counters, RHO, ALPHA, tolerances."""
+        c = self._alsolve_state(st, params)
+        xl, xu, ldb = self._var_bounds_operands(st.B, XL, XU)
+        self._check(self._lib.towr_gpu_alsolve_init_batch_device(self._h, st.B, C.byref(params), C.byref(c), xl, xu, ldb,
+                                                                 self._stream(stream, st.X)))
+
+    def alsolve_iterate(self, params, st, iters=1, GL=None, GU=None, XL=None, XU=None, stream=None):
+        """`iters` complete iterations (evaluation, line search, outer update, direction, step) on the stream, with no
+        host synchronisation. Frozen problems are still evaluated; their state no longer changes."""
+        c = self._alsolve_state(st, params)
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        self._check(self._lib.towr_gpu_alsolve_iterate_batch_device(self._h, st.B, int(iters), C.byref(params), C.byref(c),
+                                                                    gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
