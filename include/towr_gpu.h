@@ -313,6 +313,18 @@ int towr_gpu_eval_grad_f(towr_gpu_handle h, const double* x, double* grad);
 /* Batched objective on the device: F[b], GRAD[b*ldgrad + j]; stream as for eval_batch_device.    */
 int towr_gpu_eval_cost_batch_device(towr_gpu_handle h, int32_t B, const double* X, int64_t ldx,
                                     double* F, double* GRAD, int64_t ldgrad, void* stream);
+/* The objective kernel's blocks are persistent: a launch has min(B, grid) blocks and block k takes problems k,
+ * k + grid, k + 2 grid, ... The automatic grid is what the device holds at once (blocks per CU x CUs, one value
+ * for the f-only kernel and one for the gradient kernel). towr_gpu_set_cost_grid replaces it on this handle for
+ * every objective launch (f only and gradient alike): blocks >= 1 blocks, 0 = the automatic grid again, negative =
+ * TOWR_ERR_INVALID. The kernel has no grid-wide wait (a block never waits for another), so any positive value is
+ * safe; the results do not depend on it, bit for bit. A SoftConstraint child's launches are not affected. It is a
+ * test and experiment knob, like towr_gpu_set_products_chunk, and needs no device (layout-only handles accept it).
+ * towr_gpu_cost_grid returns the grid in effect (>= 1) for the f-only (grad = 0) or the gradient (grad != 0)
+ * launch, the automatic one while no override is set (1 on a layout-only handle); TOWR_ERR_INVALID (negative) for
+ * a NULL handle.                                                                                                 */
+int towr_gpu_set_cost_grid(towr_gpu_handle h, int32_t blocks);
+int towr_gpu_cost_grid(towr_gpu_handle h, int32_t grad);
 
 /* ---- trajectory export: SaveTrajectoryToCSV (towr/src/utils/save_data.cpp:9-130) ------------ */
 /* Samples at t = 0, dt, 2dt, ... (accumulated) while t <= T + 1e-9, T = the base-linear spline's total

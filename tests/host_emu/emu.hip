@@ -194,6 +194,19 @@ extern "C" int emu_cost_acc(const towr_problem_desc_t* d, const double* x, int a
   return 0;
 }
 
+// The limb arithmetic alone (engine_math.h, single-source with the kernel): CostLimbEmit::operator() on one column
+// (n_pad = 1) for v[0], v[1], ... in order, then limb_value of the three sums. limbs[k] = the signed sum of limb k,
+// *bad = CostLimbEmit's flag (the kernel then returns NaN), *value = limb_value whatever the flag.
+extern "C" void emu_limb_sum(const double* v, int k, long long limbs[3], int* bad, double* value) {
+  unsigned long long acc[3] = {0, 0, 0};
+  int flag = 0;
+  CostLimbEmit em{acc, 1, &flag};
+  for (int i = 0; i < k; ++i) em(0, 0, v[i], true);
+  for (int l = 0; l < 3; ++l) limbs[l] = (long long)acc[l];
+  *bad = flag;
+  *value = limb_value((long long)acc[0], (long long)acc[1], (long long)acc[2]);
+}
+
 namespace {
 struct CountEmit {
   static constexpr bool kSparse = true;

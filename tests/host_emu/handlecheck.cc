@@ -76,6 +76,9 @@ int exercise(towr_gpu_handle h, const towr_problem_desc_t& d) {
   CHECK(towr_gpu_pattern_outside(h, x.data(), &outside) == TOWR_OK && outside >= 0);
   CHECK(towr_gpu_algorithmic_bytes_per_call(h) > 0);
   CHECK(towr_gpu_set_products_chunk(h, 0) == TOWR_OK);
+  CHECK(towr_gpu_set_cost_grid(h, 3) == TOWR_OK && towr_gpu_cost_grid(h, 0) == 3 && towr_gpu_cost_grid(h, 1) == 3);
+  CHECK(towr_gpu_set_cost_grid(h, -1) == TOWR_ERR_INVALID && towr_gpu_cost_grid(h, 1) == 3);
+  CHECK(towr_gpu_set_cost_grid(h, 0) == TOWR_OK && towr_gpu_cost_grid(h, 1) == 1);
 
   // what needs a device is refused, and the handle stays whole
   std::vector<double> g((size_t)m + 1), v((size_t)nnz + 1), tr((size_t)ns * ncols);

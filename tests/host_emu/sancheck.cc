@@ -3,9 +3,11 @@
 // grids, structure pass, CSR, tiles, slot tables, streaming tables, cost items) and the host instantiation
 // of engine_math.h through the emulation (emu.hip), built host-only with the sanitizers. Input: the
 // problem file format of oracle/sancheck.c. Built by `make sanitize`.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -18,8 +20,47 @@ extern "C" int emu_traj(const towr_problem_desc_t* d, const double* x, double dt
 extern "C" int emu_jac_products_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, const double* V,
                                    const double* P, const double* LAM, const double* Z0, double* Y, double* Z, double* Za);
 
+extern "C" void emu_limb_sum(const double* v, int k, long long limbs[3], int* bad, double* value);
+
+// The limb arithmetic (CostLimbEmit, limb_of, limb_value) on the boundary list of tests/test_costs.py, each entry
+// alone, then all accepted ones together and 2047 of the largest accepted magnitude, in exactly sized heap buffers
+// (shifts by the exponent are where undefined behaviour would hide). Returns 0 when every flag and sum is as expected.
+static int limb_boundaries() {
+  const double inf = std::numeric_limits<double>::infinity(), top = std::nextafter(0x1p65, 0.0);
+  const double ok[] = {0x1p-60, -0x1p-60, std::nextafter(0x1p-60, 0.0), 0x1p-61, 4.9e-324, -2.2e-308, 0.0, -0.0,
+                       top, -top, 0x1p-18, -0x1p24, 1.0, -3.5e-7, 0x1p64, 0x1p-19 - 0x1p-60};
+  const double refused[] = {0x1p65, -0x1p65, inf, -inf, std::nan(""), 1e30, 1.7e308};
+  for (double x : ok) {
+    std::vector<double> v(1, x);
+    std::vector<long long> l(3);
+    int bad = -1; double val = 0.0;
+    emu_limb_sum(v.data(), 1, l.data(), &bad, &val);
+    if (bad != 0) return 1;
+    if (std::fabs(x) >= 0x1p-60 && !(std::fabs(val - x) <= 0x1p-60)) return 2;
+    if (std::fabs(x) < 0x1p-60 && (l[0] || l[1] || l[2] || val != 0.0)) return 3;
+  }
+  for (double x : refused) {
+    std::vector<double> v(1, x);
+    std::vector<long long> l(3);
+    int bad = -1; double val = 0.0;
+    emu_limb_sum(v.data(), 1, l.data(), &bad, &val);
+    if (bad != 1 || l[0] || l[1] || l[2]) return 4;
+  }
+  std::vector<double> all(ok, ok + sizeof ok / sizeof ok[0]);
+  std::vector<long long> l(3);
+  int bad = -1; double val = 0.0;
+  emu_limb_sum(all.data(), (int)all.size(), l.data(), &bad, &val);
+  if (bad != 0) return 5;
+  std::vector<double> many(2047, top);
+  emu_limb_sum(many.data(), (int)many.size(), l.data(), &bad, &val);
+  const long long lim = 1ll << 53;
+  if (bad != 0 || l[0] >= lim || l[1] >= lim || l[2] >= lim || l[0] < 0 || l[1] < 0 || l[2] <= 0) return 6;
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) { std::fprintf(stderr, "usage: %s problem.bin\n", argv[0]); return 2; }
+  if (int rc = limb_boundaries()) { std::fprintf(stderr, "limb boundaries: check %d\n", rc); return 8; }
   FILE* f = std::fopen(argv[1], "rb");
   if (!f) return 2;
   towr_problem_desc_t d;

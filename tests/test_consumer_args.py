@@ -404,3 +404,30 @@ def test_jac_csc_and_products_chunk_refuse_null(p):
         assert lib.towr_gpu_set_products_chunk(*args) == INV
         assert lib.towr_gpu_last_error(args[0]) == b"bad argument"
     assert lib.towr_gpu_set_products_chunk(h, 0) == capi.TOWR_OK
+
+
+def test_cost_grid_arguments(p):
+    """towr_gpu_set_cost_grid / towr_gpu_cost_grid on a layout-only handle (the setter needs no device, like the
+    products chunk's): NULL and negative values are refused, an override is reported for both launches and 0 restores
+    the automatic grid (1 where no device sized it); the wrappers say the same."""
+    lib, h = p._lib, p._h
+    for args in ((None, 1), (h, -1), (h, -(2 ** 31))):
+        assert lib.towr_gpu_set_cost_grid(*args) == INV
+        assert lib.towr_gpu_last_error(args[0]) == b"bad argument"
+    assert lib.towr_gpu_cost_grid(None, 0) == INV
+    assert lib.towr_gpu_last_error(None) == b"null handle"
+    auto = [lib.towr_gpu_cost_grid(h, g) for g in (0, 1)]
+    assert auto == [1, 1]
+    for blocks in (1, 3, 2048, 2 ** 31 - 1):
+        assert lib.towr_gpu_set_cost_grid(h, blocks) == capi.TOWR_OK
+        assert [lib.towr_gpu_cost_grid(h, g) for g in (0, 1, 7)] == [blocks] * 3
+    assert lib.towr_gpu_set_cost_grid(h, -1) == INV                       # a refused value leaves the override in place
+    assert lib.towr_gpu_cost_grid(h, 1) == 2 ** 31 - 1
+    assert lib.towr_gpu_set_cost_grid(h, 0) == capi.TOWR_OK
+    assert [lib.towr_gpu_cost_grid(h, g) for g in (0, 1)] == auto
+    p.set_cost_grid(5)
+    assert (p.cost_grid(False), p.cost_grid(True), p.cost_grid()) == (5, 5, 5)
+    with pytest.raises(Exception, match="bad argument"):
+        p.set_cost_grid(-2)
+    p.set_cost_grid(0)
+    assert p.cost_grid() == 1

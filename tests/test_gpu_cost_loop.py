@@ -1,0 +1,309 @@
+"""The objective kernel (towr_cost_kernel, cost_traj.hip) past a block's first problem. Its blocks are persistent: a
+launch has min(B, grid) blocks and block k takes problems k, k + grid, ... with the next problem's x prefetched in
+registers (XStage issue / commit). With the automatic grid (about 512 blocks on MI355X) every small batch is one trip
+per block, so these tests cap the grid per handle (set_cost_grid) and look at what a second trip could get wrong: a
+stale x, stale limbs or a stale error flag, the wrong problem's terrain or soft-child rows, the ragged last trip, the
+hand-over between XStage's 16-byte-aligned and unaligned paths.
+
+Common set-up: outputs and the padding of every leading dimension are NaN-prefilled; ldgrad = n + 3; ldx is odd (n + 1
+for even n, n for odd n), so consecutive rows alternate 16-byte alignment and, with an odd grid, so do a block's
+consecutive problems; rows are x0 + 0.03 * standard_normal, one seed per row. A "clean reference row" is the row
+copied to a fresh (aligned) one-row tensor and evaluated at B = 1 with the override off."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle.oracle import Oracle
+from tests.configs import config_descs, cost_descs, ext_cases
+from tests.gpu_helpers import _nan, _np_bits, _padded
+from tests.parity import ABS, REL, assert_cost_close, schedule_cols
+from towr2025_amd import TowrGpuProblem
+from towr2025_amd import _capi as capi
+from towr2025_amd import formulation as F
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+COSTS = cost_descs()
+D = C.POINTER(C.c_double)
+B_LOOP = 11
+
+
+def _rows(x0, B, seed0):
+    return np.stack([x0 + 0.03 * np.random.default_rng(seed0 + b).standard_normal(len(x0)) for b in range(B)])
+
+
+def _ldx(n):
+    return n + 1 if n % 2 == 0 else n
+
+
+def _eval(p, Xd, grad=True):
+    """One eval_cost_batch_device into NaN-prefilled outputs: host (F, GRAD with its padding) or F alone."""
+    import torch
+    B = Xd.shape[0]
+    Fd = _nan(1, B)[0]
+    Gd = _nan(B, p.n + 3) if grad else None
+    p.eval_cost_batch_device(Xd, Fd, Gd)
+    torch.cuda.synchronize()
+    return (Fd.cpu().numpy(), Gd.cpu().numpy()) if grad else Fd.cpu().numpy()
+
+
+def _clean_rows(p, X, rows=None):
+    """{b: (F, gradient)} of the clean reference rows (module docstring). Call it with the override off."""
+    import torch
+    assert X.shape[1] == p.n
+    out = {}
+    for b in (range(len(X)) if rows is None else rows):
+        xd = torch.from_numpy(np.ascontiguousarray(X[b:b + 1])).to("cuda:0")
+        assert xd.data_ptr() % 16 == 0
+        Fh, Gh = _eval(p, xd)
+        assert np.isnan(Gh[:, p.n:]).all()
+        assert np.isfinite(Fh[0]) and np.isfinite(Gh[0, :p.n]).all(), f"clean reference row {b} is not finite"
+        out[b] = (Fh[0], Gh[0, :p.n].copy())
+    return out
+
+
+def _assert_row_bits(tag, Fh, Gh, b, ref, n):
+    f, g = ref
+    assert _np_bits(Fh[b:b + 1])[0] == _np_bits(np.array([f]))[0], f"{tag}: F[{b}] {Fh[b]!r} != {f!r}"
+    diff = np.flatnonzero(_np_bits(Gh[b, :n]) != _np_bits(g))
+    assert diff.size == 0, f"{tag}: row {b} differs in {diff.size} gradient columns, first {diff[0]}: {Gh[b, diff[0]]!r} != {g[diff[0]]!r}"
+
+
+def _loop_desc(name):
+    return COSTS[name] if name in COSTS else config_descs()[name]
+
+
+@pytest.mark.parametrize("name", ["anymal_all_costs", "anymal_stairs_gaitopt_costs", "anymal_rotvec_costs",
+                                  "hopper_forces_motion", "monoped_backflip_rotvec", "monoped_hopper_flat"])
+def test_rows_under_a_looping_block(name):
+    """B = 11 distinct rows at grid 3 (trips 4 / 4 / 3: an odd grid with an odd ldx makes every block alternate between
+    XStage's aligned and unaligned paths in both directions, and the last trip is ragged), grid 1 (one block takes all
+    11), grid 2 (even: a block stays on one path) and the automatic grid (one trip per block). Every row: within
+    assert_cost_close of the oracle, F and the gradient bit-equal to the clean reference row and to eval_f /
+    eval_grad_f, the padding still NaN; the four grids' outputs bit-identical; the f-only call the same F bits at
+    each grid.
+
+    Kernel instantiations <accumulation, phase-duration optimisation, RotVec> reached (cost_acc: slots when the layout
+    has cost_nslot > 0, else limbs; cost_kernel_for; each gradient kernel with its f-only <none, ., .> twin):
+      anymal_all_costs            <slots, no, no>
+      hopper_forces_motion        <slots, no, no>, fewer cost items than the block has lanes
+      monoped_backflip_rotvec     <slots, no, yes> (fixed phase durations, RotVec, cost_nslot > 0)
+      anymal_stairs_gaitopt_costs <limbs, yes, no>
+      anymal_rotvec_costs         <limbs, yes, yes>
+      monoped_hopper_flat         <limbs, no, no>: fixed phase durations take the limbs only when the layout has no
+                                  slots, that is no cost items (this configuration: f = 0 and a zero gradient, the loop
+                                  still clears and converts the limbs per trip) or more than kCostSlotMax slots, which
+                                  no description of a testable size has. <limbs, no, yes> is the same with RotVec and is
+                                  not run."""
+    desc = _loop_desc(name)
+    o = Oracle(desc)
+    p = TowrGpuProblem(desc, device=0)
+    n, B = p.n, B_LOOP
+    X = _rows(o.initial_x(), B, 9100)
+    Xd = _padded(X, _ldx(n))
+    clean = _clean_rows(p, X)
+    auto = (p.cost_grid(False), p.cost_grid(True))
+    assert min(auto) >= B, f"automatic grids {auto}: not one trip per block at B = {B}"
+    outs = {}
+    for grid in (3, 1, 2, 0):
+        p.set_cost_grid(grid)
+        assert p.cost_grid(True) == (grid or auto[1]) and p.cost_grid(False) == (grid or auto[0])
+        Fh, Gh = _eval(p, Xd)
+        F0 = _eval(p, Xd, grad=False)
+        assert np.isnan(Gh[:, n:]).all(), f"{name} grid {grid}: gradient padding written"
+        assert np.array_equal(_np_bits(F0), _np_bits(Fh)), f"{name} grid {grid}: the f-only call's F differs"
+        outs[grid] = (Fh, Gh[:, :n])
+    p.set_cost_grid(0)
+    Fh, Gh = outs[3]
+    for b in range(B):
+        assert_cost_close(o.eval_f(X[b]), Fh[b], o.eval_grad_f(X[b]), Gh[b], f"{name} row {b} vs the oracle")
+        _assert_row_bits(f"{name} grid 3 vs the clean row", Fh, Gh, b, clean[b], n)
+        _assert_row_bits(f"{name} grid 3 vs eval_f / eval_grad_f", Fh, Gh, b, (p.eval_f(X[b]), p.eval_grad_f(X[b])), n)
+    for grid in (1, 2, 0):
+        for b in range(B):
+            _assert_row_bits(f"{name} grid {grid} vs grid 3", outs[grid][0], outs[grid][1], b, (Fh[b], Gh[b]), n)
+    print(f"{name}: n {n}, automatic grids f-only {auto[0]} gradient {auto[1]}")
+
+
+# ---------------------------------------------------------------------- per-problem terrain under the loop ----------
+def _base_height_terrains(B):
+    """Stairs with varied parameters, Flat(h) and Block by turns (no Gap: curvature classes must not mix)."""
+    rng = np.random.default_rng(31)
+    out = []
+    for b in range(B):
+        if b % 3 == 0:
+            t = F.HeightMap(F.HeightMap.StairsID, (rng.uniform(0.8, 1.4), 0.4, rng.uniform(0.1, 0.25), rng.uniform(0.1, 0.25), 1.0))
+        elif b % 3 == 1:
+            t = F.HeightMap.Flat(rng.uniform(0.05, 0.3))
+        else:
+            t = F.HeightMap(F.HeightMap.BlockID, (rng.uniform(0.3, 0.9), 3.5, rng.uniform(0.2, 0.5), 0.03))
+        out.append(t.to_c())
+    return out
+
+
+def _soft_terrains(B):
+    """The description's Stairs on even rows, Slope on odd ones: b and b + 3 always differ."""
+    stairs, slope = F.HeightMap.MakeTerrain(F.HeightMap.StairsID).to_c(), F.HeightMap.MakeTerrain(F.HeightMap.SlopeID).to_c()
+    return [slope if b % 2 else stairs for b in range(B)]
+
+
+def _terrain_key(t):
+    return (t.id, t.friction_coeff, tuple(t.p))
+
+
+@pytest.mark.parametrize("name,terrains_of", [("anymal_stairs_base_height_cost", _base_height_terrains),
+                                              ("anymal_gait_soft", _soft_terrains)])
+def test_per_problem_terrain_under_the_loop(name, terrains_of):
+    """Batch terrains at B = 11, grid 3: every row against the oracle built from the description with
+    desc.terrain = terrains[b] (and the side data). anymal_stairs_base_height_cost is the cost configuration whose
+    kernel items read the terrain (c.ter = P.terrains + b); anymal_gait_soft's soft ForceConstraintDiscretized reads it
+    in the soft child, whose rows sG + b * s_ldg and sV + b * s_ldv the kernel then picks per problem.
+    The teeth are checked on the CPU first: for every row with a neighbour b +- grid in range, the oracle's f and at
+    least one gradient column at x_b under the NEIGHBOUR's terrain differ from those under its own by more than 100
+    times assert_cost_close's tolerance, so the neighbour's terrain (or the first problem's) cannot pass."""
+    desc, data = ext_cases()[name]
+    B, G = B_LOOP, 3
+    terrains = terrains_of(B)
+    oracles = {}
+    for t in terrains:
+        if _terrain_key(t) not in oracles:
+            d = capi.ProblemDesc.from_buffer_copy(desc)
+            d.terrain = t
+            oracles[_terrain_key(t)] = Oracle(d, data)
+    orc = [oracles[_terrain_key(t)] for t in terrains]
+    X = _rows(Oracle(desc, data).initial_x(), B, 9200)
+    ref = [(orc[b].eval_f(X[b]), orc[b].eval_grad_f(X[b])) for b in range(B)]
+    weakest = np.inf
+    for b in range(B):
+        f, g = ref[b]
+        for nb in (b - G, b + G):
+            if not 0 <= nb < B:
+                continue
+            fa, ga = orc[nb].eval_f(X[b]), orc[nb].eval_grad_f(X[b])
+            tol_f = REL * max(abs(f), abs(fa)) + ABS * max(1.0, abs(f))
+            tol_g = REL * np.maximum(np.abs(g), np.abs(ga)) + ABS * max(1.0, float(np.abs(g).max()))
+            rf, rg = abs(fa - f) / tol_f, float(np.max(np.abs(ga - g) / tol_g))
+            weakest = min(weakest, rf, rg)
+            assert rf > 100 and rg > 100, (f"{name}: row {b} cannot tell its terrain from row {nb}'s "
+                                           f"(f {rf:.3g}, gradient {rg:.3g} times the tolerance): change the draw")
+    p = TowrGpuProblem(desc, device=0, data=data)
+    n = p.n
+    Xd = _padded(X, _ldx(n))
+    p.set_batch_terrain(terrains)
+    outs = {}
+    for grid in (G, 0):
+        p.set_cost_grid(grid)
+        Fh, Gh = _eval(p, Xd)
+        F0 = _eval(p, Xd, grad=False)
+        assert np.isnan(Gh[:, n:]).all(), f"{name} grid {grid}: gradient padding written"
+        assert np.array_equal(_np_bits(F0), _np_bits(Fh)), f"{name} grid {grid}: the f-only call's F differs"
+        outs[grid] = (Fh, Gh[:, :n])
+    p.set_cost_grid(0)
+    Fh, Gh = outs[G]
+    for b in range(B):
+        assert_cost_close(ref[b][0], Fh[b], ref[b][1], Gh[b], f"{name} row {b} (terrain id {terrains[b].id}) vs the oracle")
+        _assert_row_bits(f"{name} automatic grid vs grid {G}", outs[0][0], outs[0][1], b, (Fh[b], Gh[b]), n)
+    print(f"{name}: the closest neighbouring terrain is {weakest:.3g} times the tolerance away")
+
+
+# ---------------------------------------------------------------------- one bad problem and the block's next one ----
+@pytest.fixture(scope="module")
+def emu():
+    lib = os.path.join(HERE, "host_emu", "build", "libemu.so")
+    if not os.path.exists(lib):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "host_emu")])
+    L = C.CDLL(lib)
+    L.emu_cost_acc.argtypes = [C.POINTER(capi.ProblemDesc), D, C.c_int, D, D]
+    return L
+
+
+@pytest.mark.parametrize("name", ["anymal_stairs_gaitopt_costs", "biped_gaitopt_costs", "anymal_all_costs"])
+def test_bad_problem_does_not_poison_the_next(emu, name):
+    """Grid 2, B = 6: block 0 takes rows 0, 2, 4 and block 1 rows 1, 3, 5. Row 0 has x[j*] = NaN and row 3 x[j*] = 1e30,
+    j* = argmax |oracle grad f(x0)| over the node columns (not the phase durations: biped_gaitopt_costs' largest entry
+    is the duration column 689, and a phase lasting 1e30 s leaves f and every gradient entry of ordinary size in the
+    oracle too, so it raises nothing; the node columns chosen are 409 and 272). On the limb path (phase-duration optimisation) a NaN, an infinity or an entry of
+    2^65 or more raises the block's error flag: row 0's gradient is NaN in every column and F[0] is NaN; row 3's
+    gradient is NaN in every column while F[3] stays finite and within the gate of the oracle's f. The flag is reset per
+    problem: rows 2 and 4 (after row 0) and row 5 (after row 3) are bit-equal to their clean reference rows, and so is
+    row 1. That the two bad rows really raise the flag is asserted first on the CPU, through the host emulation's limb
+    path (every column NaN), so a formulation change that moves j* off a column the items read fails loudly.
+    anymal_all_costs (slots): only the neighbours and isnan(F[0]); which of the bad row's own columns are NaN is the
+    slot path's business (column-local, and not the oracle's set) and is not pinned."""
+    desc = COSTS[name]
+    limbs = bool(desc.optimize_timings)
+    o = Oracle(desc)
+    x0 = o.initial_x()
+    n, B = o.n, 6
+    j = int(np.argmax(np.where(schedule_cols(desc, n), 0.0, np.abs(o.eval_grad_f(x0)))))
+    X = _rows(x0, B, 9300)
+    X[0, j], X[3, j] = np.nan, 1e30
+    if limbs:
+        for b in (0, 3):
+            f, g = C.c_double(), np.zeros(n)
+            assert emu.emu_cost_acc(C.byref(desc), X[b].ctypes.data_as(D), 2, C.byref(f), g.ctypes.data_as(D)) == 0
+            assert np.isnan(g).all(), f"{name}: x[{j}] = {X[b, j]!r} does not raise the limb path's flag"
+    p = TowrGpuProblem(desc, device=0)
+    good = (1, 2, 4, 5)
+    clean = _clean_rows(p, X, good)
+    Xd = _padded(X, _ldx(n))
+    p.set_cost_grid(2)
+    Fh, Gh = _eval(p, Xd)
+    F0 = _eval(p, Xd, grad=False)
+    p.set_cost_grid(0)
+    assert np.isnan(Gh[:, n:]).all()
+    assert np.array_equal(_np_bits(F0), _np_bits(Fh))
+    for b in good:
+        _assert_row_bits(f"{name} row {b} after a bad one", Fh, Gh, b, clean[b], n)
+    assert np.isnan(Fh[0])
+    if limbs:
+        assert np.isnan(Gh[0, :n]).all() and np.isnan(Gh[3, :n]).all()
+        assert np.isfinite(Fh[3])
+        assert_cost_close(o.eval_f(X[3]), Fh[3], np.zeros(1), np.zeros(1), f"{name} F[3]")
+
+
+# ---------------------------------------------------------------------- the benchmark's objective workload ----------
+def test_bench_objective_workload_at_the_automatic_grid():
+    """bench.py's objective leg (every cost kind on ANYmal's trot, bench.make_batch inputs, batch terrains) at
+    B = 2 * (the larger automatic grid) + 37, so every block takes two problems and some a third: every row of F and
+    GRAD bit-equal to the same rows evaluated in slices of min(64, grid) rows, each a single trip by construction and
+    each with its own terrain slice; 12 seeded rows against the oracle; the f-only call; the NaN padding."""
+    import torch
+    import bench
+    desc = F.with_costs(F.anymal_trot()).to_desc()
+    p = TowrGpuProblem(desc, device=0)
+    g0, g1 = p.cost_grid(False), p.cost_grid(True)
+    print(f"automatic grids: f-only {g0}, gradient {g1}")
+    B = 2 * max(g0, g1) + 37
+    assert B <= 4133
+    n = p.n
+    Xh, terrains = bench.make_batch(p, B, first_id=0)
+    X = Xh[1]
+    Xd = _padded(X, _ldx(n))
+    S = min(64, g0, g1)
+    Fs, Gs, F0s = _nan(1, B)[0], _nan(B, n + 3), _nan(1, B)[0]
+    for s in range(0, B, S):
+        e = min(B, s + S)
+        p.set_batch_terrain(terrains[s:e])
+        p.eval_cost_batch_device(Xd[s:e], Fs[s:e], Gs[s:e])
+        p.eval_cost_batch_device(Xd[s:e], F0s[s:e])
+    torch.cuda.synchronize()
+    p.set_batch_terrain(terrains)
+    Fh, Gh = _eval(p, Xd)
+    F0 = _eval(p, Xd, grad=False)
+    Fs, Gs, F0s = Fs.cpu().numpy(), Gs.cpu().numpy(), F0s.cpu().numpy()
+    assert np.isnan(Gh[:, n:]).all() and np.isnan(Gs[:, n:]).all()
+    assert np.isfinite(Fh).all() and np.isfinite(Gh[:, :n]).all()
+    assert np.array_equal(_np_bits(F0), _np_bits(Fh)) and np.array_equal(_np_bits(F0s), _np_bits(Fs))
+    rows = np.flatnonzero((_np_bits(Fh) != _np_bits(Fs)) | (_np_bits(Gh[:, :n]) != _np_bits(Gs[:, :n])).any(axis=1))
+    assert rows.size == 0, f"{rows.size} rows differ from their single-trip slices, first {rows[:8]} (grids {g0}, {g1})"
+    rng = np.random.default_rng(4133)
+    for b in sorted(rng.choice(B, 12, replace=False)):
+        d = capi.ProblemDesc.from_buffer_copy(desc)
+        d.terrain = terrains[b]
+        o = Oracle(d)
+        assert_cost_close(o.eval_f(X[b]), Fh[b], o.eval_grad_f(X[b]), Gh[b, :n], f"bench objective problem {b}")

@@ -643,6 +643,32 @@ def test_keep_jacobian_pair(name):
     np.testing.assert_array_equal(p.eval_jac_values_kept(xc), p.eval_jac_values(xc))
 
 
+def test_keep_jacobian_pair_across_cost_calls():
+    """IPOPT calls eval_f and eval_grad_f between eval_g and eval_jac_g. On a handle with cost terms, the objective's
+    host callbacks (at the kept x and at another one) and one device batch of the objective between
+    eval_g_keep_jac and eval_jac_values_kept leave the kept values alone: none of them writes the values' staging,
+    and what eval_jac_values_kept returns is bit-equal to eval_jac_values."""
+    import torch
+    desc = COSTS["anymal_all_costs"]
+    o = Oracle(desc)
+    p = TowrGpuProblem(desc, device=0)
+    xa, xb = _perturb(o.initial_x(), 63), _perturb(o.initial_x(), 64)
+    ga, va = p.eval_g_jac(xa)
+    fa, gfa = p.eval_f(xa), p.eval_grad_f(xa)
+    np.testing.assert_array_equal(p.eval_g_keep_jac(xa), ga)
+    assert p.eval_f(xa) == fa and p.eval_f(xb) != fa
+    assert np.isfinite(p.eval_grad_f(xb)).all()
+    np.testing.assert_array_equal(p.eval_grad_f(xa).view(np.uint64), gfa.view(np.uint64))
+    Xd = torch.from_numpy(np.stack([xb, xa, xb])).cuda()
+    Fd = torch.full((3,), float("nan"), dtype=torch.float64, device="cuda")
+    Gd = torch.full((3, p.n), float("nan"), dtype=torch.float64, device="cuda")
+    p.eval_cost_batch_device(Xd, Fd, Gd)
+    torch.cuda.synchronize()
+    assert Fd[1].item() == fa
+    np.testing.assert_array_equal(p.eval_jac_values_kept(xa).view(np.uint64), va.view(np.uint64))
+    np.testing.assert_array_equal(p.eval_jac_values_kept(xa).view(np.uint64), p.eval_jac_values(xa).view(np.uint64))
+
+
 @pytest.mark.parametrize("name", ["anymal_stairs_gaitopt", "anymal_trot_rotvec"])
 def test_handle_regrow_and_recreate(name):
     """What a handle owns across calls: the per-problem scratch (the streaming path's records for the gait layout, the

@@ -177,6 +177,8 @@ SYMBOLS = {
                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "towr_gpu_set_products_chunk": (C.c_int, [_HANDLE, C.c_int32]),
+    "towr_gpu_set_cost_grid": (C.c_int, [_HANDLE, C.c_int32]),
+    "towr_gpu_cost_grid": (C.c_int, [_HANDLE, C.c_int32]),
     "towr_gpu_residual_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double,
                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -3,6 +3,12 @@
 // reaches them through cost_kernel_for / traj_kernel_for (kernel_common.h).
 #include <hip/hip_runtime.h>
 
+// Multiply-adds are fused as the expressions are written (one statement at a time), not wherever the optimiser finds a
+// product with a single use: the f-only and the gradient instantiations of the objective kernel then do the same
+// arithmetic for f, where the default (fast) fused differently once the gradient code was dead and F differed in the
+// last bit on a few problems per thousand. Before the includes: it covers engine_math.h as compiled here.
+#pragma clang fp contract(on)
+
 #include "engine_math.h"
 #include "kernel_common.h"
 #include "layout.h"
@@ -28,7 +34,8 @@ namespace {
 // (towr_gpu.hip's column lists of the soft pattern).
 enum { kAccNone = 0, kAccSlots = 1, kAccLimbs = 2 };
 
-// Blocks are persistent (the host launches as many as fit the device at once, cost_grid): a block stages the
+// Blocks are persistent (the host launches as many as fit the device at once, cost_grid, or as many as
+// towr_gpu_set_cost_grid says; no block ever waits for another, so any grid is safe): a block stages the
 // node table and the slot tables once, then takes problems blockIdx.x, + gridDim.x, ...; the next problem's x
 // is in flight (XStage registers) while the block evaluates the current one, and goes to LDS after it.
 template <int ACC, bool GAIT, bool ROTVEC>

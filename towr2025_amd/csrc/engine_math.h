@@ -2359,7 +2359,8 @@ struct CostLimbEmit {
     const int ex = (int)((bits >> 52) & 0x7ff);
     if (ex == 0) return;                                        // subnormal: below the resolution
     const int sh = ex - 1075 + 60;                              // v * 2^60 = m * 2^sh
-    if (ex == 0x7ff || sh > 126 - 53) { *bad = 1; return; }     // NaN / inf / |v| >= 2^65
+    // NaN / inf / |v| >= 2^65: m < 2^53, so an accepted m * 2^sh stays below 2^125 and its top limb below 2^41
+    if (ex == 0x7ff || sh > 125 - 53) { *bad = 1; return; }
     const unsigned long long m = (bits & ((1ull << 52) - 1)) | (1ull << 52);
     long long l0 = limb_of(m, sh), l1 = limb_of(m, sh - 42), l2 = limb_of(m, sh - 84);
     if (bits >> 63) { l0 = -l0; l1 = -l1; l2 = -l2; }

@@ -132,6 +132,7 @@ struct towr_gpu_handle_s {
   uint16_t* d_c_cptr = nullptr;     // the cost gradient's slot lists (Layout::cost_cptr / cost_cslot)
   uint16_t* d_c_cslot = nullptr;
   int cost_grid[3] = {1, 1, 1};     // the cost kernel's persistent grid per accumulation (launch_cost)
+  int32_t cost_grid_override = 0;   // towr_gpu_set_cost_grid: blocks for every accumulation (0 = the automatic grid)
   double *d_sg = nullptr, *d_sv = nullptr;
   int64_t soft_cap_g = 0, soft_cap_v = 0;   // problems the scratch holds
   // What the solver-step entry points (auglag.hip) keep on the handle: device tables uploaded by the first call that

@@ -725,7 +725,8 @@ int tg::host::launch_cost(towr_gpu_handle h, int B, const double* X, int64_t ldx
   P.c_cptr = h->d_c_cptr; P.c_cslot = h->d_c_cslot; P.c_nslot = L.cost_nslot;
   P.F = F; P.GR = GR; P.ldgr = ldgr;
   void* args[] = {&P};
-  HIPCHK(h, launch_kernel(cost_kernel_for(L.gait, acc, L.rotvec), dim3((unsigned)std::min(B, h->cost_grid[acc])),
+  const int grid = h->cost_grid_override > 0 ? h->cost_grid_override : h->cost_grid[acc];
+  HIPCHK(h, launch_kernel(cost_kernel_for(L.gait, acc, L.rotvec), dim3((unsigned)std::min(B, grid)),
                             dim3(kCostBlock), args, cost_lds_bytes(L, acc), s));
   return h->soft ? scratch_release(h, s) : TOWR_OK;
 }
@@ -1525,6 +1526,17 @@ int towr_gpu_eval_cost_batch_device(towr_gpu_handle h, int32_t B, const double* 
   int per;
   if (int rc = batch_terrain(h, B, false, &ter, &per)) return rc;
   return launch_cost(h, B, X, ldx, F, GRAD, ldgrad, reinterpret_cast<hipStream_t>(stream), ter, per);
+}
+
+int towr_gpu_set_cost_grid(towr_gpu_handle h, int32_t blocks) {
+  if (!h || blocks < 0) return fail(h, TOWR_ERR_INVALID, "bad argument");
+  h->cost_grid_override = blocks;
+  return TOWR_OK;
+}
+
+int towr_gpu_cost_grid(towr_gpu_handle h, int32_t grad) {
+  if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
+  return h->cost_grid_override > 0 ? h->cost_grid_override : h->cost_grid[cost_acc(h->L, grad != 0)];
 }
 
 int towr_gpu_trajectory_size(towr_gpu_handle h, double dt, int32_t* n_samples, int32_t* n_cols) {

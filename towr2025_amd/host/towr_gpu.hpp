@@ -183,6 +183,13 @@ class Engine {
     return towr_gpu_alsolve_iterate_batch_device(h_, B, iters, &params, &state, GL, GU, ldgb, XL, XU, ldxb, stream);
   }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
+  // the objective kernel's persistent grid (towr_gpu_set_cost_grid / towr_gpu_cost_grid); 0 = automatic
+  void SetCostGrid(int blocks) const { Check(towr_gpu_set_cost_grid(h_, blocks)); }
+  int CostGrid(bool grad) const {
+    const int g = towr_gpu_cost_grid(h_, grad ? 1 : 0);
+    if (g < 0) Check(g);
+    return g;
+  }
   // page-lock caller memory for in-place host transfers (towr_gpu_register_host); returns the status
   int RegisterHost(void* p, size_t bytes) const { return towr_gpu_register_host(h_, p, (int64_t)bytes); }
   int UnregisterHost(void* p) const { return towr_gpu_unregister_host(h_, p); }

@@ -667,6 +667,18 @@ class TowrGpuProblem:
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
         self._check(self._lib.towr_gpu_set_products_chunk(self._h, int(k)))
 
+    def set_cost_grid(self, blocks: int):
+        """Blocks of the objective kernel's persistent grid for every launch on this handle (0 = automatic). A launch
+        has min(B, blocks) blocks; block k takes problems k, k + blocks, ... The results do not depend on it."""
+        self._check(self._lib.towr_gpu_set_cost_grid(self._h, int(blocks)))
+
+    def cost_grid(self, grad: bool = True) -> int:
+        """The objective kernel's grid in effect for the gradient (or the f-only) launch."""
+        g = self._lib.towr_gpu_cost_grid(self._h, int(bool(grad)))
+        if g < 0:
+            self._check(g)
+        return g
+
     def step_launches(self):
         """Kernel indices (see kernels()) that one evaluation launches: fusion groups, then the unfused classes."""
         buf = (C.c_int32 * 16)()
