@@ -713,6 +713,69 @@ int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t 
                                           const double* GL, const double* GU, int64_t ldgb,
                                           const double* XL, const double* XU, int64_t ldxb, void* stream);
 
+/* ---- a Gauss-Newton direction for the resident loop: truncated CG on rho J^T W J + mu I --------------------------- */
+/* The CG parameters (host memory, read at the call): at most ncg steps, the damping mu >= 0 (it stands in for a cost
+ * Hessian), the relative residual tolerance tol >= 0.                                                              */
+typedef struct { int32_t ncg, reserved; double mu, tol; } towr_gn_params_t;
+
+/* Per problem a whole CG solve of H d = g on the free columns, H = rho_b (J^T diag(w) J)_ff + mu I, on the CSR values V
+ * (as towr_gpu_eval_batch_device writes them, ldv >= nnz) without forming H. w_i = 1.0 if LAMP[b][i] != 0.0 (lam+ of the
+ * residual kernel: the row is active; a NaN counts as active), else 0.0. rho_b = RHO[b], or the scalar rho when RHO is
+ * NULL. g = GR[b*ldgr + ..]. The held columns are exactly those of towr_gpu_lbfgs_direction_batch_device (the same
+ * comparisons on X, g and the bounds; X = NULL: every column is free and the bounds are not read; XL = XU = NULL: the
+ * handle's bounds; ldb = 0: one shared row). From d = 0, r = p = g on free columns (p = 0 on held ones),
+ * rr = bb = sum_free g^2; bb == 0 ends at once (code 3); else for it < ncg:
+ *   1. stop (code 1) if rr <= tol*tol*bb (the rounded products (tol*tol)*bb; a NaN rr goes on to step 5);
+ *   2. t = w .* (J p) over all rows (the product w_i * (J p)_i: a NaN or infinity in an inactive row still gives NaN);
+ *   3. Hp = rho_b * (J^T t) + mu * p on free columns (two rounded products, one rounded addition), 0 on held ones;
+ *   4. pHp = sum_free p Hp;
+ *   5. stop (code 2) unless pHp > 0 (a NaN anywhere — GR, V, rho_b — ends here);
+ *   6. a = rr / pHp, d = d + a p, r = r - a Hp, rn = sum_free r r, p = r + (rn / rr) p, rr = rn; one step completed.
+ * ncg steps completed: code 0. D_j = d_j on free columns and D_j = g_j bit for bit on held ones; when no step
+ * completed D equals GR bit for bit. SUM[b*lds + ..] holds 6 doubles (lds >= 6): [0] steps completed; [1] bb; [2] the
+ * final rr; [3] sum_j g_j D_j over all columns (the slope); [4] the number of held columns; [5] the stop code.
+ * RUN = NULL: every problem; else problem b is skipped when RUN[b*run_stride] >= 2 (the frozen phases of
+ * towr_alsolve_state_t's ISTATE with run_stride = 4): not one byte of its D or SUM row is touched.
+ * J p and J^T t are the sums of towr_gpu_jac_vec_batch_device and towr_gpu_jac_tvec_batch_device on the same trees, the
+ * dot products one fixed tree each, the stop decisions taken on them: problem b's outputs are a function of its own
+ * operands alone (the same bits for any B, position, stream and run). Nothing beyond nnz (V), m (LAMP), n (X, GR, D, the
+ * bounds) or 6 (SUM) is read or written in any row. D must not overlap any input. No handle scratch is used and the kept
+ * Jacobian is not dropped. All pointers are DEVICE pointers. TOWR_ERR_INVALID before anything runs for: NULL gn, V, LAMP,
+ * GR, D or SUM, ncg < 1, mu or tol negative or NaN, rho <= 0 or NaN with RHO == NULL, ldv < nnz, ldlp < m,
+ * ldx (with X) / ldgr / ldd < n, lds < 6, only one of XL / XU, 0 < ldb < n. TOWR_ERR_UNSUPPORTED at the call when the
+ * kernel's LDS (8 (3 n + m) + 20 KiB + m bytes) does not fit the workgroup's 160 KiB.                                 */
+int towr_gpu_gn_direction_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn,
+                                       const double* V, int64_t ldv, const double* LAMP, int64_t ldlp,
+                                       const double* RHO, double rho, const double* X, int64_t ldx,
+                                       const double* GR, int64_t ldgr, const double* XL, const double* XU, int64_t ldb,
+                                       const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd,
+                                       double* SUM, int64_t lds, void* stream);
+
+/* towr_gpu_alsolve_iterate_batch_device with the Gauss-Newton direction: `iters` complete iterations on `stream`, with
+ * no host synchronisation. DC (B rows, ldx) and GSUM (ldgs >= 6) are caller-owned DEVICE memory beside `state`: the
+ * direction at the candidate and its summary. One iteration:
+ *   1. towr_gpu_eval_cost_batch_device at XC, F = FC and GRAD = GRC;
+ *   2. towr_gpu_eval_batch_device at XC (g and the values in handle scratch), towr_gpu_residual_batch_device with LAM
+ *      and rho = RHO[b] (LAMP, RSUM), towr_gpu_jac_tvec_batch_device of LAMP accumulated onto GRC, and
+ *      towr_gpu_gn_direction_batch_device on those values with (LAMP, RHO, X = XC, GR = GRC), RUN = ISTATE and
+ *      run_stride = 4 (frozen problems are skipped), D = DC, SUM = GSUM;
+ *   3. towr_gpu_linesearch_batch_device (it still offers pairs to the history, which arms the retry below);
+ *   4. towr_gpu_auglag_outer_batch_device;
+ *   5. the select, per problem by the flags the line search wrote (the outer update clears them where it acts): bit 0
+ *      (a base was accepted: X = XC, GR = GRC) D <- DC; else bit 2 (the trial length fell through alpha_min with a pair
+ *      in the history) D <- GR, one steepest-descent retry; else D is untouched. Copies, bit for bit;
+ *   6. towr_gpu_step_batch_device, XC = P(X - ALPHA D), SSUM its SUM.
+ * Bit-identical to those calls in sequence, whatever the products chunk. HS, HY and HMETA are written by the line search
+ * but no direction reads them; DSUM is not written. Frozen problems, batch terrains, the cross-stream scratch rule and
+ * the kept Jacobian as for towr_gpu_alsolve_iterate_batch_device. TOWR_ERR_INVALID before anything runs for what that
+ * entry refuses, NULL gn, DC or GSUM, ncg < 1, mu or tol negative or NaN, ldgs < 6. TOWR_ERR_UNSUPPORTED as for the
+ * L-BFGS kernels and the GN direction.                                                                              */
+int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters,
+                                             const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                             const towr_gn_params_t* gn, double* DC, double* GSUM, int64_t ldgs,
+                                             const double* GL, const double* GU, int64_t ldgb,
+                                             const double* XL, const double* XU, int64_t ldxb, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

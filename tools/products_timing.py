@@ -22,7 +22,11 @@
       device copies that restore X and GR; (q0) times those alone and q - q0 is printed;
   (s) auglag_outer_batch_device with every problem's multipliers updated (LAM <- LAMP, 16 m B bytes; ISTATE restored
       before every call: (s0) times that copy alone and s - s0 is printed) beside (u) a copy of the same bytes;
-  (t) alsolve_iterate(iters = 1) in a running solve from X (mem = MEM), beside row (o) + (q - q0) + s,
+  (t) alsolve_iterate(iters = 1) in a running solve from X (mem = MEM), beside row (o) + (q - q0) + s;
+  (v) gn_direction_batch_device at ncg = NCG (8), tol = 0 (every step runs), on the values of (a), lam+ of (e), GR = J^T lam+,
+      the handle's bounds: beside NCG (b + c), the same passes by the product kernels (one launch and one LDS staging
+      each); (v1) the same call at ncg = 1 (the pass that cannot come from a cache);
+  (w) alsolve_gn_iterate(iters = 1) in a running solve of its own from X (ncg = NCG, mu = 1e-2, tol = 1e-3), beside (t),
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -36,12 +40,13 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from towr2025_amd import AlSolveState, TowrGpuProblem, _capi as capi, alsolve_params  # noqa: E402
+from towr2025_amd import AlSolveState, TowrGpuProblem, _capi as capi, alsolve_params, gn_params  # noqa: E402
 from towr2025_amd import formulation as F  # noqa: E402
 
 REPS = int(os.environ.get("REPS", "20"))
 ROUNDS = int(os.environ.get("ROUNDS", "5"))
 MEM = int(os.environ.get("MEM", "8"))
+NCG = int(os.environ.get("NCG", "8"))
 PEAK = 8.0e12
 
 
@@ -131,6 +136,17 @@ def run(name, f, B):
     stt.X.copy_(Xs[:, :p.n])
     part = alsolve_params(mem=mem, shrink=0.1, curv_eps=1e-14, alpha_min=1e-16, max_inner=100, max_outer=1000)
     p.alsolve_init(part, stt, stream=stream)
+    # the GN direction on (V, lam+ of the residual, GR = J^T lam+) and a running GN solve of its own
+    p.eval_batch_device(X, G, V, stream=stream)
+    p.residual_batch_device(G, SUM, LAM=LAM, rho=rho, LAMP=LAMP, stream=stream)
+    GRg, Dg, GSUM = torch.empty_like(P), torch.empty_like(P), torch.empty((B, 16), dtype=torch.float64, device=dev)
+    p.jac_tvec_batch_device(V, LAMP, GRg, stream=stream)
+    gnv, gnv1, gnw = gn_params(ncg=NCG, mu=1e-2, tol=0.0), gn_params(ncg=1, mu=1e-2, tol=0.0), gn_params(ncg=NCG, mu=1e-2, tol=1e-3)
+    stg = AlSolveState.allocate(p, B, mem)
+    stg.X.copy_(Xs[:, :p.n])
+    p.alsolve_init(part, stg, stream=stream)
+    DCg, GSg = torch.empty_like(stg.X), torch.empty((B, 8), dtype=torch.float64, device=dev)
+    codes_g, steps_g = [], []
     codes = []
     bytes_ls = 8 * (10 * p.n + 30) * B
     bytes_out = 8 * 2 * p.m * B
@@ -145,6 +161,10 @@ def run(name, f, B):
     cq, co, ct = p._alsolve_state(sq, par), p._alsolve_state(so, par), p._alsolve_state(stt, part)
     ls_call = lambda: p._check(p._lib.towr_gpu_linesearch_batch_device(p._h, B, C.byref(par), C.byref(cq), None, None, 0, sp))
     outer_call = lambda: p._check(p._lib.towr_gpu_auglag_outer_batch_device(p._h, B, C.byref(par), C.byref(co), sp))
+    cg = p._alsolve_state(stg, part)
+    gn_iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_gn_iterate_batch_device(
+        p._h, B, 1, C.byref(part), C.byref(cg), C.byref(gnw), C.c_void_p(DCg.data_ptr()), C.c_void_p(GSg.data_ptr()), GSg.stride(0),
+        None, None, 0, None, None, 0, sp))
     iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_iterate_batch_device(p._h, B, 1, C.byref(part), C.byref(ct), None, None, 0,
                                                                               None, None, 0, sp))
 
@@ -184,7 +204,11 @@ def run(name, f, B):
                 ("s0 ISTATE restore alone", lambda: so.ISTATE.copy_(IS_outer)),
                 ("u copy, outer's bytes", lambda: copies["u"][1].copy_(copies["u"][0])),
                 (f"t alsolve iterate mem={mem}", lambda: (p.set_products_chunk(0), iter_call(),
-                                                         codes.append(stt.LSUM[:, 0].clone())))]
+                                                         codes.append(stt.LSUM[:, 0].clone()))),
+                (f"v gn direction ncg={NCG}", lambda: p.gn_direction_batch_device(gnv, V, LAMP, GRg, Dg, GSUM, rho=rho, X=Xs, stream=stream)),
+                ("v1 gn direction ncg=1", lambda: p.gn_direction_batch_device(gnv1, V, LAMP, GRg, Dg, GSUM, rho=rho, X=Xs, stream=stream)),
+                (f"w alsolve gn iterate ncg={NCG}", lambda: (p.set_products_chunk(0), gn_iter_call(),
+                                                            codes_g.append(stg.LSUM[:, 0].clone()), steps_g.append(GSg[:, 0].clone())))]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
         for _ in range(3):
             fn()
@@ -230,6 +254,13 @@ def run(name, f, B):
           f"{torch.bincount(so.ISTATE.view(B, 4)[:, 0].to(torch.int64), minlength=5).tolist()}; iteration t {mq['t']:.4f} ms vs "
           f"o + (q - q0) + (s - s0) {med['o'] + ls + mq['s']:.4f} ms, ratio {mq['t'] / (med['o'] + ls + mq['s']):.3f}; LSUM[0] codes 0..5 over the "
           f"timed iterations {hist}", flush=True)
+    mv = {k.split()[0]: statistics.median(times[k]) for k, _ in variants if k.split()[0] in ("b", "c", "v", "v1", "w", "t")}
+    hist_g = torch.bincount(torch.stack(codes_g).flatten().to(torch.int64), minlength=6).tolist()
+    print(f"  gn direction ncg={NCG}: v {mv['v']:.4f} ms vs {NCG} (b + c) {NCG * (mv['b'] + mv['c']):.4f} ms, ratio "
+          f"{mv['v'] / (NCG * (mv['b'] + mv['c'])):.3f}; per step (v - v1) / {NCG - 1} {(mv['v'] - mv['v1']) / max(NCG - 1, 1):.4f} ms vs b + c "
+          f"{mv['b'] + mv['c']:.4f} ms, first step v1 {mv['v1']:.4f} ms; gn iteration w "
+          f"{mv['w']:.4f} ms vs t {mv['t']:.4f} ms, w - t {mv['w'] - mv['t']:.4f} ms; CG steps per timed iteration "
+          f"{torch.stack(steps_g).mean().item():.2f}; LSUM[0] codes 0..5 {hist_g}", flush=True)
     p.set_products_chunk(0)
 
 

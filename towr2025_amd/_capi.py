@@ -98,6 +98,10 @@ class AlSolveStateC(C.Structure):   # towr_alsolve_state_t
                 ("LSUM", C.c_void_p), ("ldls", C.c_int64)]
 
 
+class GnParams(C.Structure):   # towr_gn_params_t
+    _fields_ = [("ncg", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double), ("tol", C.c_double)]
+
+
 class CostDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("ee", C.c_int32), ("weight", C.c_double), ("dt", C.c_double),
                 ("p", C.c_double * 4), ("ip", C.c_int32 * 4)]
@@ -220,6 +224,15 @@ SYMBOLS = {
     "towr_gpu_alsolve_iterate_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.POINTER(AlSolveParams),
                                                          C.POINTER(AlSolveStateC), C.c_void_p, C.c_void_p, C.c_int64,
                                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_gn_direction_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(GnParams), C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                      C.c_void_p]),
+    "towr_gpu_alsolve_gn_iterate_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.POINTER(AlSolveParams),
+                                                            C.POINTER(AlSolveStateC), C.POINTER(GnParams), C.c_void_p,
+                                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

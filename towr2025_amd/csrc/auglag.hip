@@ -1,7 +1,7 @@
 // auglag.hip — the batched solver-step entry points of the C-ABI (include/towr_gpu.h), what a device-resident
 // augmented-Lagrangian loop calls between evaluations: Jacobian products (J p, J^T lam), constraint residuals and
-// multiplier updates, the projected step, the L-BFGS history and direction, and the fused sequences of these behind
-// an evaluation. Host code only: the kernels live in jprod.hip, resid.hip, step.hip and lbfgs.hip, their argument
+// multiplier updates, the projected step, the L-BFGS history and direction, the Gauss-Newton (CG) direction, and the
+// fused sequences of these behind an evaluation. Host code only: the kernels live in jprod.hip, resid.hip, step.hip and lbfgs.hip, their argument
 // structs in layout.h. The evaluator (towr_gpu.hip) is used through handle.h alone: launch, launch_cost,
 // batch_terrain, bind and the scratch helpers.
 //
@@ -93,6 +93,25 @@ int products_ready(towr_gpu_handle h) {
   return TOWR_OK;
 }
 
+// the GN direction kernel: the product tables, its dynamic LDS within the workgroup's (the static reduction buffers and
+// the runtime's own share beside it: 1 KiB kept free) and the limit raised past the default 64 KiB where it needs more
+int gn_fits(towr_gpu_handle h) {
+  if (h->L.n > kGnMaxN || gn_direction_lds(h->L.n, h->L.m) + 1024 > kLdsMax)
+    return fail(h, TOWR_ERR_UNSUPPORTED, "problem too large for the GN direction kernel's LDS");
+  return TOWR_OK;
+}
+int gn_ready(towr_gpu_handle h) {
+  if (int rc = products_ready(h)) return rc;
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.gn_ready) return TOWR_OK;
+  if (int rc = gn_fits(h)) return rc;
+  const size_t lds = gn_direction_lds(h->L.n, h->L.m);
+  if (lds > 64 * 1024 && hipFuncSetAttribute(gn_direction_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  al.gn_ready = true;
+  return TOWR_OK;
+}
+
 // the residual kernel's tables: the sets' row ranges and, when every set's bounds are known, the description bounds
 int residual_ready(towr_gpu_handle h) {
   towr_gpu_handle_s::AugLag& al = h->al;
@@ -171,6 +190,16 @@ int lbfgs_args(towr_gpu_handle h, const Args& a, int64_t lds_min) {
 int lbfgs_fits(towr_gpu_handle h) {
   if (std::max(lbfgs_update_lds(h->L.n), lbfgs_direction_lds(h->L.n)) > kLbfgsMaxLds)
     return fail(h, TOWR_ERR_UNSUPPORTED, "n too large for the L-BFGS kernels' LDS");
+  return TOWR_OK;
+}
+
+// the CG parameters of a GN direction (towr_gn_params_t) and where its outputs go
+int gn_params(towr_gpu_handle h, const towr_gn_params_t* gn, const double* D, const double* SUM, int64_t lds) {
+  if (!gn) return fail(h, TOWR_ERR_INVALID, "null gn params");
+  if (gn->ncg < 1) return fail(h, TOWR_ERR_INVALID, "gn: ncg must be >= 1");
+  if (!(gn->mu >= 0) || !(gn->tol >= 0)) return fail(h, TOWR_ERR_INVALID, "gn: mu or tol is negative or NaN");
+  if (!D || !SUM) return fail(h, TOWR_ERR_INVALID, "null GN direction or summary (D / SUM, DC / GSUM)");
+  if (lds < 6) return fail(h, TOWR_ERR_INVALID, "leading dimension of the GN summary smaller than 6");
   return TOWR_OK;
 }
 
@@ -276,6 +305,22 @@ int launch_lbfgs_direction(towr_gpu_handle h, int B, LbfgsDirArgs a, hipStream_t
   return TOWR_OK;
 }
 
+// (XL NULL: the handle's bounds, one row — with X, after step_ready; after gn_ready)
+int launch_gn(towr_gpu_handle h, int B, GnArgs a, hipStream_t s) {
+  if (a.X && !a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
+  a.jp = h->al.jp;   // the tables (products_ready)
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(gn_direction_kernel(), dim3((unsigned)B), dim3(kGnBlock), args, gn_direction_lds(a.jp.n, a.jp.m), s));
+  return TOWR_OK;
+}
+
+int launch_gn_select(towr_gpu_handle h, int B, const towr_alsolve_state_t& st, const double* DC, hipStream_t s) {
+  GnSelectArgs a{st.ISTATE, DC, st.ldx, st.GR, st.ldx, st.D, st.ldx, h->L.n, 0};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(gn_select_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
 // (XL NULL: the handle's bounds, one row — after step_ready)
 int launch_linesearch(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const towr_alsolve_state_t& st, const double* XL,
                       const double* XU, int64_t ldb, hipStream_t s) {
@@ -325,9 +370,12 @@ int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> r
 // problems the evaluation at e.X (values into d_pv, never d_v, so the kept Jacobian survives), the residual kernel on
 // that g and the J^T product with lam+ into z.Out, back to back on the caller's stream. e.G / r.LAMP NULL: g / lam+
 // stay in handle scratch (d_rg / d_rl). e, r and z hold the whole batch's operands (r.G, z.V and z.Vec are not used); a
-// chunk launches with its rows of them.
+// chunk launches with its rows of them. With gn (the resident GN loop): behind a chunk's product, while its values are
+// still in d_pv, the GN direction at (e.X, z.Out) with that lam+ and rho into the chunk's rows of gn->D / gn->SUM (of gn
+// the bounds, RUN, D, SUM and the CG parameters are used).
 struct EvalStage { const double* X; int64_t ldx; double* G; int64_t ldg; };
-int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r, const JpArgs& z, const Batch& b) {
+int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r, const JpArgs& z, const Batch& b,
+                  const GnArgs* gn = nullptr) {
   towr_gpu_handle_s::AugLag& al = h->al;
   const int64_t ldv = ld16(h->L.nnz), ldr = ld16(h->L.m);
   const int C = chunk_plan(h, B);
@@ -347,6 +395,19 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
     if (rc == TOWR_OK) rc = launch_residual(h, cb, a, b.s);
     if (rc == TOWR_OK)
       rc = launch_product(h, true, cb, product(al.d_pv, ldv, a.LAMP, a.ldlp, z.Out + (int64_t)c0 * z.ldo, z.ldo, z.accumulate), b.s);
+    if (rc == TOWR_OK && gn) {
+      GnArgs g = *gn;
+      g.V = al.d_pv; g.ldv = ldv;
+      g.LAMP = a.LAMP; g.ldlp = a.ldlp;
+      g.RHO = a.RHO; g.rho = r.rho;
+      g.X = e.X + (int64_t)c0 * e.ldx; g.ldx = e.ldx;
+      g.GR = z.Out + (int64_t)c0 * z.ldo; g.ldgr = z.ldo;
+      g.XL = row_at(gn->XL, c0, gn->ldb); g.XU = row_at(gn->XU, c0, gn->ldb);
+      g.RUN = row_at(gn->RUN, c0, gn->run_stride);
+      g.D = gn->D + (int64_t)c0 * gn->ldd;
+      g.SUM = gn->SUM + (int64_t)c0 * gn->lds;
+      rc = launch_gn(h, cb, g, b.s);
+    }
   }
   return rc;
 }
@@ -674,6 +735,69 @@ int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t 
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
       if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
       if (rc == TOWR_OK) rc = launch_lbfgs_direction(h, B, dir, b.s);
+      if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
+    }
+    return rc;
+  });
+}
+
+// ---- the Gauss-Newton direction (jprod.hip) and the resident loop that uses it ------------------------------------------
+int towr_gpu_gn_direction_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, const double* V, int64_t ldv,
+                                       const double* LAMP, int64_t ldlp, const double* RHO, double rho, const double* X,
+                                       int64_t ldx, const double* GR, int64_t ldgr, const double* XL, const double* XU,
+                                       int64_t ldb, const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd, double* SUM,
+                                       int64_t lds, void* stream) {
+  if (!h || B < 0 || !V || !LAMP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null V, LAMP or GR, or B < 0)");
+  if (int rc = gn_params(h, gn, D, SUM, lds)) return rc;
+  const Layout& L = h->L;
+  if (!RHO && !(rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 without RHO");
+  if (ldv < L.nnz || ldlp < L.m || (X && ldx < L.n) || ldgr < L.n || ldd < L.n)
+    return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAMP) / n (X, GR, D)");
+  if (int rc = box_args(h, XL, XU, ldb, L.n, "XL / XU", "n")) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = gn_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = gn_ready(h)) return rc;
+  if (X && !XL)
+    if (int rc = step_ready(h)) return rc;
+  GnArgs a{V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN, run_stride, D, ldd, SUM, lds, gn->mu, gn->tol, gn->ncg, 0};
+  return launch_gn(h, B, a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// Per iteration what the public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag chunks
+// with the per-problem RHO accumulated onto GRC and, per chunk, the GN direction at (XC, GRC) into DC on the values still
+// in handle scratch (RUN = the phases: frozen problems are skipped), the line search, the outer update, the select
+// (D <- DC or GR by the flags) and the step.
+int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                             const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC,
+                                             double* GSUM, int64_t ldgs, const double* GL, const double* GU, int64_t ldgb,
+                                             const double* XL, const double* XU, int64_t ldxb, void* stream) {
+  if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
+  if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
+  if (int rc = gn_params(h, gn, DC, GSUM, ldgs)) return rc;
+  const towr_alsolve_state_t& st = *state;
+  ResArgs r{nullptr, 0, GL, GU, ldgb, st.LAM, st.ldl, st.LAMP, st.ldl, st.RSUM, st.ldrs};
+  r.rho = 1.0;
+  r.RHO = st.RHO;
+  GnArgs g{};   // (V, LAMP, RHO, X and GR: the chunk's, auglag_chunks)
+  g.XL = XL; g.XU = XU; g.ldb = ldxb;
+  g.RUN = st.ISTATE; g.run_stride = 4;
+  g.D = DC; g.ldd = st.ldx; g.SUM = GSUM; g.lds = ldgs;
+  g.mu = gn->mu; g.tol = gn->tol; g.ncg = gn->ncg;
+  const StepArgs step{st.X, st.ldx, st.D, st.ldx, st.ALPHA, 0.0, XL, XU, ldxb, st.XC, st.ldx, st.SSUM, st.ldss};
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (int rc = gn_fits(h)) return rc;
+  if (iters == 0) return TOWR_OK;
+  return fused(h, B, stream, {gn_ready, residual_ready, step_ready}, [&](const Batch& b) {
+    int rc = TOWR_OK;
+    for (int it = 0; it < iters && rc == TOWR_OK; ++it) {
+      rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
+      if (rc == TOWR_OK)
+        rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b, &g);
+      if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
+      if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
+      if (rc == TOWR_OK) rc = launch_gn_select(h, B, st, DC, b.s);
       if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
     }
     return rc;

@@ -147,6 +147,7 @@ struct towr_gpu_handle_s {
     double* d_pv = nullptr;
     int64_t pv_cap = 0;
     int32_t products_chunk = 0;
+    bool gn_ready = false;   // the GN direction kernel's LDS fits and its limit is raised (gn_ready; after products_ready)
     // Residuals (resid.hip): the device copies of the constraint sets' row ranges and of the description bounds
     // (residual_ready), and the fused entries' g / lam+ scratch (a chunk of problems)
     bool res_ready = false;

@@ -12,8 +12,13 @@
 //           the chunk's partial is added to the column's running sum in LDS, chunks in ascending order.
 // Every output element is one fixed tree of IEEE additions over exactly its own entries — no atomics, nothing that
 // depends on B, the block's place in the grid, the stream or timing — so the bits are a function of the problem alone.
+// Behind them: the Gauss-Newton direction (towr_gpu_gn_direction_batch_device), a whole CG solve per block on the same
+// walk and trees.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "consumer_common.h"
 #include "layout.h"
 
 namespace tg {
@@ -143,7 +148,288 @@ __global__ void __launch_bounds__(kJpBlock) towr_jac_tvec_kernel(JpArgs a) {
   }
 }
 
+// ---- the Gauss-Newton direction (towr_gpu_gn_direction_batch_device) ---------------------------------------------------
+// One block of kGnBlock threads per problem (twice the product kernels': the vectors' LDS admits two blocks per CU, and
+// 16 waves hide the walk better than 8) stays resident for the whole CG solve on H = rho (J^T W J)_ff + mu I.
+// Every step is the J p pass
+// and the J^T t pass of the two kernels above over the problem's values — the same chunk walk, tiles, carries and segment
+// trees — with the vectors kept in LDS between the passes instead of going through global memory: the first pass
+// brings the values from HBM, the later ones find them in the caches (plain loads here, not non-temporal ones).
+// Lane l owns columns l, l + kGnBlock, ... for everything that is per column (the held bit, p, r, Hp, d in the D row),
+// so those updates need no barrier among themselves; a barrier stands between an update of p and the next J p pass.
+// The dot products are block_sums of lbfgs.hip: the lane's partial in column order, a fixed shuffle tree, the waves'
+// partials added in wave order by one lane, the scalar broadcast through LDS — every lane takes the stop decisions on
+// the same bits. Contraction is off: every product and sum is the plain IEEE expression the header states.
+constexpr int kGnPer = kJpChunk / kGnBlock;   // entries per lane and chunk
+constexpr int kGnWaves = kGnBlock / 64;
+static_assert(kJpChunk % kGnBlock == 0 && (sizeof(uint16_t) * kJpChunk / kGnBlock == 8 || sizeof(uint16_t) * kJpChunk / kGnBlock == 16),
+              "a lane stages 4 or 8 by-column positions per chunk");
+using GnCx = std::conditional<kGnPer == 4, uint2, uint4>::type;   // the lane's share of a chunk's by-column list
+
+template <int K>
+__device__ inline void gn_block_sums(double (&v)[K], double (*s_part)[kGnWaves], double* s_bc, int tid) {
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] += __shfl_down(v[k], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_part[k][tid >> 6] = v[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      double t = s_part[k][0];
+      for (int w = 1; w < kGnWaves; ++w) t += s_part[k][w];
+      s_bc[k] = t;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = s_bc[k];
+}
+
+// A block runs few at a time per CU (its LDS), so the walk's dependent table loads are not hidden by other blocks as
+// in the product kernels: the chunk descriptors are read two chunks ahead and lane tid's first short segment and its
+// wave's first long one a chunk ahead (the sums and their order are unchanged).
+struct GnSegs { JpSeg s, l; };
+__device__ inline GnSegs gn_fetch(const JpSeg* seg, int s0, int ns, int nl, int tid) {
+  GnSegs f{};
+  if (tid < ns) f.s = seg[s0 + tid];
+  if ((tid >> 6) < nl) f.l = seg[s0 + ns + (tid >> 6)];
+  return f;
+}
+
+// t = w .* (J p): towr_jac_vec_kernel's walk with p in LDS and the row's sum scaled by its weight into t (LDS). The
+// caller's barrier stands before it (p complete, the tile free); it ends behind its own last barrier.
+__device__ inline void gn_jp_pass(const JpArgs& a, const double* Vb, const double* p, double* tile, double* carry, double* t,
+                                  const uint8_t* act, int tid) {
+#pragma clang fp contract(off)
+  double v[kGnPer];
+  int32_t c[kGnPer];
+#pragma unroll
+  for (int i = 0; i < kGnPer; ++i) {
+    const int64_t k = (int64_t)i * kGnBlock + tid;
+    v[i] = 0.0; c[i] = 0;
+    if (k < a.nnz) { v[i] = Vb[k]; c[i] = a.col[k]; }
+  }
+  const JpChunk none{};
+  JpChunk ch = a.n_chunks > 0 ? a.chunks[0] : none, nx = a.n_chunks > 1 ? a.chunks[1] : none;
+  GnSegs cur = gn_fetch(a.rseg, ch.rs0, ch.rns, ch.rnl, tid);
+  for (int ci = 0; ci < a.n_chunks; ++ci) {
+    const int64_t k0 = (int64_t)ci * kJpChunk;
+#pragma unroll
+    for (int i = 0; i < kGnPer; ++i)
+      if (k0 + i * kGnBlock + tid < a.nnz) tile[i * kGnBlock + tid] = v[i] * p[c[i]];
+#pragma unroll
+    for (int i = 0; i < kGnPer; ++i) {
+      const int64_t k = k0 + kJpChunk + (int64_t)i * kGnBlock + tid;
+      if (k < a.nnz) { v[i] = Vb[k]; c[i] = a.col[k]; }
+    }
+    const JpChunk n2 = ci + 2 < a.n_chunks ? a.chunks[ci + 2] : none;
+    const GnSegs nxt = gn_fetch(a.rseg, nx.rs0, nx.rns, nx.rnl, tid);   // (no chunk: no segments, nothing is read)
+    __syncthreads();
+    auto finish = [&](const JpSeg& s, double sum) {
+      if (s.flags & 1) sum = carry[(ci & 1) ^ 1] + sum;
+      if (s.flags & 2) carry[ci & 1] = sum;
+      else t[s.out] = (act[s.out] ? 1.0 : 0.0) * sum;
+    };
+    for (int q = tid; q < ch.rns; q += kGnBlock) {
+      const JpSeg s = q == tid ? cur.s : a.rseg[ch.rs0 + q];
+      finish(s, seg_sum<false, false>(s, tile, nullptr));
+    }
+    for (int q = tid >> 6; q < ch.rnl; q += kGnBlock / 64) {
+      const JpSeg s = q == (tid >> 6) ? cur.l : a.rseg[ch.rs0 + ch.rns + q];
+      const double sum = seg_sum<true, false>(s, tile, nullptr);
+      if ((tid & 63) == 0) finish(s, sum);
+    }
+    __syncthreads();
+    ch = nx; nx = n2; cur = nxt;
+  }
+}
+
+// z += J^T t: towr_jac_tvec_kernel's walk with t and the columns' running sums z in LDS (z zeroed by the caller, before
+// a barrier). Ends behind its own last barrier.
+__device__ inline void gn_jtt_pass(const JpArgs& a, const double* Vb, const double* t, double* z, double* tile, uint16_t* cidx,
+                                   int tid) {
+#pragma clang fp contract(off)
+  double v[kGnPer];
+  int32_t r[kGnPer];
+  GnCx cx{};
+#pragma unroll
+  for (int i = 0; i < kGnPer; ++i) {
+    const int64_t k = (int64_t)i * kGnBlock + tid;
+    v[i] = 0.0; r[i] = 0;
+    if (k < a.nnz) { v[i] = Vb[k]; r[i] = a.row[k]; }
+  }
+  if (a.n_chunks > 0) cx = reinterpret_cast<const GnCx*>(a.cidx)[tid];
+  const JpChunk none{};
+  JpChunk ch = a.n_chunks > 0 ? a.chunks[0] : none, nx = a.n_chunks > 1 ? a.chunks[1] : none;
+  GnSegs cur = gn_fetch(a.cseg, ch.cs0, ch.cns, ch.cnl, tid);
+  for (int ci = 0; ci < a.n_chunks; ++ci) {
+    const int64_t k0 = (int64_t)ci * kJpChunk;
+#pragma unroll
+    for (int i = 0; i < kGnPer; ++i)
+      if (k0 + i * kGnBlock + tid < a.nnz) tile[i * kGnBlock + tid] = v[i] * t[r[i]];
+    reinterpret_cast<GnCx*>(cidx)[tid] = cx;
+#pragma unroll
+    for (int i = 0; i < kGnPer; ++i) {
+      const int64_t k = k0 + kJpChunk + (int64_t)i * kGnBlock + tid;
+      if (k < a.nnz) { v[i] = Vb[k]; r[i] = a.row[k]; }
+    }
+    if (ci + 1 < a.n_chunks) cx = reinterpret_cast<const GnCx*>(a.cidx + k0 + kJpChunk)[tid];
+    const JpChunk n2 = ci + 2 < a.n_chunks ? a.chunks[ci + 2] : none;
+    const GnSegs nxt = gn_fetch(a.cseg, nx.cs0, nx.cns, nx.cnl, tid);
+    __syncthreads();
+    for (int q = tid; q < ch.cns; q += kGnBlock) {
+      const JpSeg s = q == tid ? cur.s : a.cseg[ch.cs0 + q];
+      z[s.out] += seg_sum<false, true>(s, tile, cidx);
+    }
+    for (int q = tid >> 6; q < ch.cnl; q += kGnBlock / 64) {
+      const JpSeg s = q == (tid >> 6) ? cur.l : a.cseg[ch.cs0 + ch.cns + q];
+      const double sum = seg_sum<true, true>(s, tile, cidx);
+      if ((tid & 63) == 0) z[s.out] += sum;
+    }
+    __syncthreads();
+    ch = nx; nx = n2; cur = nxt;
+  }
+}
+
+__global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double s_part[2][kGnWaves], s_bc[2];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  if (a.RUN && a.RUN[b * a.run_stride] >= 2) return;   // (block-uniform: before any barrier)
+  const JpArgs& T = a.jp;
+  const int n = T.n, m = T.m;
+  const int n2 = (n + 1) & ~1, m2 = (m + 1) & ~1;
+  double* p = jp_lds;                 // n (padded): 0 on held columns
+  double* r = p + n2;                 // n
+  double* z = r + n2;                 // n: the columns' running sums of J^T t, then H p
+  double* t = z + n2;                 // m
+  double* tile = t + m2;              // kJpChunk products
+  double* carry = tile + kJpChunk;    // 2
+  uint16_t* cidx = reinterpret_cast<uint16_t*>(carry + 2);   // the chunk's by-column list (16-byte aligned)
+  uint8_t* act = reinterpret_cast<uint8_t*>(cidx + kJpChunk);   // m: the row is active (w = 1)
+  const double* Vb = a.V + b * a.ldv;
+  const double* Gb = a.GR + b * a.ldgr;
+  const double* LPb = a.LAMP + b * a.ldlp;
+  double* Db = a.D + b * a.ldd;
+  const double rho = a.RHO ? a.RHO[b] : a.rho;
+  const double mu = a.mu;
+  const double tol2 = a.tol * a.tol;
+
+  // the held mask (bit k: the lane's k-th column), r = p = g on free columns, bb = sum_free g^2
+  unsigned held = 0u;
+  double v2[2] = {0.0, 0.0};   // bb, the held count (integers below 2^53: exact in any order)
+  {
+    const double* Xb = a.X ? a.X + b * a.ldx : nullptr;
+    const double* Lb = a.X ? a.XL + b * a.ldb : nullptr;
+    const double* Ub = a.X ? a.XU + b * a.ldb : nullptr;
+    int k = 0;
+    for (int j = tid; j < n; j += kGnBlock, ++k) {
+      const double g = Gb[j];
+      bool h = false;
+      if (Xb) {
+        const double x = Xb[j], l = Lb[j], u = Ub[j];
+        const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+        h = (has_l && x <= l && g > 0.0) || (has_u && x >= u && g < 0.0) || (has_l && has_u && l == u);
+      }
+      if (h) {
+        held |= 1u << k;
+        v2[1] += 1.0;
+        p[j] = 0.0;
+        r[j] = 0.0;
+      } else {
+        v2[0] += g * g;
+        p[j] = g;
+        r[j] = g;
+      }
+    }
+  }
+  for (int i = tid; i < m; i += kGnBlock) act[i] = LPb[i] != 0.0;   // (a NaN is active)
+  for (int i = tid; i < T.n_empty; i += kGnBlock) t[T.empty_rows[i]] = 0.0;   // rows without entries: never written again
+  gn_block_sums<2>(v2, s_part, s_bc, tid);   // (its barriers: p, act and t are complete)
+  const double bb = v2[0], nheld = v2[1];
+
+  double rr = bb;
+  int steps = 0, code = 0;
+  if (bb == 0.0) code = 3;
+  else {
+    for (int it = 0; it < a.ncg; ++it) {
+      if (rr <= tol2 * bb) { code = 1; break; }   // (a NaN goes on to the curvature test, which ends on it)
+      for (int j = tid; j < n; j += kGnBlock) z[j] = 0.0;
+      gn_jp_pass(T, Vb, p, tile, carry, t, act, tid);
+      __syncthreads();   // (also without a chunk: z is zero before the sums below)
+      gn_jtt_pass(T, Vb, t, z, tile, cidx, tid);
+      double s1[1] = {0.0};   // sum_free p Hp
+      int k = 0;
+      for (int j = tid; j < n; j += kGnBlock, ++k) {
+        double hp = 0.0;
+        if (!((held >> k) & 1u)) {
+          const double pj = p[j];
+          hp = rho * z[j] + mu * pj;
+          s1[0] += pj * hp;
+        }
+        z[j] = hp;
+      }
+      gn_block_sums<1>(s1, s_part, s_bc, tid);
+      if (!(s1[0] > 0.0)) { code = 2; break; }   // (a NaN anywhere ends here)
+      const double al = rr / s1[0];
+      double s2[1] = {0.0};   // sum_free r r
+      k = 0;
+      for (int j = tid; j < n; j += kGnBlock, ++k) {
+        if ((held >> k) & 1u) continue;
+        const double d0 = steps ? Db[j] : 0.0;
+        Db[j] = d0 + al * p[j];
+        const double rj = r[j] - al * z[j];
+        r[j] = rj;
+        s2[0] += rj * rj;
+      }
+      gn_block_sums<1>(s2, s_part, s_bc, tid);
+      const double beta = s2[0] / rr;
+      k = 0;
+      for (int j = tid; j < n; j += kGnBlock, ++k)
+        if (!((held >> k) & 1u)) p[j] = r[j] + beta * p[j];
+      rr = s2[0];
+      ++steps;
+      __syncthreads();   // p is complete before the next pass reads it
+    }
+  }
+
+  // D on the held columns (or everywhere when no step completed) and the slope sum g D over all columns
+  double w[1] = {0.0};
+  {
+    int k = 0;
+    for (int j = tid; j < n; j += kGnBlock, ++k) {
+      const double g = Gb[j];
+      double d = g;
+      if (steps && !((held >> k) & 1u)) d = Db[j];
+      else Db[j] = g;
+      w[0] += g * d;
+    }
+  }
+  gn_block_sums<1>(w, s_part, s_bc, tid);
+  if (tid == 0) {
+    double* Sb = a.SUM + b * a.lds;
+    Sb[0] = (double)steps;
+    Sb[1] = bb;
+    Sb[2] = rr;
+    Sb[3] = w[0];
+    Sb[4] = nheld;
+    Sb[5] = (double)code;
+  }
+}
+
 }  // namespace
+
+size_t gn_direction_lds(int n, int m) {
+  return sizeof(double) * (size_t)(3 * ((n + 1) & ~1) + ((m + 1) & ~1) + kJpChunk + 2) + sizeof(uint16_t) * kJpChunk +
+         (size_t)((m + 15) & ~15);
+}
+const void* gn_direction_kernel() { return reinterpret_cast<const void*>(&towr_gn_direction_kernel); }
 
 size_t jp_vec_lds(int n, int m) { return sizeof(double) * (size_t)(((n + 1) & ~1) + kJpChunk + 2); }
 size_t jp_tvec_lds(int n, int m) {

@@ -460,6 +460,41 @@ size_t jp_tvec_lds(int n, int m);
 const void* jp_vec_kernel();
 const void* jp_tvec_kernel();
 
+// The Gauss-Newton direction (jprod.hip, towr_gpu_gn_direction_batch_device): one block of kGnBlock threads per problem
+// runs the whole CG solve on (rho J^T W J)_ff + mu I, every step one J p and one J^T t pass over the problem's values
+// with the product kernels' tables (jp: products_ready's; its operand members are not used). p, r, the column
+// accumulator (n each), t (m), the chunk tile, the by-column list and the active-row bytes live in dynamic LDS
+// (gn_direction_lds); d lives in the D row. XL / XU / ldb as in StepArgs (X NULL: every column free, bounds not read).
+struct GnArgs {
+  const double* V; int64_t ldv;
+  const double* LAMP; int64_t ldlp;
+  const double* RHO; double rho;       // RHO[b], or the scalar when RHO is NULL
+  const double* X; int64_t ldx;
+  const double* GR; int64_t ldgr;
+  const double *XL, *XU; int64_t ldb;
+  const int32_t* RUN; int64_t run_stride;   // a block whose RUN[b*run_stride] >= 2 returns at once; NULL: every block runs
+  double* D; int64_t ldd;
+  double* SUM; int64_t lds;
+  double mu, tol;
+  int32_t ncg, reserved;
+  JpArgs jp;
+};
+constexpr int kGnBlock = 512;            // twice the product kernels' block: its LDS admits two blocks per CU
+constexpr int kGnMaxN = 32 * kGnBlock;   // the held mask is one 32-bit word per lane
+size_t gn_direction_lds(int n, int m);   // dynamic LDS (bytes)
+const void* gn_direction_kernel();
+
+// The resident GN loop's select (lbfgs.hip): per problem by the flags the line search wrote, D <- DC (bit 0), else
+// D <- GR (bit 2), else nothing; one block of kLbfgsBlock threads per problem.
+struct GnSelectArgs {
+  const int32_t* ISTATE;
+  const double* DC; int64_t lddc;
+  const double* GR; int64_t ldgr;
+  double* D; int64_t ldd;
+  int32_t n, reserved;
+};
+const void* gn_select_kernel();
+
 #ifndef TOWR_COST_SLOT_MAX   // (experiment builds: -DTOWR_COST_SLOT_MAX=0, the limbs everywhere)
 #define TOWR_COST_SLOT_MAX 8192
 #endif

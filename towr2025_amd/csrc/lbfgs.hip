@@ -476,8 +476,23 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_init_kernel(AlInitAr
   Sc[3] = a.omega0;
 }
 
+// The select of the resident GN loop (towr_gpu_alsolve_gn_iterate_batch_device): by the flags the line search wrote,
+// D <- DC when a base was accepted (bit 0), else D <- GR when the history was reset (bit 2: the steepest-descent retry),
+// else nothing. Copies only; every lane reads the flags, which no kernel writes meanwhile.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_gn_select_kernel(GnSelectArgs a) {
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int flags = a.ISTATE[4 * b + 1];
+  if (!(flags & (1 | 4))) return;
+  const double* Sb = (flags & 1) ? a.DC + b * a.lddc : a.GR + b * a.ldgr;
+  double* Db = a.D + b * a.ldd;
+#pragma unroll 4
+  for (int j = tid; j < a.n; j += kLbfgsBlock) Db[j] = Sb[j];
+}
+
 }  // namespace
 
+const void* gn_select_kernel() { return reinterpret_cast<const void*>(&towr_gn_select_kernel); }
 const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }
 const void* linesearch_kernel() { return reinterpret_cast<const void*>(&towr_linesearch_kernel); }

@@ -182,6 +182,20 @@ class Engine {
                      const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb, void* stream) const {
     return towr_gpu_alsolve_iterate_batch_device(h_, B, iters, &params, &state, GL, GU, ldgb, XL, XU, ldxb, stream);
   }
+  // the Gauss-Newton (CG) direction and the resident iteration that uses it (towr_gpu.h)
+  int GnDirectionBatchDevice(int B, const towr_gn_params_t& gn, const double* V, int64_t ldv, const double* LAMP, int64_t ldlp,
+                             const double* RHO, double rho, const double* X, int64_t ldx, const double* GR, int64_t ldgr,
+                             const double* XL, const double* XU, int64_t ldb, const int32_t* RUN, int32_t run_stride, double* D,
+                             int64_t ldd, double* SUM, int64_t lds, void* stream) const {
+    return towr_gpu_gn_direction_batch_device(h_, B, &gn, V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN,
+                                              run_stride, D, ldd, SUM, lds, stream);
+  }
+  int AlsolveGnIterate(int B, int iters, const towr_alsolve_params_t& params, const towr_alsolve_state_t& state,
+                       const towr_gn_params_t& gn, double* DC, double* GSUM, int64_t ldgs, const double* GL, const double* GU,
+                       int64_t ldgb, const double* XL, const double* XU, int64_t ldxb, void* stream) const {
+    return towr_gpu_alsolve_gn_iterate_batch_device(h_, B, iters, &params, &state, &gn, DC, GSUM, ldgs, GL, GU, ldgb, XL, XU,
+                                                    ldxb, stream);
+  }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // the objective kernel's persistent grid (towr_gpu_set_cost_grid / towr_gpu_cost_grid); 0 = automatic
   void SetCostGrid(int blocks) const { Check(towr_gpu_set_cost_grid(h_, blocks)); }

@@ -76,6 +76,12 @@ def alsolve_params(**kw) -> capi.AlSolveParams:
     return capi.AlSolveParams(**{**AL_PARAM_DEFAULTS, **kw})
 
 
+def gn_params(ncg=8, mu=0.0, tol=0.0) -> capi.GnParams:
+    """towr_gn_params_t: at most ncg CG steps, the damping mu, the relative residual tolerance tol; the C-ABI checks
+    the ranges."""
+    return capi.GnParams(ncg=int(ncg), reserved=0, mu=float(mu), tol=float(tol))
+
+
 class AlSolveState:
     """The tensors of towr_alsolve_state_t (towr_gpu.h) for B problems and `mem` pairs; allocate() makes them (zeros) on
     the problem's device. X holds the starting points and LAM the starting multipliers before alsolve_init."""
@@ -662,6 +668,51 @@ class TowrGpuProblem:
         xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
         self._check(self._lib.towr_gpu_alsolve_iterate_batch_device(self._h, st.B, int(iters), C.byref(params), C.byref(c),
                                                                     gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
+
+    # -------------------------------------------------------------------- Gauss-Newton -------
+    def gn_direction_batch_device(self, gn, V, LAMP, GR, D, SUM, rho=1.0, X=None, XL=None, XU=None, RUN=None, run_stride=1,
+                                  stream=None):
+        """D[b] = the truncated CG solution of (rho_b (J^T W J)_ff + mu I) d = g on the free columns (held columns:
+        D = GR), J_b the CSR values V[b], W the rows whose LAMP is not zero, g = GR[b]; gn: gn_params(...). rho: a float
+        or a 1-D tensor of B values. X None: every column is free. XL / XU: None (the handle's bounds), 1-D (shared) or
+        (B, >= n). RUN: None, or an int32 tensor; problem b is skipped when RUN[b * run_stride] >= 2. SUM (B, >= 6):
+        steps, bb, rr, slope sum g D, held columns, stop code (towr_gpu.h)."""
+        import torch
+        B = GR.shape[0]
+        ops = [(V, "V", self.nnz), (LAMP, "LAMP", self.m), (GR, "GR", self.n), (D, "D", self.n), (SUM, "SUM", 6)]
+        if X is not None:
+            ops.append((X, "X", self.n))
+        self._check_rows(B, *ops)
+        xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        if isinstance(rho, (int, float)):
+            rp, r = C.c_void_p(None), float(rho)
+        else:
+            _check_per_problem(rho, "RHO", B, self.device)
+            rp, r = C.c_void_p(rho.data_ptr()), 0.0
+        run = C.c_void_p(None)
+        if RUN is not None:
+            if RUN.dtype != torch.int32 or RUN.device.type != "cuda" or RUN.device.index != self.device or not RUN.is_contiguous() \
+                    or run_stride < 1 or RUN.numel() < (B - 1) * run_stride + 1:
+                raise TowrGpuError("RUN: expected a contiguous int32 tensor of >= (B - 1) run_stride + 1 entries on the handle's device")
+            run = C.c_void_p(RUN.data_ptr())
+        self._check(self._lib.towr_gpu_gn_direction_batch_device(
+            self._h, B, C.byref(gn), *_opt(V), *_opt(LAMP), rp, r, *_opt(X), *_opt(GR), xl, xu, ldb, run, int(run_stride),
+            *_opt(D), *_opt(SUM), self._stream(stream, GR)))
+
+    def alsolve_gn_iterate(self, params, st, gn, DC, GSUM, iters=1, GL=None, GU=None, XL=None, XU=None, stream=None):
+        """alsolve_iterate with the Gauss-Newton direction: per iteration the evaluation, the CG solve at the candidate
+        into DC (B, the leading dimension of st.X) and GSUM (B, >= 6), the line search, the outer update, the select
+        (st.D <- DC on an accepted base, st.GR on the one steepest-descent retry) and the step, with no host
+        synchronisation (towr_gpu.h)."""
+        c = self._alsolve_state(st, params)
+        self._check_rows(st.B, (DC, "DC", self.n), (GSUM, "GSUM", 6))
+        if DC.stride(0) != st.X.stride(0):
+            raise TowrGpuError("X and DC: they share one leading dimension")
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        self._check(self._lib.towr_gpu_alsolve_gn_iterate_batch_device(
+            self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
+            gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
