@@ -244,3 +244,52 @@ def anymal_long_gait(n_phases=17, phase=0.2):
         f.params_.ee_phase_durations_[ee] = [phase] * n_phases
         f.params_.ee_in_contact_at_start_[ee] = True
     return f.to_desc()
+
+
+def many_short_rows(rows=1500):
+    """(ProblemDesc, side data): the procedural monoped with one more LinearEquality set on variable set 0 (base-lin),
+    `rows` rows of one or two nonzeros each drawn with default_rng(5) — more short row segments in one chunk of the
+    Jacobian products' tables than any formulation of the repository has (at 1500 rows: more than twice the block of the
+    Gauss-Newton direction kernel, so a lane walks three of them; at 700: a few more than one block)."""
+    import numpy as np
+    from towr2025_amd import _capi as capi
+    f, vs, cs, goal, T = F.procedural_monoped()
+    d0 = f.to_desc(varsets=vs, constraints=cs, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)
+    cols = _varset_cols(d0)[0][1]
+    rng = np.random.default_rng(5)
+    M = np.zeros((rows, cols))
+    count = rng.integers(1, 3, rows)
+    for i in range(rows):
+        c = rng.choice(cols, count[i], replace=False)
+        M[i, c] = rng.uniform(0.5, 1.5, count[i]) * rng.choice([-1.0, 1.0], count[i])
+    cs2 = cs + [dict(kind=capi.C_LINEAR_EQ, ip=[0, rows])]
+    d = f.to_desc(varsets=vs, constraints=cs2, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)
+    return d, [(capi.DATA_LINEAR_M, len(cs), M)]
+
+
+def many_short_columns(chunk=2048):
+    """(ProblemDesc, side data): ANYmal's trot with one LinearEquality set per variable set whose matrix is the
+    identity (one entry per row and column), behind a LinearEquality set of single-entry rows that pads the Jacobian's
+    entries to a multiple of `chunk` (the products' chunk length) — so one chunk of the product tables holds all n
+    columns as short segments: more than twice the block of the Gauss-Newton direction kernel, which no formulation of
+    the repository reaches on the column side."""
+    import numpy as np
+    from towr2025_amd import TowrGpuProblem
+    from towr2025_amd import _capi as capi
+    f = F.anymal_trot()
+    cs = f.constraint_sets()
+    nnz0 = TowrGpuProblem(f.to_desc(), device=-1).sizes()[2]
+    cols = [n for _, n in _varset_cols(f.to_desc())]
+    pad = (-nnz0) % chunk
+    rng = np.random.default_rng(6)
+    sets, data = [], []
+    if pad:
+        M = np.zeros((pad, cols[0]))
+        M[np.arange(pad), np.arange(pad) % cols[0]] = rng.uniform(0.5, 1.5, pad)
+        sets.append(dict(kind=capi.C_LINEAR_EQ, ip=[0, pad]))
+        data.append(M)
+    for v, k in enumerate(cols):
+        sets.append(dict(kind=capi.C_LINEAR_EQ, ip=[v, k]))
+        data.append(np.diag(rng.uniform(0.5, 1.5, k) * rng.choice([-1.0, 1.0], k)))
+    d = f.to_desc(constraints=cs + sets)
+    return d, [(capi.DATA_LINEAR_M, len(cs) + i, M) for i, M in enumerate(data)]

@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE ONLY — host emulation of towr_eval_kernel's per-item loop, used by the
 // CPU test suite to check engine_math.h values against the oracle before GPU runs. It is built
 // into tests/host_emu/build/libemu.so and is never linked into or loaded by the product.
+#include "../../towr2025_amd/csrc/consumer_common.h"
 #include "../../towr2025_amd/csrc/gs_cls.h"
 #include "../../towr2025_amd/csrc/layout.h"
 
@@ -391,16 +392,18 @@ extern "C" int emu_traj(const towr_problem_desc_t* d, const double* x, double dt
 }
 
 // The product tables of build_jprod (Layout::jp_chunks, jp_rseg, jp_cseg, jp_cidx, jp_empty_rows, jp_row) as plain
-// arrays. sizes (9): chunks, row segments, column segments, empty rows, jp_long, kJpChunk, nnz, m, n. An output that
+// arrays. sizes (10): chunks, row segments, column segments, empty rows, jp_long, kJpChunk, nnz, m, n, kGnBlock. An output that
 // is null is skipped (a first call with all of them null gives the sizes to allocate). chunks: {rs0, rns, rnl, cs0,
 // cns, cnl} per chunk; rseg / cseg: {out, q0, len, flags} per segment; cidx: kJpChunk entries per chunk.
-extern "C" int emu_jp_tables(const towr_problem_desc_t* d, int64_t* sizes, int32_t* chunks, int32_t* rseg, int32_t* cseg,
-                             uint16_t* cidx, int32_t* empty_rows, int32_t* row) {
+// emu_jp_tables_ex: the same for a description with side data, and a tenth size: kGnBlock (the block of
+// towr_gn_direction_kernel, by which the tests classify that kernel's branches without a constant of their own).
+extern "C" int emu_jp_tables_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, int64_t* sizes, int32_t* chunks,
+                                int32_t* rseg, int32_t* cseg, uint16_t* cidx, int32_t* empty_rows, int32_t* row) {
   Layout L; std::string e;
-  if (build_layout(*d, L, e)) return -1;
-  const int64_t sz[9] = {(int64_t)L.jp_chunks.size(), (int64_t)L.jp_rseg.size(), (int64_t)L.jp_cseg.size(),
-                         (int64_t)L.jp_empty_rows.size(), L.jp_long, kJpChunk, L.nnz, L.m, L.n};
-  for (int i = 0; i < 9; ++i) sizes[i] = sz[i];
+  if (build_layout_ex(*d, n_data, data, L, e)) return -1;
+  const int64_t sz[10] = {(int64_t)L.jp_chunks.size(), (int64_t)L.jp_rseg.size(), (int64_t)L.jp_cseg.size(),
+                          (int64_t)L.jp_empty_rows.size(), L.jp_long, kJpChunk, L.nnz, L.m, L.n, kGnBlock};
+  for (int i = 0; i < 10; ++i) sizes[i] = sz[i];
   if (chunks)
     for (size_t c = 0; c < L.jp_chunks.size(); ++c) {
       const JpChunk& ch = L.jp_chunks[c];
@@ -418,6 +421,10 @@ extern "C" int emu_jp_tables(const towr_problem_desc_t* d, int64_t* sizes, int32
   if (empty_rows) std::copy(L.jp_empty_rows.begin(), L.jp_empty_rows.end(), empty_rows);
   if (row) std::copy(L.jp_row.begin(), L.jp_row.end(), row);
   return 0;
+}
+extern "C" int emu_jp_tables(const towr_problem_desc_t* d, int64_t* sizes, int32_t* chunks, int32_t* rseg, int32_t* cseg,
+                             uint16_t* cidx, int32_t* empty_rows, int32_t* row) {
+  return emu_jp_tables_ex(d, 0, nullptr, sizes, chunks, rseg, cseg, cidx, empty_rows, row);
 }
 
 // The two product kernels of jprod.hip for one problem, as a host walk of the same tables in the same order, so that
@@ -487,6 +494,137 @@ extern "C" int emu_jac_products_ex(const towr_problem_desc_t* d, int n_data, con
 extern "C" int emu_jac_products(const towr_problem_desc_t* d, const double* V, const double* P, const double* LAM,
                                 const double* Z0, double* Y, double* Z, double* Za) {
   return emu_jac_products_ex(d, 0, nullptr, V, P, LAM, Z0, Y, Z, Za);
+}
+
+// towr_gn_direction_kernel (jprod.hip) for one problem, operation for operation: the held rule, act (a NaN is active),
+// and per CG step t = act .* (J p) through the row segments with their carries (t = 0 on empty rows), z = J^T t through
+// the column segments into running sums in chunk order, hp = rho z + mu p on the free columns, the dot products,
+// al = rr / pHp, the updates of D, r and p, and the stop tests in the kernel's order and form; then D on the held
+// columns (everywhere when no step completed), the slope and the six SUM entries. Every dot product is the kernel's
+// tree: lane l's partial over its columns l, l + kGnBlock, ... in order from 0.0, the 64-lane __shfl_down tree of
+// each wave (offsets 32..1, lane 0's value), the waves' partials added in wave order. X null: every column is free
+// (XL / XU are not read). The tile is refilled with NaN before every chunk of every pass and the carries before every
+// pass: a segment that reads what its chunk did not write, or a carry not handed on, shows as NaN in D.
+// Returns 0; -1: the layout failed; -2: n is past the kernel's held mask (kGnMaxN).
+namespace {
+double gn_block_sum(const std::vector<double>& lane) {   // lane: kGnBlock partials
+  double part[kGnBlock / 64];
+  for (int w = 0; w < kGnBlock / 64; ++w) {
+    double v[64];
+    for (int l = 0; l < 64; ++l) v[l] = lane[(size_t)w * 64 + l];
+    for (int o = 32; o > 0; o >>= 1)
+      for (int l = 0; l < o; ++l) v[l] += v[l + o];
+    part[w] = v[0];
+  }
+  double t = part[0];
+  for (int w = 1; w < kGnBlock / 64; ++w) t += part[w];
+  return t;
+}
+}
+extern "C" int emu_gn_direction_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, const double* V,
+                                   const double* LAMP, const double* GR, const double* X, const double* XL, const double* XU,
+                                   double rho, double mu, double tol, int ncg, double* D, double* SUM) {
+  Layout L; std::string e;
+  if (build_layout_ex(*d, n_data, data, L, e)) return -1;
+  if (L.n > kGnMaxN) return -2;
+  const int n = L.n, m = L.m, n_chunks = (int)L.jp_chunks.size();
+  const double nan = std::nan("");
+  std::vector<double> p((size_t)n), r((size_t)n), z((size_t)n), t((size_t)m, nan), tile((size_t)kJpChunk), lane((size_t)kGnBlock);
+  std::vector<uint8_t> held((size_t)n, 0), act((size_t)m);
+  const double tol2 = tol * tol;
+  // term(j, acc) on lane tid's columns in the lane's order (acc: its partial), then the block's tree
+  auto lane_sums = [&](auto&& term) {
+    for (int tid = 0; tid < kGnBlock; ++tid) {
+      double acc = 0.0;
+      for (int j = tid; j < n; j += kGnBlock) term(j, acc);
+      lane[(size_t)tid] = acc;
+    }
+    return gn_block_sum(lane);
+  };
+
+  for (int j = 0; j < n; ++j) {
+    const double g = GR[j];
+    bool h = false;
+    if (X) {
+      const double x = X[j], l = XL[j], u = XU[j];
+      const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+      h = (has_l && x <= l && g > 0.0) || (has_u && x >= u && g < 0.0) || (has_l && has_u && l == u);
+    }
+    held[(size_t)j] = h;
+    p[(size_t)j] = r[(size_t)j] = h ? 0.0 : g;
+  }
+  const double bb = lane_sums([&](int j, double& acc) { if (!held[(size_t)j]) acc += GR[j] * GR[j]; });
+  const double nheld = lane_sums([&](int j, double& acc) { if (held[(size_t)j]) acc += 1.0; });
+  for (int i = 0; i < m; ++i) act[(size_t)i] = LAMP[i] != 0.0;
+  for (int32_t i : L.jp_empty_rows) t[(size_t)i] = 0.0;
+
+  double rr = bb;
+  int steps = 0, code = 0;
+  if (bb == 0.0) code = 3;
+  else {
+    for (int it = 0; it < ncg; ++it) {
+      if (rr <= tol2 * bb) { code = 1; break; }
+      std::fill(z.begin(), z.end(), 0.0);
+      double carry[2] = {nan, nan};
+      for (int ci = 0; ci < n_chunks; ++ci) {   // gn_jp_pass
+        const int64_t k0 = (int64_t)ci * kJpChunk, k1 = std::min<int64_t>(L.nnz, k0 + kJpChunk);
+        const JpChunk& ch = L.jp_chunks[(size_t)ci];
+        std::fill(tile.begin(), tile.end(), nan);
+        for (int64_t k = k0; k < k1; ++k) tile[(size_t)(k - k0)] = V[k] * p[(size_t)L.col[(size_t)k]];
+        for (int q = 0; q < ch.rns + ch.rnl; ++q) {
+          const JpSeg& s = L.jp_rseg[(size_t)(ch.rs0 + q)];
+          double sum = jp_seg_sum(s, tile.data(), nullptr, q >= ch.rns);
+          if (s.flags & 1) sum = carry[(ci & 1) ^ 1] + sum;
+          if (s.flags & 2) carry[ci & 1] = sum;
+          else t[(size_t)s.out] = (act[(size_t)s.out] ? 1.0 : 0.0) * sum;
+        }
+      }
+      for (int ci = 0; ci < n_chunks; ++ci) {   // gn_jtt_pass
+        const int64_t k0 = (int64_t)ci * kJpChunk, k1 = std::min<int64_t>(L.nnz, k0 + kJpChunk);
+        const JpChunk& ch = L.jp_chunks[(size_t)ci];
+        std::fill(tile.begin(), tile.end(), nan);
+        for (int64_t k = k0; k < k1; ++k) tile[(size_t)(k - k0)] = V[k] * t[(size_t)L.jp_row[(size_t)k]];
+        const uint16_t* cidx = L.jp_cidx.data() + k0;
+        for (int q = 0; q < ch.cns + ch.cnl; ++q) {
+          const JpSeg& s = L.jp_cseg[(size_t)(ch.cs0 + q)];
+          z[(size_t)s.out] += jp_seg_sum(s, tile.data(), cidx, q >= ch.cns);
+        }
+      }
+      const double php = lane_sums([&](int j, double& acc) {
+        double hp = 0.0;
+        if (!held[(size_t)j]) {
+          const double pj = p[(size_t)j];
+          hp = rho * z[(size_t)j] + mu * pj;
+          acc += pj * hp;
+        }
+        z[(size_t)j] = hp;
+      });
+      if (!(php > 0.0)) { code = 2; break; }
+      const double al = rr / php;
+      const double rn = lane_sums([&](int j, double& acc) {
+        if (held[(size_t)j]) return;
+        const double d0 = steps ? D[j] : 0.0;
+        D[j] = d0 + al * p[(size_t)j];
+        const double rj = r[(size_t)j] - al * z[(size_t)j];
+        r[(size_t)j] = rj;
+        acc += rj * rj;
+      });
+      const double beta = rn / rr;
+      for (int j = 0; j < n; ++j)
+        if (!held[(size_t)j]) p[(size_t)j] = r[(size_t)j] + beta * p[(size_t)j];
+      rr = rn;
+      ++steps;
+    }
+  }
+  const double slope = lane_sums([&](int j, double& acc) {
+    const double g = GR[j];
+    double dj = g;
+    if (steps && !held[(size_t)j]) dj = D[j];
+    else D[j] = g;
+    acc += g * dj;
+  });
+  SUM[0] = (double)steps; SUM[1] = bb; SUM[2] = rr; SUM[3] = slope; SUM[4] = nheld; SUM[5] = (double)code;
+  return 0;
 }
 #pragma clang fp contract(fast)
 

@@ -19,6 +19,9 @@ extern "C" int emu_cost(const towr_problem_desc_t* d, const double* x, double* f
 extern "C" int emu_traj(const towr_problem_desc_t* d, const double* x, double dt, double* out, int max_rows);
 extern "C" int emu_jac_products_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, const double* V,
                                    const double* P, const double* LAM, const double* Z0, double* Y, double* Z, double* Za);
+extern "C" int emu_gn_direction_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, const double* V,
+                                   const double* LAMP, const double* GR, const double* X, const double* XL, const double* XU,
+                                   double rho, double mu, double tol, int ncg, double* D, double* SUM);
 
 extern "C" void emu_limb_sum(const double* v, int k, long long limbs[3], int* bad, double* value);
 
@@ -93,6 +96,17 @@ int main(int argc, char** argv) {
   if (emu_jac_products_ex(&d, nd, data.data(), vx.data(), x.data(), lam.data(), x.data(), y.data(), z.data(), za.data())) {
     std::fprintf(stderr, "products: layout\n");
     return 7;
+  }
+  // the GN direction's walk (emu_gn_direction_ex) on the same values, two CG steps, in exactly-sized buffers:
+  // LAMP = g, GR = x, the layout's variable bounds at X = x when it has them (else every column free)
+  {
+    const bool vb = L.x_lower.size() == (size_t)L.n && L.x_upper.size() == (size_t)L.n;
+    std::vector<double> dir((size_t)L.n), sum(6);
+    if (emu_gn_direction_ex(&d, nd, data.data(), vx.data(), lam.data(), x.data(), vb ? x.data() : nullptr,
+                            vb ? L.x_lower.data() : nullptr, vb ? L.x_upper.data() : nullptr, 10.0, 1e-3, 0.0, 2, dir.data(), sum.data())) {
+      std::fprintf(stderr, "gn direction: layout\n");
+      return 9;
+    }
   }
   std::printf("ok n=%d m=%d nnz=%lld\n", L.n, L.m, (long long)L.nnz);
   return 0;

@@ -123,6 +123,11 @@ def _linesearch_operands(p, lo, up, B, mem, rnd):
 
 @pytest.mark.parametrize("name,B", CASES)
 def test_linesearch_against_numpy(name, B):
+    check_linesearch(name, B)
+
+
+def check_linesearch(name, B):
+    """The line search on the handle `name` of tests/test_gpu_lbfgs.py _problem (a configuration or "sweep_seed_N")."""
     import torch
     p, lo, up, _ = _problem(name)
     n, m, mem = p.n, p.m, LS_PAR["mem"]
@@ -217,6 +222,11 @@ OUTER_CASES = {"converged":      (1e-4, 0.1, 0.1, 1e-4, R.SEARCH, 3, 2, 0, 10.0)
 
 @pytest.mark.parametrize("name,B", CASES)
 def test_outer_against_numpy(name, B):
+    check_outer(name, B)
+
+
+def check_outer(name, B):
+    """The outer update on the handle `name` of tests/test_gpu_lbfgs.py _problem."""
     import torch
     p, lo, up, _ = _problem(name)
     n, m, mem = p.n, p.m, OUTER_PAR["mem"]
@@ -334,17 +344,30 @@ def test_fused_entry_is_bit_identical_to_the_pieces(name, B):
     """FUSED_ITERS iterate(iters=1) calls against the public calls in sequence, in every state array after every
     iteration, at the automatic products chunk and at chunk 2 (a ragged last chunk), with batch terrains set and a RHO row
     of distinct values; iterate(iters=3) against three iterate(iters=1)."""
-    import torch
     gait = name == "anymal_stairs_gaitopt_costs"
     f = F.with_costs(F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True) if gait else F.anymal_trot())
     f.params_.enable_stance_tracking = False
-    desc = cost_descs()[name]
-    p = TowrGpuProblem(desc, device=0, data=f.var_bounds_data())
+    p = TowrGpuProblem(cost_descs()[name], device=0, data=f.var_bounds_data())
     lo, up = p.variable_bounds()
+    p.set_batch_terrain(_terrains(name, B, np.random.default_rng(7)))
+    check_fused(name, p, lo, up, B, FUSED_ITERS, {1, 2, 3})
+
+
+def empty_sets(p):
+    """The constraint sets without rows."""
+    return [s for s, (_, _, _, rows) in enumerate(p.constraint_info()) if rows == 0]
+
+
+def check_fused(name, p, lo, up, B, iters, need):
+    """`iters` iterate(iters=1) calls on the handle p against the public calls in sequence (every state array after
+    every iteration, products chunks 0 and 2, a RHO row of distinct values), then iterate(iters=3) against three calls.
+    `need`: the line-search codes (LSUM[0]) that must occur in the run. The maximum of a constraint set without rows stays
+    +0.0 in RSUM through every residual call of the loop. Returns the codes per iteration."""
+    import torch
     mem = FUSED_PAR["mem"]
     par = alsolve_params(**FUSED_PAR)
-    p.set_batch_terrain(_terrains(name, B, np.random.default_rng(7)))
     h0 = _start(p, lo, up, B, mem, 7300)
+    empty = empty_sets(p)
 
     def fresh():
         st = _state(p, B, mem, h0)
@@ -354,28 +377,31 @@ def test_fused_entry_is_bit_identical_to_the_pieces(name, B):
     want, ref, codes = [], fresh(), []
     xc = ref.XC.cpu().numpy()[:, :p.n]
     assert (xc >= lo).all() and (xc <= up).all() and np.isnan(ref.XC.cpu().numpy()[:, p.n:]).all()
-    for k in range(FUSED_ITERS):
+    for k in range(iters):
         _pieces_iteration(p, par, ref)
         want.append(ref.clone())
         codes.append(ref.LSUM[:, 0].cpu().numpy().astype(int).tolist())
     print(f"{name}: LSUM[0] per iteration {codes}; phases {ref.ISTATE.view(B, 4)[:, 0].tolist()} outer {ref.ISTATE.view(B, 4)[:, 3].tolist()}")
     flat = {c for row in codes for c in row}
-    assert {1, 2, 3} <= flat, "no restart, accepted base or shrink in the run: the comparison would show nothing"
+    assert need <= flat, f"codes {sorted(need - flat)} do not occur in the run: the comparison would show nothing"
     assert (want[-1].HMETA.view(B, 2)[:, 0] > 0).any() or any((w.DSUM[:, 0] > 0).any() for w in want), "no pair was ever used"
     try:
         for chunk in (0, 2):
             p.set_products_chunk(chunk)
             st = fresh()
-            for k in range(FUSED_ITERS):
+            for k in range(iters):
                 p.alsolve_iterate(par, st)
                 torch.cuda.synchronize()
                 _assert_same(st, want[k], f"{name} chunk {chunk} iteration {k}")
+                for s_ in empty:
+                    assert (_np_bits(st.RSUM.cpu().numpy()[:, 4 + s_]) == 0).all(), f"{name} iteration {k}: the maximum of empty set {s_} is not +0.0"
             st = fresh()
             p.alsolve_iterate(par, st, iters=3)
             torch.cuda.synchronize()
             _assert_same(st, want[2], f"{name} chunk {chunk} iters=3")
     finally:
         p.set_products_chunk(0)
+    return codes
 
 
 def test_fused_rows_do_not_depend_on_batch_stream_or_run():

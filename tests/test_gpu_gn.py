@@ -14,18 +14,21 @@ reference <= 8 max(e64, gamma_n scale), e64 = the larger error of two float64 ev
 different summation orders, scale = max |value| (of D: over its free columns). On these operands e64 / scale stays below 1e-14, so the gate is
 gamma_n scale-sized. It still refuses a wrong system: a reference that treats every row as active lies more than
 1000 gates away on every problem checked (asserted on the CPU inside the test; measured >= 1.9e3, on gait-opt
->= 6e6). Largest err / gate seen on MI355X: 8.4e-3 (per case: DESIGN 4k)."""
+>= 6e6). Largest err / gate seen on MI355X: 8.4e-3 (per case: DESIGN 4k). The gate and the comparison live in
+tests/gn_gate.py (shared with the CPU tests of the kernel's host walk, tests/test_gn_emu.py); the device's bits against
+that walk, the swept shapes and the stop codes 2 (without a NaN) and 3 are in tests/test_gpu_sweep_gn.py."""
 import functools
 
 import numpy as np
 import pytest
 
 from tests import alsolve_ref as R
+from tests import gn_gate as GATE
 from tests import gn_ref as G
 from tests import lbfgs_ref
 from tests.configs import cost_descs
 from tests.gpu_helpers import _dev, _nan, _np_bits, _padded, _same_bits, _terrains, _vec
-from tests.test_gpu_alsolve import FUSED_PAR, SOLVE_PAR, _assert_same, _start, _state
+from tests.test_gpu_alsolve import FUSED_PAR, SOLVE_PAR, _assert_same, _start, _state, empty_sets
 from tests.test_gpu_lbfgs import _gamma, _ints, _problem
 from towr2025_amd import TowrGpuProblem, alsolve_params, gn_params
 from towr2025_amd import formulation as F
@@ -42,8 +45,14 @@ COMBOS = [(mk, ncg) for mk in MUS for ncg in NCGS]
 @functools.lru_cache(maxsize=None)
 def _operands(name, B):
     """Device and host copies of one case's operands, the pattern, the held masks and mu's base."""
-    import torch
     p, lo, up, _ = _problem(name)
+    return build_operands(p, lo, up, B)
+
+
+def build_operands(p, lo, up, B, redraw=None):
+    """_operands on a handle with its variable bounds. `redraw`: when the handle's bounds hold no column at these
+    operands, redraw(X) -> per-problem (XL, XU) (B, n) that the call then takes explicitly (XLd / XUd in the result)."""
+    import torch
     n, m, nnz = p.n, p.m, p.nnz
     rng = np.random.default_rng(8100 + B)
     X = R.clamp(p.initial_x() + 0.05 * rng.standard_normal((B, n)), lo, up)
@@ -58,19 +67,31 @@ def _operands(name, B):
     p.jac_tvec_batch_device(Vd, LPd, GRd)
     torch.cuda.synchronize()
     V, LAMP, GR = Vd.cpu().numpy()[:, :nnz], LPd.cpu().numpy()[:, :m], GRd.cpu().numpy()[:, :n]
+    return finish_operands(p, lo, up, B, X, V, LAMP, GR, rho, Xd, Vd, LPd, GRd, redraw)
+
+
+def finish_operands(p, lo, up, B, X, V, LAMP, GR, rho, Xd, Vd, LPd, GRd, redraw=None):
+    """The checks on the operands and the dict the helpers below take. lo / up: (n) or per problem (B, n)."""
+    n, m, nnz = p.n, p.m, p.nnz
     assert np.isfinite(V).all() and np.isfinite(LAMP).all() and np.isfinite(GR).all()
     rp, col = p.jac_csr()
     P = G.Pattern(rp, col, n)
-    held = np.stack([lbfgs_ref.held_mask(X[b], GR[b], lo, up) for b in range(B)])
+    lo, up = np.broadcast_to(lo, (B, n)), np.broadcast_to(up, (B, n))
+    held = np.stack([lbfgs_ref.held_mask(X[b], GR[b], lo[b], up[b]) for b in range(B)])
+    extra = {}
+    if redraw is not None and not held.any():
+        lo, up = redraw(X)
+        held = np.stack([lbfgs_ref.held_mask(X[b], GR[b], lo[b], up[b]) for b in range(B)])
+        extra = dict(XLd=_padded(lo, n + 4), XUd=_padded(up, n + 4))
     w0 = G.weights(LAMP[0])
     mu_base = float(np.max(rho[0] * np.bincount(P.col, weights=w0[P.row] * V[0] * V[0], minlength=n)))
     inactive = int((LAMP == 0).sum())
     assert mu_base > 0 and inactive > 0 and held.any(), "no curvature, no inactive row or no held column: the case shows nothing"
     return dict(p=p, lo=lo, up=up, n=n, m=m, nnz=nnz, B=B, X=X, V=V, LAMP=LAMP, GR=GR, rho=rho, P=P, held=held, mu_base=mu_base,
-                Xd=Xd, Vd=Vd, LPd=LPd, GRd=GRd, RHOd=_vec(rho))
+                Xd=Xd, Vd=Vd, LPd=LPd, GRd=GRd, RHOd=_vec(rho), **extra)
 
 
-def _run(c, gn, rows=None, stream=None, V=None, GR=None, RUN=None, run_stride=1):
+def _run(c, gn, rows=None, stream=None, V=None, GR=None, RUN=None, run_stride=1, LAMP=None):
     """The device call on the problems `rows` (default: all) into NaN-filled D (n + 5) and SUM (6 + 3)."""
     import torch
     n = c["n"]
@@ -81,8 +102,9 @@ def _run(c, gn, rows=None, stream=None, V=None, GR=None, RUN=None, run_stride=1)
     D, SUM = _nan(B, n + 5), _nan(B, 6 + 3)
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
-    c["p"].gn_direction_batch_device(gn, Vd, sel(c["LPd"]), GRd, D, SUM, rho=sel(c["RHOd"]), X=sel(c["Xd"]), RUN=RUN,
-                                     run_stride=run_stride, stream=stream)
+    XL, XU = (sel(c["XLd"]), sel(c["XUd"])) if "XLd" in c else (None, None)   # (explicit bounds: tests/test_gpu_sweep_gn.py)
+    c["p"].gn_direction_batch_device(gn, Vd, sel(c["LPd"] if LAMP is None else LAMP), GRd, D, SUM, rho=sel(c["RHOd"]), X=sel(c["Xd"]),
+                                     XL=XL, XU=XU, RUN=RUN, run_stride=run_stride, stream=stream)
     torch.cuda.synchronize()
     return D, SUM
 
@@ -93,33 +115,14 @@ def _refs(c, b, ncg, mu, tol):
     return (G.direction(*a, dtype=LD, **kw), [G.direction(*a, reverse=rev, **kw) for rev in (False, True)])
 
 
-def _gate(ld, f64, key, n):
-    """(long double value, gate, e64 / scale) of D (key 'D', its free columns) or of a scalar."""
-    v = np.asarray(ld[key], dtype=LD)
-    sel = ld["free"] if key == "D" else ...
-    e64 = max(float(np.max(np.abs(np.asarray(f[key]).astype(LD) - v)[sel], initial=0.0)) for f in f64)
-    scale = float(np.max(np.abs(v)[sel], initial=0.0))   # (D: over its free columns — the held ones hold g, far larger)
-    return v, 8 * max(e64, _gamma(n) * scale), e64 / scale if scale else 0.0
+_gate = GATE.gate   # (the gate and the comparison live in tests/gn_gate.py, importable without torch)
 
 
 def _check_problem(tag, c, b, Dh, S, ld, f64):
     """Row b of the device outputs against the references; returns the largest err / gate."""
-    n, g, held = c["n"], c["GR"][b], c["held"][b]
+    n = c["n"]
     assert np.isnan(Dh[n:]).all() and np.isnan(S[6:]).all(), f"{tag}: padding written"
-    assert np.array_equal(_np_bits(Dh[:n][held]), _np_bits(g[held])), f"{tag}: held columns"
-    assert all((f["steps"], f["code"]) == (ld["steps"], ld["code"]) for f in f64), f"{tag}: the references disagree"
-    assert (S[0], S[4], S[5]) == (ld["steps"], ld["nheld"], ld["code"]), f"{tag}: steps / held / code {S[:6]} vs {ld['steps'], ld['nheld'], ld['code']}"
-    if ld["steps"] == 0:
-        assert np.array_equal(_np_bits(Dh[:n]), _np_bits(g)), f"{tag}: no step completed, D must be GR"
-    worst = 0.0
-    for key, got in (("D", Dh[:n]), ("bb", S[1]), ("rr", S[2]), ("slope", S[3])):
-        v, gate, _ = _gate(ld, f64, key, n)
-        sel = ld["free"] if key == "D" else ...
-        err = float(np.max(np.abs(np.asarray(got).astype(LD) - v)[sel], initial=0.0))
-        print(f"{tag}: {key} err {err:.3e} gate {gate:.3e}")
-        assert err <= gate, f"{tag}: {key} err {err:.3e} gate {gate:.3e}"
-        worst = max(worst, err / gate if gate > 0 else 0.0)
-    return worst
+    return GATE.check_values(tag, n, c["GR"][b], c["held"][b], Dh, S, ld, f64)
 
 
 @pytest.mark.parametrize("name,B", CASES)
@@ -196,7 +199,7 @@ def test_bits_and_isolation(name, B):
         D3, S3 = _run(c, gn, rows=[b], stream=torch.cuda.Stream(device=_dev()))
         assert _same_bits(D0[b:b + 1], D3) and _same_bits(S0[b:b + 1], S3), f"problem {b} as a B = 1 call on another stream"
     # a NaN in one problem's GR (a column that is not fixed) or V: code 2 and D == GR there, no other problem's bits change
-    col = int(np.flatnonzero(c["lo"] < c["up"])[5])
+    col = int(np.flatnonzero(c["lo"][1] < c["up"][1])[5])   # (of problem 1, whose GR takes the NaN: the bounds are per problem rows)
     GRn, Vn = c["GRd"].clone(), c["Vd"].clone()
     GRn[1, col] = float("nan")
     Vn[0, nnz // 2] = float("nan")
@@ -260,17 +263,27 @@ def test_fused_entry_is_bit_identical_to_the_pieces(name, B):
     terrains set and a RHO row of distinct values; iters=3 against three calls; then one forced iteration (M0 lowered so
     that the trial is refused: a shrink that keeps D, and a fall through alpha_min that takes D <- GR); then frozen
     problems, whose bits stop changing."""
-    import torch
     gait = name == "anymal_stairs_gaitopt_costs"
     f = F.with_costs(F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True) if gait else F.anymal_trot())
     f.params_.enable_stance_tracking = False
     p = TowrGpuProblem(cost_descs()[name], device=0, data=f.var_bounds_data())
     lo, up = p.variable_bounds()
+    p.set_batch_terrain(_terrains(name, B, np.random.default_rng(7)))
+    check_fused(name, p, lo, up, B, GN_ITERS, {1, 2}, frozen=True)
+
+
+def check_fused(name, p, lo, up, B, iters, need, frozen=False):
+    """`iters` alsolve_gn_iterate(iters=1) calls on the handle p against the public calls in sequence (every state
+    array, DC and GSUM after every iteration, products chunks 0 and 2, a RHO row of distinct values), iters=3 against
+    three calls, then one forced iteration (see the test above). `need`: the line-search codes (LSUM[0]) that must occur
+    in the first `iters` iterations. The maximum of a constraint set without rows stays +0.0 in RSUM through every
+    residual call of the loop. `frozen`: also the frozen-problems run. Returns the codes per iteration."""
+    import torch
     n, mem = p.n, FUSED_PAR["mem"]
     par = alsolve_params(**FUSED_PAR)
     gn = gn_params(ncg=6, mu=1e-2, tol=1e-3)
-    p.set_batch_terrain(_terrains(name, B, np.random.default_rng(7)))
     h0 = _start(p, lo, up, B, mem, 7300)
+    empty = empty_sets(p)
 
     def fresh(par=par):
         st = _state(p, B, mem, h0)
@@ -287,30 +300,33 @@ def test_fused_entry_is_bit_identical_to_the_pieces(name, B):
 
     Gs, Vs = _nan(B, p.m + 1), _nan(B, p.nnz + 5)
     (ref, DCr, GSr), want, codes = fresh(), [], []
-    for k in range(GN_ITERS + 1):
-        if k == GN_ITERS:
+    for k in range(iters + 1):
+        if k == iters:
             force(ref)
             d_before = ref.D.clone()
         _pieces_iteration(p, par, gn, ref, DCr, GSr, Gs, Vs)
         want.append((ref.clone(), DCr.clone(), GSr.clone()))
         codes.append(ref.LSUM[:, 0].cpu().numpy().astype(int).tolist())
     print(f"{name}: LSUM[0] per iteration {codes}; CG steps / codes at the end {GSr[:, 0].tolist()} / {GSr[:, 5].tolist()}")
-    assert {1, 2} <= {c for row in codes[:GN_ITERS] for c in row}, "no restart or accepted base: the comparison would show nothing"
+    flat = {c for row in codes[:iters] for c in row}
+    assert need <= flat, f"codes {sorted(need - flat)} do not occur in the run: the comparison would show nothing"
     assert (GSr[:, 0] > 0).all() and np.isnan(GSr.cpu().numpy()[:, 6:]).all() and np.isnan(DCr.cpu().numpy()[:, n:]).all()
-    assert codes[GN_ITERS][:2] == [4, 3], codes[GN_ITERS]
+    assert codes[iters][:2] == [4, 3], codes[iters]
     assert _same_bits(ref.D[0, :n], ref.GR[0, :n]) and _same_bits(ref.D[1], d_before[1]), "the forced select"
     try:
         for chunk in (0, 2):
             p.set_products_chunk(chunk)
             st, DC, GS = fresh()
-            for k in range(GN_ITERS + 1):
-                if k == GN_ITERS:
+            for k in range(iters + 1):
+                if k == iters:
                     force(st)
                 p.alsolve_gn_iterate(par, st, gn, DC, GS)
                 torch.cuda.synchronize()
                 what = f"{name} chunk {chunk} iteration {k}"
                 _assert_same(st, want[k][0], what)
                 assert _same_bits(DC, want[k][1]) and _same_bits(GS, want[k][2]), f"{what}: DC / GSUM"
+                for s_ in empty:
+                    assert (_np_bits(st.RSUM.cpu().numpy()[:, 4 + s_]) == 0).all(), f"{what}: the maximum of empty set {s_} is not +0.0"
             st, DC, GS = fresh()
             p.alsolve_gn_iterate(par, st, gn, DC, GS, iters=3)
             torch.cuda.synchronize()
@@ -318,6 +334,8 @@ def test_fused_entry_is_bit_identical_to_the_pieces(name, B):
             assert _same_bits(DC, want[2][1]) and _same_bits(GS, want[2][2]), f"{name} chunk {chunk} iters=3: DC / GSUM"
     finally:
         p.set_products_chunk(0)
+    if not frozen:
+        return codes
     # frozen: max_outer = 1 ends every problem MAXED; from then on no bit changes, DC and GSUM included
     par2 = alsolve_params(**{**FUSED_PAR, "max_inner": 3, "max_outer": 1})
     st, DC, GS = fresh(par2)
@@ -330,6 +348,7 @@ def test_fused_entry_is_bit_identical_to_the_pieces(name, B):
     torch.cuda.synchronize()
     _assert_same(st, keep, "frozen problems")
     assert _same_bits(DC, DCk) and _same_bits(GS, GSk), "frozen problems: DC / GSUM"
+    return codes
 
 
 # ---- a short solve -----------------------------------------------------------------------------------------------------
