@@ -234,16 +234,74 @@ def ext_cases():
     return out
 
 
-def anymal_long_gait(n_phases=17, phase=0.2):
+def anymal_long_gait(n_phases=17, phase=0.2, costs=False):
     """ANYmal on stairs with phase-duration optimisation over a longer horizon (n_phases phases of `phase` s per
     foot, every foot in contact at the start and the end). At 17 phases the FDISC record launch's LDS (staging +
-    its FsBlock / window / template tables, towr_gpu.hip rec_launch_lds) is past 64 kB."""
+    its FsBlock / window / template tables, towr_gpu.hip rec_launch_lds) is past 64 kB. costs: with every default
+    cost kind (F.with_costs)."""
     f = F.anymal_trot(terrain=F.HeightMap.MakeTerrain(F.HeightMap.StairsID), optimize_timings=True,
                       total_duration=phase * n_phases)
     for ee in range(4):
         f.params_.ee_phase_durations_[ee] = [phase] * n_phases
         f.params_.ee_in_contact_at_start_[ee] = True
+    if costs:
+        _with_costs(f)
     return f.to_desc()
+
+
+def emu_cost_slots(desc):
+    """Layout::cost_nslot of a description through the host emulation (0: the gradient goes through the limbs)."""
+    import ctypes as C
+    import os
+    import subprocess
+    from towr2025_amd import _capi as capi
+    here = os.path.dirname(os.path.abspath(__file__))
+    lib = os.path.join(here, "host_emu", "build", "libemu.so")
+    if not os.path.exists(lib):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(here, "host_emu")])
+    capi.load_library()   # first: libemu.so links the HIP runtime too, and torch's has to be the process's one (_capi.py)
+    L = C.CDLL(lib)
+    L.emu_cost_slots.argtypes = [C.POINTER(capi.ProblemDesc)]
+    n = L.emu_cost_slots(C.byref(desc))
+    assert n >= 0, "the host emulation refuses the description"
+    return n
+
+
+_SLOT_LIMIT = {}
+
+
+def anymal_trot_slot_limit():
+    """name -> ProblemDesc, four descriptions: every default cost kind on the default ANYmal trot (fixed phase
+    durations), lengthened to the longest horizon in steps of 0.1 s whose layout still has gradient slots
+    (anymal_trot_slots_max: the slot path at its largest LDS footprint) and to the next one, whose layout has more than
+    kCostSlotMax entries and none (anymal_trot_past_slots: fixed durations through the limbs, with Energy Gram items),
+    and their RotVec twins (..._rotvec). The horizons are searched upwards from the default 2.4 s, not written down; anymal_slot_horizons()
+    gives them in tenths of a second and tests/test_cost_sweep.py asserts what they are. Built once per process."""
+    if _SLOT_LIMIT:
+        return dict(_SLOT_LIMIT["descs"])
+
+    def formulation(tenths, rotvec=False):
+        f = _with_costs(F.anymal_trot(total_duration=tenths / 10.0))
+        return _rotvec(f) if rotvec else f
+    tenths = 24
+    assert emu_cost_slots(formulation(tenths).to_desc()) > 0
+    while emu_cost_slots(formulation(tenths + 1).to_desc()) > 0:
+        tenths += 1
+        assert tenths < 100, "no horizon below 10 s is past the slot limit"
+    _SLOT_LIMIT["tenths"] = (tenths, tenths + 1)
+    _SLOT_LIMIT["descs"] = {
+        "anymal_trot_slots_max": formulation(tenths).to_desc(),
+        "anymal_trot_slots_max_rotvec": formulation(tenths, rotvec=True).to_desc(),
+        "anymal_trot_past_slots": formulation(tenths + 1).to_desc(),
+        "anymal_trot_past_slots_rotvec": formulation(tenths + 1, rotvec=True).to_desc(),
+    }
+    return dict(_SLOT_LIMIT["descs"])
+
+
+def anymal_slot_horizons():
+    """(last horizon with slots, first without) of anymal_trot_slot_limit, in tenths of a second."""
+    anymal_trot_slot_limit()
+    return _SLOT_LIMIT["tenths"]
 
 
 def many_short_rows(rows=1500):

@@ -1,7 +1,8 @@
 """Helpers the GPU tests of the batched solver-step entry points share (test_gpu_jac_products, test_gpu_residual,
 test_gpu_step, test_gpu_lbfgs): device operands with NaN padding, bit comparisons, and the formulations / batch
-terrains of the configurations they use; and the Jacobian products' extended-precision reference with its a-priori
-dot-product gate (_reference, _check_products: tests/test_gpu_jac_products.py has the derivation), shared with the CPU
+terrains of the configurations they use; the batch set-up of the objective kernel's tests (test_gpu_cost_loop,
+test_gpu_cost_sweep: _rows, _ldx, _eval, _clean_rows, _assert_row_bits); and the Jacobian products'
+extended-precision reference with its a-priori dot-product gate (_reference, _check_products: tests/test_gpu_jac_products.py has the derivation), shared with the CPU
 tests of the product tables and the swept-shape consumer tests. torch is imported where it is used, so the module
 imports without it."""
 import math
@@ -50,6 +51,48 @@ def _same_bits(a, b):
 
 def _np_bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _rows(x0, B, seed0):
+    return np.stack([x0 + 0.03 * np.random.default_rng(seed0 + b).standard_normal(len(x0)) for b in range(B)])
+
+
+def _ldx(n):
+    return n + 1 if n % 2 == 0 else n
+
+
+def _eval(p, Xd, grad=True):
+    """One eval_cost_batch_device into NaN-prefilled outputs: host (F, GRAD with its padding) or F alone."""
+    import torch
+    B = Xd.shape[0]
+    Fd = _nan(1, B)[0]
+    Gd = _nan(B, p.n + 3) if grad else None
+    p.eval_cost_batch_device(Xd, Fd, Gd)
+    torch.cuda.synchronize()
+    return (Fd.cpu().numpy(), Gd.cpu().numpy()) if grad else Fd.cpu().numpy()
+
+
+def _clean_rows(p, X, rows=None):
+    """{b: (F, gradient)} of the clean reference rows: row b copied to a fresh (aligned) one-row tensor and evaluated at
+    B = 1. Call it with the cost-grid override off."""
+    import torch
+    assert X.shape[1] == p.n
+    out = {}
+    for b in (range(len(X)) if rows is None else rows):
+        xd = torch.from_numpy(np.ascontiguousarray(X[b:b + 1])).to("cuda:0")
+        assert xd.data_ptr() % 16 == 0
+        Fh, Gh = _eval(p, xd)
+        assert np.isnan(Gh[:, p.n:]).all()
+        assert np.isfinite(Fh[0]) and np.isfinite(Gh[0, :p.n]).all(), f"clean reference row {b} is not finite"
+        out[b] = (Fh[0], Gh[0, :p.n].copy())
+    return out
+
+
+def _assert_row_bits(tag, Fh, Gh, b, ref, n):
+    f, g = ref
+    assert _np_bits(Fh[b:b + 1])[0] == _np_bits(np.array([f]))[0], f"{tag}: F[{b}] {Fh[b]!r} != {f!r}"
+    diff = np.flatnonzero(_np_bits(Gh[b, :n]) != _np_bits(g))
+    assert diff.size == 0, f"{tag}: row {b} differs in {diff.size} gradient columns, first {diff[0]}: {Gh[b, diff[0]]!r} != {g[diff[0]]!r}"
 
 
 def _formulation(name):

@@ -216,6 +216,35 @@ struct CountEmit {
   void operator()(int, int col, double, bool p) { ++emits; if (p && col >= 0) { ++pres; ++(*colcnt)[col]; } }
 };
 }
+// Layout::cost_nslot: the slot path's LDS slots (0: the objective's gradient goes through the limbs); -1 = no layout
+extern "C" int emu_cost_slots(const towr_problem_desc_t* d) {
+  Layout L; std::string e;
+  if (build_layout(*d, L, e)) return -1;
+  return L.cost_nslot;
+}
+
+// the largest number of gradient contributions any one column receives at x (the count emu_cost_stats prints as
+// max/col, without the printing): limb_value is exact below 2^11 of them; -1 = no layout
+extern "C" int emu_cost_col_max(const towr_problem_desc_t* d, const double* x) {
+  Layout L; std::string e;
+  if (build_layout(*d, L, e)) return -1;
+  std::vector<int> colcnt(L.n + 1, 0);
+  Ctx c{};
+  c.x = x; c.nodecol = L.nodecol.data(); c.spl = L.spl.data(); c.dur = L.dur.data();
+  c.ter = &L.terrain; c.rb = L.rb; c.fdisc_motion = L.fdisc_motion;
+  c.gait = L.gait; c.pinfo = L.pinfo.data(); c.pcols = L.pcols.data(); c.pact = L.pact.data(); c.sched = L.sched.data();
+  c.eelin = L.eelin.data(); c.rotvec = L.rotvec; c.cq = L.cost_q.data();
+  for (const CostItem& it : L.cost_items) {
+    if (it.type >= CT_COUNT) continue;   // a no-op lane of the wave schedule
+    c.seg = it.seg >= 0 ? L.segs.data() + (size_t)it.seg * L.spl.size() : nullptr;
+    CountEmit em{}; em.colcnt = &colcnt;
+    eval_cost_item(c, it, em);
+  }
+  int mx = 0;
+  for (int j = 0; j < L.n; ++j) mx = std::max(mx, colcnt[j]);
+  return mx;
+}
+
 // cost work statistics at x (experiment aid): items per type, emissions, contributions per column
 extern "C" int emu_cost_stats(const towr_problem_desc_t* d, const double* x) {
   Layout L; std::string e;

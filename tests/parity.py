@@ -147,7 +147,8 @@ def assert_close(g_ref, g, rows_ref, v_ref, v, m, what="", cols_ref=None, floor_
 def assert_cost_close(f_ref, f, g_ref, g, what=""):
     """Objective and dense gradient: the value tolerance above with the floor 1e-12 * max(1, |f|) for f
     and 1e-12 * max(1, max |grad|) for the gradient (its entries are sums over many samples whose
-    order differs: the device accumulates them with atomics)."""
+    order differs from the reference's: the device sums a column's LDS slots in the host's fixed order or,
+    under phase-duration optimisation and past kCostSlotMax, adds exact fixed-point limbs)."""
     assert bool(_within(np.float64(f_ref), np.float64(f), abs(f - f_ref), REL * max(abs(f), abs(f_ref)) + ABS * max(1.0, abs(f_ref)))), \
         f"{what}: f ref {f_ref!r} got {f!r}"
     fin = np.abs(g_ref)[np.isfinite(g_ref)]

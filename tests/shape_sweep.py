@@ -9,7 +9,10 @@ every seed, in a fixed order, so a seed is one shape for good. Reproducing a cas
 Left out on purpose: Gap terrain (it moves the reference pattern; the Gap configurations and tests/gap_frozen.py cover
 it) and Chimney. With the Swing constraint every foot has an odd phase count and starts in contact: a foot in swing at
 a trajectory boundary makes SwingConstraint index out of range in the reference, and both the oracle and the engine
-refuse it (refused_descs below)."""
+refuse it (refused_descs below).
+
+make_with_costs(seed) adds cost terms to make(seed)'s shape from a random stream of its own (tests/test_cost_sweep.py,
+DESIGN.md "Cost sweep")."""
 import numpy as np
 
 from towr2025_amd import formulation as F
@@ -94,6 +97,51 @@ def make(seed):
     info["never_touches_down"] = [ee for ee in range(E) if info["phases"][ee] == 1 and not info["contact_at_start"][ee]]
     info["single_stance"] = [ee for ee in range(E) if info["phases"][ee] == 1 and info["contact_at_start"][ee]]
     return f, info
+
+
+COST_KINDS = (F.Parameters.ForcesCostID, F.Parameters.EEMotionCostID, F.Parameters.EnergyCostID, F.Parameters.AngMomCostID)
+P_COST_KIND, P_EE_BASE_POS, P_BASE_HEIGHT = 0.75, 0.6, 0.3
+TORQUE_WEIGHTS = (0.0, 0.5, 2.0)
+DT_COST = (0.02, 0.03, 0.11)             # dt_cost_energy_, dt_cost_ang_mom_
+DT_COST_EE_BASE_POS = (0.05, 0.07)
+DT_BASE_HEIGHT = (0.01, 0.05)
+
+
+def make_with_costs(seed):
+    """make(seed) with cost terms -> (NlpFormulation, info, costs): the description is f.to_desc(costs=costs).
+    make(seed) is called unchanged and the cost knobs come from a stream of their own, default_rng([seed, 1]), every
+    knob drawn for every seed in a fixed order, so make(seed) and the seed lists built on it stay what they are. The
+    four Parameters::costs_ kinds are each present with p = 0.75 (weight 10^U(-4, 0)); if nothing at all was drawn,
+    Energy is switched on. A BaseHeightCost term (as configs._biped_example_costs(..., with_nodes=False) builds it,
+    target = the initial base height) follows the formulation's own terms. No SoftConstraint terms: they need side
+    data (configs.ext_cases covers them)."""
+    from tests.configs import _biped_example_costs
+    f, info = make(seed)
+    rng = np.random.default_rng([seed, 1])
+    P = f.params_
+    kinds, drawn = [], {}
+    for name in COST_KINDS:
+        on, drawn[name] = bool(rng.random() < P_COST_KIND), float(10.0 ** rng.uniform(-4.0, 0.0))
+        if on:
+            kinds.append((name, drawn[name]))
+    info["torque_weight"] = _pick(rng, TORQUE_WEIGHTS)
+    info["ee_base_pos"], w_eebp = bool(rng.random() < P_EE_BASE_POS), float(10.0 ** rng.uniform(-3.0, -1.0))
+    info["dt_cost_energy"], info["dt_cost_ang_mom"] = _pick(rng, DT_COST), _pick(rng, DT_COST)
+    info["dt_cost_ee_base_pos"] = _pick(rng, DT_COST_EE_BASE_POS)
+    info["base_height"], info["dt_base_height"] = bool(rng.random() < P_BASE_HEIGHT), _pick(rng, DT_BASE_HEIGHT)
+    if not kinds and not info["ee_base_pos"] and not info["base_height"]:
+        kinds.append((F.Parameters.EnergyCostID, drawn[F.Parameters.EnergyCostID]))
+    F.with_costs(f, costs=kinds, ee_base_pos=info["ee_base_pos"], torque_weight=info["torque_weight"])
+    P.swing_ee_base_pos_tracking_weight_ = w_eebp
+    P.dt_cost_energy_, P.dt_cost_ang_mom_ = info["dt_cost_energy"], info["dt_cost_ang_mom"]
+    P.dt_cost_swing_ee_base_pos_tracking_ = info["dt_cost_ee_base_pos"]
+    info["cost_kinds"] = [name for name, _ in kinds]
+    costs = f.cost_terms()
+    if info["base_height"]:
+        bh = _biped_example_costs(f, f.initial_base_.lin_p[2], with_nodes=False)
+        bh[0]["dt"] = info["dt_base_height"]
+        costs += bh
+    return f, info, costs
 
 
 def refused_descs():

@@ -17,8 +17,8 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
-from tests.configs import config_descs, cost_descs, ext_cases
-from tests.gpu_helpers import _nan, _np_bits, _padded
+from tests.configs import anymal_trot_slot_limit, config_descs, cost_descs, ext_cases
+from tests.gpu_helpers import _assert_row_bits, _clean_rows, _eval, _ldx, _nan, _np_bits, _padded, _rows
 from tests.parity import ABS, REL, assert_cost_close, schedule_cols
 from towr2025_amd import TowrGpuProblem
 from towr2025_amd import _capi as capi
@@ -28,57 +28,17 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 COSTS = cost_descs()
+SLOT_LIMIT = anymal_trot_slot_limit()
 D = C.POINTER(C.c_double)
 B_LOOP = 11
 
 
-def _rows(x0, B, seed0):
-    return np.stack([x0 + 0.03 * np.random.default_rng(seed0 + b).standard_normal(len(x0)) for b in range(B)])
-
-
-def _ldx(n):
-    return n + 1 if n % 2 == 0 else n
-
-
-def _eval(p, Xd, grad=True):
-    """One eval_cost_batch_device into NaN-prefilled outputs: host (F, GRAD with its padding) or F alone."""
-    import torch
-    B = Xd.shape[0]
-    Fd = _nan(1, B)[0]
-    Gd = _nan(B, p.n + 3) if grad else None
-    p.eval_cost_batch_device(Xd, Fd, Gd)
-    torch.cuda.synchronize()
-    return (Fd.cpu().numpy(), Gd.cpu().numpy()) if grad else Fd.cpu().numpy()
-
-
-def _clean_rows(p, X, rows=None):
-    """{b: (F, gradient)} of the clean reference rows (module docstring). Call it with the override off."""
-    import torch
-    assert X.shape[1] == p.n
-    out = {}
-    for b in (range(len(X)) if rows is None else rows):
-        xd = torch.from_numpy(np.ascontiguousarray(X[b:b + 1])).to("cuda:0")
-        assert xd.data_ptr() % 16 == 0
-        Fh, Gh = _eval(p, xd)
-        assert np.isnan(Gh[:, p.n:]).all()
-        assert np.isfinite(Fh[0]) and np.isfinite(Gh[0, :p.n]).all(), f"clean reference row {b} is not finite"
-        out[b] = (Fh[0], Gh[0, :p.n].copy())
-    return out
-
-
-def _assert_row_bits(tag, Fh, Gh, b, ref, n):
-    f, g = ref
-    assert _np_bits(Fh[b:b + 1])[0] == _np_bits(np.array([f]))[0], f"{tag}: F[{b}] {Fh[b]!r} != {f!r}"
-    diff = np.flatnonzero(_np_bits(Gh[b, :n]) != _np_bits(g))
-    assert diff.size == 0, f"{tag}: row {b} differs in {diff.size} gradient columns, first {diff[0]}: {Gh[b, diff[0]]!r} != {g[diff[0]]!r}"
-
-
 def _loop_desc(name):
-    return COSTS[name] if name in COSTS else config_descs()[name]
+    return COSTS[name] if name in COSTS else SLOT_LIMIT[name] if name in SLOT_LIMIT else config_descs()[name]
 
 
 @pytest.mark.parametrize("name", ["anymal_all_costs", "anymal_stairs_gaitopt_costs", "anymal_rotvec_costs",
-                                  "hopper_forces_motion", "monoped_backflip_rotvec", "monoped_hopper_flat"])
+                                  "hopper_forces_motion", "monoped_backflip_rotvec", "monoped_hopper_flat"] + sorted(SLOT_LIMIT))
 def test_rows_under_a_looping_block(name):
     """B = 11 distinct rows at grid 3 (trips 4 / 4 / 3: an odd grid with an odd ldx makes every block alternate between
     XStage's aligned and unaligned paths in both directions, and the last trip is ragged), grid 1 (one block takes all
@@ -95,10 +55,14 @@ def test_rows_under_a_looping_block(name):
       anymal_stairs_gaitopt_costs <limbs, yes, no>
       anymal_rotvec_costs         <limbs, yes, yes>
       monoped_hopper_flat         <limbs, no, no>: fixed phase durations take the limbs only when the layout has no
-                                  slots, that is no cost items (this configuration: f = 0 and a zero gradient, the loop
-                                  still clears and converts the limbs per trip) or more than kCostSlotMax slots, which
-                                  no description of a testable size has. <limbs, no, yes> is the same with RotVec and is
-                                  not run."""
+                                  slots. This configuration has no cost items: f = 0 and a zero gradient, the loop
+                                  still clears and converts the limbs per trip.
+      anymal_trot_past_slots      <limbs, no, no> with cost items: the default ANYmal trot with every cost kind at 3.6 s
+                                  has more than kCostSlotMax gradient entries (configs.anymal_trot_slot_limit), so the
+                                  Energy Gram items, the fixed-duration EEBasePos / BaseHeight items go through the limbs
+      anymal_trot_past_slots_rotvec  <limbs, no, yes>
+      anymal_trot_slots_max       <slots, no, no> at 3.5 s: 8044 of kCostSlotMax = 8192 slots, the largest LDS footprint
+      anymal_trot_slots_max_rotvec   <slots, no, yes>, the same"""
     desc = _loop_desc(name)
     o = Oracle(desc)
     p = TowrGpuProblem(desc, device=0)
