@@ -127,6 +127,190 @@ extern "C" int emu_eval(const towr_problem_desc_t* d, const double* x, double* g
   return emu_eval_ex(d, 0, nullptr, x, g, v, err, errlen);
 }
 
+// What the LDS emitters take for granted about the tile tables, walked as the kernels walk them. AccEmit above drops
+// a dummy-slot store and never looks at the LDS layout; here every lane of every tile goes through eval_item with an
+// emitter that follows TileEmit / TileEmitPre (tile_emit.h, tiles.hip) load by load and store by store. The
+// expectations are restated from the emitters, not from build_layout's arithmetic:
+//   * a tile's lanes are the launch's threads: tile_block(type, gait) of them (the kernels' BLOCK template argument
+//     and the slot table's stride), 64 for a small kind (TileEmit<64, 3> in misc_body); lane l's groups start at
+//     base + l, group g at + g * block; a tile's groups end where the next tile's begin;
+//   * an item emits ItemDesc::ncand candidates (of its selected rows, ItemDesc::rsel);
+//   * a present candidate's position is inside [0, v1 - v0), holds the candidate's (row, column) in the CSR pattern,
+//     and every position of the tile is hit exactly once; a direct range (ItemDirect, TileEmit DIRECT) gives the slot
+//     table's position and holds present candidates only;
+//   * an absent candidate's position is the lane's dummy slot, type_lds_dummy_off + (lane & 63); the 64 dummy slots lie
+//     past the tile's values (DIRECT: `s < nvals` is the only thing that keeps them out of V) and before the g rows;
+//   * the g rows (not for fixed-gait Dynamic: kGDirect) and Dynamic's scratch of instants x n_ee x 6 end inside the
+//     class's LDS; a small-kind wave's [values | dummies | g rows] ends where the group's next wave begins, and the
+//     last one inside misc_region;
+//   * the furthest slot group an emitter loads is one of the tile's: TileEmit's ring (depth kTileDepth, the small
+//     kinds' kMiscDepth) at construction, idle lanes included, and one group ahead per 8 candidates; DIRECT's
+//     preloaded groups (gait_slot_pre: 6 for RangeOfMotion, else 1); TileEmitPre's four groups from
+//     kDynG0PhaseA >> 3 on Dynamic's group-0 lanes; threads without a lane (the fused launch's fourth wave, a group's
+//     empty waves) read from slot 0 at their launch's stride;
+//   * what no candidate owns still holds the all-ones filler.
+// out (8): tiles, lanes with an item, present candidates, absent candidates, candidates through a direct range,
+// values covered by the tiles, the smallest number of groups left past the furthest load, the largest LDS end
+// (doubles) over the classes. Returns 0, -1 (no layout) or the number of the check that failed, with `err`.
+namespace {
+constexpr int kTileDepth = 2, kMiscDepth = 3;   // tiles.hip slot_depth(), misc_body's TileEmit<64, 3>
+constexpr int gait_pre(int type) { return type == IT_ROM ? 6 : 1; }   // tiles.hip gait_slot_pre()
+static_assert(tile_block(IT_ROM, false) == 192 && tile_block(IT_FDISC, false) == 192 && tile_block(IT_TQDISC, false) == 192 &&
+              tile_block(IT_DYN, false) == 256, "towr_step_kernel's tile_body<.., 192 | 256, KBLOCK, ..> instantiations");
+struct BoundsEmit {
+  const Layout* L; const TileDesc* td; const SlotGroup* slot; int64_t base, end; int block, lane, depth;
+  bool direct; int dummy; std::vector<int>* hit; ItemDirect dd{}; int flo = 0, fcnt = 0;
+  int j = 0, far = -1, bad = 0; long present = 0, absent = 0, ranged = 0; char msg[160] = {0};
+  static constexpr bool kFilter = true;
+  bool want(int row) const { return fcnt == 0 || (unsigned)(row - flo) < (unsigned)fcnt; }
+  void fail(int code, const char* what, int a, int b) {
+    if (!bad) { bad = code; std::snprintf(msg, sizeof msg, "%s (lane %d candidate %d: %d, %d)", what, lane, j, a, b); }
+  }
+  const SlotGroup* load(int g) {   // group g of this lane, as the kernels address it
+    far = std::max(far, g);
+    const int64_t at = (int64_t)(slot - L->slot_groups.data()) + (int64_t)g * block;
+    if (at < base || at >= end) { fail(20, "slot group outside the tile's groups", g, (int)((end - base) / block)); return nullptr; }
+    return slot + (int64_t)g * block;
+  }
+  void construct() {   // TileEmit's constructor: the ring, or DIRECT's preloaded groups
+    for (int g = 0; g < (direct ? gait_pre(td->type) : depth); ++g) load(g);
+  }
+  void g(int row, double) { if (row < td->r0 || row >= td->r1) fail(10, "g row outside the tile's rows", row, td->r1); }
+  void operator()(int row, int col, double, bool pres) {
+    if (!want(row) || bad) return;
+    const SlotGroup* q = load(j >> 3);
+    if (!q) return;
+    const int s = slot_pick(*q, j & 7), nv = td->v1 - td->v0;
+    const bool p = pres && col >= 0;
+    int sd = 0, k = -1;   // DIRECT: a direct range stores at off + col without the table
+    if (direct && col >= dd.c0[0] && col < dd.c1[0]) k = 0;
+    else if (direct && col >= dd.c0[1] && col < dd.c1[1]) k = 1;
+    if (k >= 0) {
+      sd = dd.off[k] + col;
+      ++ranged;
+      if (!p) fail(11, "an absent candidate in a direct range", col, sd);
+      else if (sd != s) fail(12, "a direct range disagrees with the slot table", sd, s);
+    }
+    if (p) {
+      ++present;
+      if (s < 0 || s >= nv) fail(13, "a present candidate outside the tile's values", s, nv);
+      else if (row < 0 || row >= L->m || td->v0 + s < L->row_ptr[row] || td->v0 + s >= L->row_ptr[row + 1] || L->col[td->v0 + s] != col)
+        fail(14, "a present candidate's position is not its (row, column)", row, col);
+      else ++(*hit)[s];
+    } else {
+      ++absent;
+      if (s != dummy + (lane & 63)) fail(15, "an absent candidate is not at the lane's dummy slot", s, dummy + (lane & 63));
+    }
+    ++j;
+    if (!direct && (j & 7) == 0) load((j >> 3) + depth - 1);   // the ring's prefetch
+  }
+  void flush() {}
+};
+}
+extern "C" int emu_tile_bounds_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, int64_t* out, char* err, int errlen) {
+  Layout L; std::string e;
+  if (build_layout_ex(*d, n_data, data, L, e)) { if (err) std::snprintf(err, errlen, "%s", e.c_str()); return -1; }
+  auto fail = [&](int code, const std::string& what) { if (err) std::snprintf(err, errlen, "%s", what.c_str()); return code; };
+  const int E = L.rb.n_ee;
+  Ctx c{};
+  c.x = L.x0.data(); c.nodecol = L.nodecol.data(); c.spl = L.spl.data(); c.dur = L.dur.data();
+  c.ter = &L.terrain; c.rb = L.rb; c.fdisc_motion = L.fdisc_motion;
+  c.gait = L.gait; c.pinfo = L.pinfo.data(); c.pcols = L.pcols.data(); c.pact = L.pact.data(); c.sched = L.sched.data();
+  c.eelin = L.eelin.data(); c.lin = L.lin.data(); c.rotvec = L.rotvec;
+  const int64_t total = (int64_t)L.slot_groups.size();
+  int64_t lanes = 0, present = 0, absent = 0, ranged = 0, covered = 0, spare = INT32_MAX, lds_end = 0;
+  // Dynamic's scratch as the block sees it: [dyn_scr_off, type_lds) of its LDS, exactly that many doubles
+  const int scr_n = L.type_lds[IT_DYN] - L.dyn_scr_off;
+  if (scr_n < 0 || L.dyn_scr_off < 0) return fail(30, "Dynamic scratch before the start of its LDS");
+  std::vector<double> scratch((size_t)scr_n);
+  for (size_t ti = 0; ti < L.tiles.size(); ++ti) {
+    const TileDesc& td = L.tiles[ti];
+    const int t = td.type, block = td.i1 - td.i0, nv = td.v1 - td.v0, nr = td.r1 - td.r0;
+    const bool misc = is_misc_kind(t), direct = L.gait && !misc;
+    const std::string tag = "tile " + std::to_string(ti) + " type " + std::to_string(t) + ": ";
+    if (block != (misc ? 64 : tile_block(t, L.gait)) || block != L.type_block[t]) return fail(1, tag + "lanes are not the kernel's block");
+    if (nv < 0 || nr <= 0 || td.v0 != L.row_ptr[td.r0] || td.v1 != L.row_ptr[td.r1]) return fail(2, tag + "values are not the rows' CSR range");
+    const int64_t base = L.items[td.i0].slot;
+    const int64_t end = ti + 1 < L.tiles.size() ? (int64_t)L.items[L.tiles[ti + 1].i0].slot : total;
+    if (base < 0 || end <= base || end > total || (end - base) % block) return fail(3, tag + "slot groups are not whole rounds of the block");
+    const int ng = (int)((end - base) / block), dummy = L.type_lds_dummy_off[t];
+    // LDS of the tile: [values | 64 dummy slots | g rows] (DIRECT: positions only, no tile)
+    if (dummy < nv || dummy + 64 > kSlotAbsent) return fail(4, tag + "dummy slots overlap the values or leave the uint16 range");
+    if (!misc && !direct) {
+      const bool gdirect = t == IT_DYN;   // fixed-gait Dynamic: g straight to HBM, the scratch follows the dummies
+      const int after = gdirect ? L.dyn_scr_off : L.type_lds_rows_off[t];
+      if (dummy + 64 > after) return fail(5, tag + "dummy slots overlap what follows them");
+      if (!gdirect && L.type_lds_rows_off[t] + nr > L.type_lds[t]) return fail(6, tag + "g rows past the class's LDS");
+      lds_end = std::max<int64_t>(lds_end, L.type_lds[t]);
+    }
+    std::vector<int> hit((size_t)nv, 0);
+    int far = -1;
+    for (int l = 0; l < block; ++l) {
+      const ItemDesc& it = L.items[td.i0 + l];
+      if (it.slot != base + l) return fail(7, tag + "lane " + std::to_string(l) + " does not start at base + lane");
+      BoundsEmit em{&L, &td, L.slot_groups.data() + it.slot, base, end, block, l, misc ? kMiscDepth : kTileDepth, direct, dummy, &hit};
+      if (direct && !L.idirect.empty()) em.dd = L.idirect[td.i0 + l];
+      if (it.rsel > 0) { em.flo = it.row0 + rsel_first(it.rsel); em.fcnt = rsel_count(it.rsel); }
+      em.construct();
+      int cand = 0;
+      if (it.type != IT_NONE) {
+        if (it.type != t) return fail(8, tag + "a lane of another type");
+        ++lanes;
+        cand = it.ncand;
+        if (t == IT_DYN) {
+          if (it.a2 < 0 || (int64_t)(it.a2 + 1) * E * 6 > scr_n) return fail(31, tag + "a Dynamic lane's instant past the scratch");
+          if (it.group == 0)   // TileEmitPre: four groups loaded before the barrier between the phases
+            for (int g = 0; g < 4; ++g) em.load((kDynG0PhaseA >> 3) + g);
+        }
+        c.seg = it.seg >= 0 ? L.segs.data() + (size_t)it.seg * L.spl.size() : nullptr;
+        c.dyn_scratch = t == IT_DYN ? scratch.data() : nullptr;
+        eval_item(c, it, em);
+        if (!em.bad && em.j != it.ncand) em.fail(9, "the item's candidates are not ItemDesc::ncand", em.j, it.ncand);
+      }
+      if (em.bad) return fail(em.bad, tag + em.msg);
+      present += em.present; absent += em.absent; ranged += em.ranged;
+      far = std::max(far, em.far);
+      for (int j = cand; j < 8 * ng; ++j)   // past the lane's candidates: the filler
+        if (slot_pick(L.slot_groups[(size_t)(base + (int64_t)(j >> 3) * block + l)], j & 7) != kSlotAbsent)
+          return fail(16, tag + "lane " + std::to_string(l) + " position " + std::to_string(j) + " is not the all-ones filler");
+    }
+    for (int s = 0; s < nv; ++s)
+      if (hit[(size_t)s] != 1) return fail(17, tag + "position " + std::to_string(s) + " hit " + std::to_string(hit[(size_t)s]) + " times");
+    covered += nv;
+    spare = std::min<int64_t>(spare, ng - 1 - far);
+  }
+  // the small-kind groups: kMiscWaves waves back to back, each [values | dummies | g rows] of its tile's kind
+  if (L.misc_tiles.size() % kMiscWaves || L.misc_lds.size() != 2 * L.misc_tiles.size()) return fail(40, "small-kind groups are not whole blocks");
+  std::vector<int> seen(L.tiles.size(), 0);
+  for (size_t q = 0; q < L.misc_tiles.size(); ++q) {
+    const int32_t ti = L.misc_tiles[q];
+    if (ti < 0) continue;
+    if ((size_t)ti >= L.tiles.size() || !is_misc_kind(L.tiles[(size_t)ti].type) || seen[(size_t)ti]++) return fail(41, "a small-kind wave's tile");
+    const TileDesc& td = L.tiles[(size_t)ti];
+    const int wl = L.misc_lds[2 * q], rows = L.misc_lds[2 * q + 1], dummy = L.type_lds_dummy_off[td.type];
+    int next = L.misc_region;   // where the group's next wave with a tile begins
+    for (size_t k = q + 1; k % kMiscWaves; ++k)
+      if (L.misc_tiles[k] >= 0) { next = L.misc_lds[2 * k]; break; }
+    if (wl < 0 || dummy + 64 > rows || wl + rows + (td.r1 - td.r0) > next || next > L.misc_region)
+      return fail(42, "small-kind tile " + std::to_string(ti) + ": its LDS overlaps the next wave's or leaves misc_region");
+    lds_end = std::max<int64_t>(lds_end, L.misc_region);
+  }
+  for (int t = 0; t < IT_COUNT; ++t)
+    for (int ti = L.type_tile0[t]; is_misc_kind(t) && ti < L.type_tile0[t + 1]; ++ti)
+      if (!seen[(size_t)ti]) return fail(43, "small-kind tile " + std::to_string(ti) + " is in no group");
+  // threads without a lane read their ring from slot 0 at the launch's stride
+  bool fixed_tile = false;
+  for (const TileDesc& td : L.tiles) fixed_tile = fixed_tile || (!L.gait && !is_misc_kind(td.type));
+  if (fixed_tile && total <= (int64_t)(kTileDepth - 1) * 192) return fail(44, "the slot table is shorter than an idle thread's ring");
+  if (!L.misc_tiles.empty() && total <= (int64_t)(kMiscDepth - 1) * 64) return fail(45, "the slot table is shorter than an empty wave's ring");
+  const int64_t o[8] = {(int64_t)L.tiles.size(), lanes, present, absent, ranged, covered, spare, lds_end};
+  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  return 0;
+}
+extern "C" int emu_tile_bounds(const towr_problem_desc_t* d, int64_t* out, char* err, int errlen) {
+  return emu_tile_bounds_ex(d, 0, nullptr, out, err, errlen);
+}
+
 // objective and dense gradient through engine_math.h's cost items (host instantiation)
 namespace {
 struct GradEmit {

@@ -23,6 +23,8 @@ extern "C" int emu_gn_direction_ex(const towr_problem_desc_t* d, int n_data, con
                                    const double* LAMP, const double* GR, const double* X, const double* XL, const double* XU,
                                    double rho, double mu, double tol, int ncg, double* D, double* SUM);
 
+extern "C" int emu_tile_bounds_ex(const towr_problem_desc_t* d, int n_data, const towr_data_t* data, int64_t* out, char* err, int errlen);
+
 extern "C" void emu_limb_sum(const double* v, int k, long long limbs[3], int* bad, double* value);
 
 // The limb arithmetic (CostLimbEmit, limb_of, limb_value) on the boundary list of tests/test_costs.py, each entry
@@ -107,6 +109,17 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "gn direction: layout\n");
       return 9;
     }
+  }
+  // the tile tables' walk (emu_tile_bounds_ex: every lane's slot groups, positions, dummy slots and LDS regions as the
+  // emitters address them; its hit counters and Dynamic scratch are exactly sized), eight counts and a message
+  {
+    std::vector<int64_t> counts(8);
+    std::vector<char> msg(256);
+    if (int rc = emu_tile_bounds_ex(&d, nd, data.data(), counts.data(), msg.data(), (int)msg.size())) {
+      std::fprintf(stderr, "tile bounds: check %d: %s\n", rc, msg.data());
+      return 10;
+    }
+    if (counts[5] != L.nnz) { std::fprintf(stderr, "tile bounds: the tiles cover %lld of %lld values\n", (long long)counts[5], (long long)L.nnz); return 10; }
   }
   std::printf("ok n=%d m=%d nnz=%lld\n", L.n, L.m, (long long)L.nnz);
   return 0;

@@ -217,34 +217,40 @@ def test_stage_overflow_shape_reads_what_the_overflow_stages():
             assert q.n <= 1152 or fdisc_entries_past(q, 1152) == 0, seed
 
 
+def _large_batch_shapes(optimize, rotvec, pt, kern, launches, what):
+    """The launch shapes of one layout at B >= kSplitBatch, by name, from its paths by class, kernels by index and
+    step_launches() (shared with tests/test_want_flags_cases.py)."""
+    for k in (DYN, ROM, FDISC, TQDISC):   # a class is launched exactly when it has tiles
+        assert (pt[k] != -1) == (k in kern), (what, k)
+    fused = [k for k in launches if k >= 5]
+    assert all(k in kern for k in launches) and not (fused and optimize), what
+    streamed = [k for k in (DYN, ROM, FDISC, TQDISC) if pt[k] == 1]
+    tiled = [k for k in (FDISC, TQDISC) if pt[k] == 0]
+    shapes = []
+    if not optimize:
+        shapes.append("fixed-gait RotVec" if rotvec else "fixed-gait Euler with a fusion group" if fused else "fixed-gait Euler")
+    else:
+        assert DYN in streamed and ROM in streamed, what
+        if FDISC in streamed and TQDISC in streamed:
+            shapes.append("FDISC + TQDISC streamed")
+        elif FDISC in streamed:
+            shapes.append("FDISC streamed beside RangeOfMotion / Dynamic")
+        elif TQDISC in streamed and pt[FDISC] == -1:
+            shapes.append("TQDISC streamed without an FDISC grid")
+        elif pt[FDISC] == -1 and pt[TQDISC] == -1:
+            shapes.append("RangeOfMotion / Dynamic streamed alone")
+        if tiled:
+            shapes.append("tile-path FDISC or TQDISC beside streamed classes")
+    return shapes
+
+
 def test_seed_lists_reach_the_large_batch_launch_shapes():
     """What test_gpu_batch_above_the_split runs at B = 65 (>= kSplitBatch, towr_gpu.hip): the launch shapes the two
     lists reach between them, from kernel_path, kernels() and step_launches() of the layout-only handles."""
     reached = {}
     for seed in GPU_SEEDS + FIXED_GAIT_SEEDS:
         info, p, pt, kern, launches = _launch_shape(seed)
-        for k in (DYN, ROM, FDISC, TQDISC):   # a class is launched exactly when it has tiles
-            assert (pt[k] != -1) == (k in kern), (seed, k)
-        fused = [k for k in launches if k >= 5]
-        assert all(k in kern for k in launches) and not (fused and info["optimize"]), seed
-        streamed = [k for k in (DYN, ROM, FDISC, TQDISC) if pt[k] == 1]
-        tiled = [k for k in (FDISC, TQDISC) if pt[k] == 0]
-        shapes = []
-        if not info["optimize"]:
-            shapes.append("fixed-gait RotVec" if info["rotvec"] else "fixed-gait Euler with a fusion group" if fused else "fixed-gait Euler")
-        else:
-            assert DYN in streamed and ROM in streamed, seed
-            if FDISC in streamed and TQDISC in streamed:
-                shapes.append("FDISC + TQDISC streamed")
-            elif FDISC in streamed:
-                shapes.append("FDISC streamed beside RangeOfMotion / Dynamic")
-            elif TQDISC in streamed and pt[FDISC] == -1:
-                shapes.append("TQDISC streamed without an FDISC grid")
-            elif pt[FDISC] == -1 and pt[TQDISC] == -1:
-                shapes.append("RangeOfMotion / Dynamic streamed alone")
-            if tiled:
-                shapes.append("tile-path FDISC or TQDISC beside streamed classes")
-        for sh in shapes:
+        for sh in _large_batch_shapes(info["optimize"], info["rotvec"], pt, kern, launches, seed):
             reached.setdefault(sh, []).append(seed)
     print({k: v for k, v in sorted(reached.items())})
     assert len(reached.get("fixed-gait Euler with a fusion group", [])) >= 6
