@@ -776,6 +776,51 @@ int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32
                                              const double* GL, const double* GU, int64_t ldgb,
                                              const double* XL, const double* XU, int64_t ldxb, void* stream);
 
+/* ---- the Gauss-Newton direction with a Jacobi (diagonal) preconditioner ------------------------------------------ */
+#define TOWR_GN_PC_NONE 0
+#define TOWR_GN_PC_JACOBI 1
+
+/* towr_gpu_gn_direction_batch_device with a choice of preconditioner. PC (B rows, ldpc >= n) is caller-owned DEVICE
+ * memory; lds >= 8. precond = TOWR_GN_PC_NONE launches that entry's kernel: D and SUM[0..5] are its bits, PC (which
+ * may be NULL) and SUM[6..7] are not written. precond = TOWR_GN_PC_JACOBI, per problem, with H, w, rho_b, g, the held
+ * columns and RUN exactly as above:
+ *   dg_j = sum_i w_i * (v_ij * v_ij) over the entries of column j (two rounded products per term; a NaN or infinity in
+ *   an inactive row still gives NaN), summed on the by-column tree of towr_gpu_jac_tvec_batch_device: the bits that
+ *   entry gives for the values v*v and LAM = w;
+ *   M_j = rho_b * dg_j + mu (one rounded product, one rounded addition); M_j == 0.0 exactly is replaced by 1.0 (a
+ *   column without active entries at mu = 0); a NaN stays NaN. PC[b*ldpc + j] = M_j on free columns, +0.0 on held ones.
+ * From d = 0: r = g and z = r ./ M (a division) on free columns, p = z (0 on held ones), bb = rr = sum_free g^2,
+ * rz = sum_free r z; bb == 0 ends at once (code 3; PC, SUM[6] and SUM[7] are written all the same); else for it < ncg:
+ *   1. stop (code 1) if rr <= (tol*tol)*bb;
+ *   2. t = w .* (J p);   3. Hp = rho_b * (J^T t) + mu * p on free columns;   4. pHp = sum_free p Hp;
+ *   5. stop (code 2) unless pHp > 0 (a NaN anywhere ends here);
+ *   6. a = rz / pHp, d = d + a p, r = r - a Hp, z = r ./ M, rn = sum_free r r, rzn = sum_free r z,
+ *      p = z + (rzn / rz) p, rz = rzn, rr = rn; one step completed.
+ * D and SUM[0..5] as above ([2] is the true residual rr, not rz); SUM[6] the final rz; SUM[7] the number of free columns
+ * whose M was replaced by 1.0. A problem skipped by RUN has no byte of its D, PC or SUM row touched. The same trees and
+ * the same independence of B, position, stream and run as above; nothing beyond n (PC) or 8 (SUM) is read or written in
+ * a row. TOWR_ERR_INVALID before anything runs for what the entry above refuses, precond outside {0, 1}, PC NULL with
+ * TOWR_GN_PC_JACOBI, ldpc < n (with PC), lds < 8, and a PC that overlaps V, LAMP, X, GR or D. TOWR_ERR_UNSUPPORTED as
+ * above: the kernel's LDS is the same (M lives in PC).                                                            */
+int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, int32_t precond,
+                                          const double* V, int64_t ldv, const double* LAMP, int64_t ldlp,
+                                          const double* RHO, double rho, const double* X, int64_t ldx,
+                                          const double* GR, int64_t ldgr, const double* XL, const double* XU, int64_t ldb,
+                                          const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd,
+                                          double* SUM, int64_t lds, double* PC, int64_t ldpc, void* stream);
+
+/* towr_gpu_alsolve_gn_iterate_batch_device with that direction: step 2 calls towr_gpu_gn_direction_pc_batch_device
+ * with `precond` and PC (B rows, leading dimension ldx; caller-owned DEVICE memory) at the chunk's rows; ldgs >= 8.
+ * Everything else is that entry's. Bit-identical to the public calls in sequence, whatever the products chunk, and with
+ * precond = TOWR_GN_PC_NONE to that entry (PC may be NULL, GSUM[6..7] is not written). TOWR_ERR_INVALID before anything
+ * runs for what that entry refuses, precond outside {0, 1}, PC NULL with TOWR_GN_PC_JACOBI, ldgs < 8, and a PC that
+ * overlaps LAMP, XC, GRC or DC.                                                                                    */
+int towr_gpu_alsolve_gn_pc_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters,
+                                                const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                                const towr_gn_params_t* gn, int32_t precond, double* DC, double* GSUM,
+                                                int64_t ldgs, double* PC, const double* GL, const double* GU, int64_t ldgb,
+                                                const double* XL, const double* XU, int64_t ldxb, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

@@ -27,10 +27,14 @@
       the handle's bounds: beside NCG (b + c), the same passes by the product kernels (one launch and one LDS staging
       each); (v1) the same call at ncg = 1 (the pass that cannot come from a cache);
   (w) alsolve_gn_iterate(iters = 1) in a running solve of its own from X (ncg = NCG, mu = 1e-2, tol = 1e-3), beside (t),
+  (x) gn_pc_direction_batch_device (the Jacobi-preconditioned recursion) on the operands of (v) at ncg = NCG and (x1) at
+      ncg = 1, beside v and v1: x1 - v1 is the diagonal pass with the PC row's write, (x - x1) - (v - v1) what the
+      division and the PC row's read add to NCG - 1 steps,
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
-printed. usage: python tools/products_timing.py [anymal|gait|all]"""
+printed. ONLY=b,c,v,v1,x,x1 (a comma list of the letters above) times those variants alone and prints the summary lines
+they suffice for. usage: python tools/products_timing.py [anymal|gait|all]"""
 import os
 import statistics
 import sys
@@ -47,6 +51,7 @@ REPS = int(os.environ.get("REPS", "20"))
 ROUNDS = int(os.environ.get("ROUNDS", "5"))
 MEM = int(os.environ.get("MEM", "8"))
 NCG = int(os.environ.get("NCG", "8"))
+ONLY = set(os.environ.get("ONLY", "").split(",")) - {""}
 PEAK = 8.0e12
 
 
@@ -140,6 +145,7 @@ def run(name, f, B):
     p.eval_batch_device(X, G, V, stream=stream)
     p.residual_batch_device(G, SUM, LAM=LAM, rho=rho, LAMP=LAMP, stream=stream)
     GRg, Dg, GSUM = torch.empty_like(P), torch.empty_like(P), torch.empty((B, 16), dtype=torch.float64, device=dev)
+    Dx, PCx, XSUM = torch.empty_like(P), torch.empty_like(P), torch.empty((B, 16), dtype=torch.float64, device=dev)
     p.jac_tvec_batch_device(V, LAMP, GRg, stream=stream)
     gnv, gnv1, gnw = gn_params(ncg=NCG, mu=1e-2, tol=0.0), gn_params(ncg=1, mu=1e-2, tol=0.0), gn_params(ncg=NCG, mu=1e-2, tol=1e-3)
     stg = AlSolveState.allocate(p, B, mem)
@@ -208,7 +214,13 @@ def run(name, f, B):
                 (f"v gn direction ncg={NCG}", lambda: p.gn_direction_batch_device(gnv, V, LAMP, GRg, Dg, GSUM, rho=rho, X=Xs, stream=stream)),
                 ("v1 gn direction ncg=1", lambda: p.gn_direction_batch_device(gnv1, V, LAMP, GRg, Dg, GSUM, rho=rho, X=Xs, stream=stream)),
                 (f"w alsolve gn iterate ncg={NCG}", lambda: (p.set_products_chunk(0), gn_iter_call(),
-                                                            codes_g.append(stg.LSUM[:, 0].clone()), steps_g.append(GSg[:, 0].clone())))]
+                                                            codes_g.append(stg.LSUM[:, 0].clone()), steps_g.append(GSg[:, 0].clone()))),
+                (f"x gn pc direction ncg={NCG}", lambda: p.gn_pc_direction_batch_device(gnv, V, LAMP, GRg, Dx, XSUM, PC=PCx, rho=rho, X=Xs,
+                                                                                       stream=stream)),
+                ("x1 gn pc direction ncg=1", lambda: p.gn_pc_direction_batch_device(gnv1, V, LAMP, GRg, Dx, XSUM, PC=PCx, rho=rho, X=Xs,
+                                                                                   stream=stream))]
+    if ONLY:
+        variants = [(k, fn) for k, fn in variants if k.split()[0] in ONLY]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
         for _ in range(3):
             fn()
@@ -233,6 +245,15 @@ def run(name, f, B):
                   bytes_ls if k[:2] in ("q ", "r ") else bytes_out if k[0] in "su" else 0)
         rate = f"  {nbytes / (med * 1e-3) / 1e12:.2f} TB/s = {100 * nbytes / (med * 1e-3) / PEAK:.0f} % of 8 TB/s" if nbytes else ""
         print(f"  {k:22s} {med:.4f} ms  (min {min(t):.4f} max {max(t):.4f}){rate}", flush=True)
+    if not ONLY or {"v", "v1", "x", "x1"} <= ONLY:
+        mx = {k.split()[0]: statistics.median(times[k]) for k, _ in variants if k.split()[0] in ("v", "v1", "x", "x1")}
+        print(f"  gn pc direction ncg={NCG}: x {mx['x']:.4f} ms vs v {mx['v']:.4f} ms, ratio {mx['x'] / mx['v']:.3f}; ncg=1: x1 {mx['x1']:.4f} ms "
+              f"vs v1 {mx['v1']:.4f} ms, x1 - v1 {mx['x1'] - mx['v1']:.4f} ms; per step (x - x1) / {NCG - 1} "
+              f"{(mx['x'] - mx['x1']) / max(NCG - 1, 1):.4f} ms vs (v - v1) / {NCG - 1} {(mx['v'] - mx['v1']) / max(NCG - 1, 1):.4f} ms; "
+              f"columns whose M was replaced {XSUM[:, 7].mean().item():.2f}", flush=True)
+    if ONLY:
+        p.set_products_chunk(0)
+        return
     parts = sum(statistics.median(times[k]) for k in ("a eval_batch_device", "e residual", "c jac_tvec"))
     print(f"  residual bytes {bytes_res / 1e9:.3f} GB; auglag parts a + e + c {parts:.4f} ms, fused / parts "
           f"{statistics.median(times['g auglag fused auto']) / parts:.3f}", flush=True)

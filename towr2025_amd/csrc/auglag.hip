@@ -106,8 +106,9 @@ int gn_ready(towr_gpu_handle h) {
   if (al.gn_ready) return TOWR_OK;
   if (int rc = gn_fits(h)) return rc;
   const size_t lds = gn_direction_lds(h->L.n, h->L.m);
-  if (lds > 64 * 1024 && hipFuncSetAttribute(gn_direction_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  for (const void* k : {gn_direction_kernel(), gn_direction_pc_kernel()})
+    if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   al.gn_ready = true;
   return TOWR_OK;
 }
@@ -200,6 +201,23 @@ int gn_params(towr_gpu_handle h, const towr_gn_params_t* gn, const double* D, co
   if (!(gn->mu >= 0) || !(gn->tol >= 0)) return fail(h, TOWR_ERR_INVALID, "gn: mu or tol is negative or NaN");
   if (!D || !SUM) return fail(h, TOWR_ERR_INVALID, "null GN direction or summary (D / SUM, DC / GSUM)");
   if (lds < 6) return fail(h, TOWR_ERR_INVALID, "leading dimension of the GN summary smaller than 6");
+  return TOWR_OK;
+}
+
+// [p, p + (B - 1) ld + len) and [q, ...) share a byte (B rows each; a NULL or B < 1 shares nothing)
+bool rows_overlap(int B, const double* p, int64_t ldp, int64_t lenp, const double* q, int64_t ldq, int64_t lenq) {
+  if (!p || !q || B < 1) return false;
+  const double *pe = p + (int64_t)(B - 1) * ldp + lenp, *qe = q + (int64_t)(B - 1) * ldq + lenq;
+  return p < qe && q < pe;
+}
+
+// the preconditioned entries' own arguments, behind gn_params: the choice, the M rows and the two summary entries more
+int gn_pc_params(towr_gpu_handle h, int32_t precond, const double* PC, int64_t ldpc, int64_t lds) {
+  if (precond != TOWR_GN_PC_NONE && precond != TOWR_GN_PC_JACOBI)
+    return fail(h, TOWR_ERR_INVALID, "gn: precond outside {TOWR_GN_PC_NONE, TOWR_GN_PC_JACOBI}");
+  if (precond == TOWR_GN_PC_JACOBI && !PC) return fail(h, TOWR_ERR_INVALID, "gn: null PC with TOWR_GN_PC_JACOBI");
+  if (PC && ldpc < h->L.n) return fail(h, TOWR_ERR_INVALID, "gn: leading dimension of PC (ldpc) smaller than n");
+  if (lds < 8) return fail(h, TOWR_ERR_INVALID, "leading dimension of the GN summary smaller than 8");
   return TOWR_OK;
 }
 
@@ -305,12 +323,13 @@ int launch_lbfgs_direction(towr_gpu_handle h, int B, LbfgsDirArgs a, hipStream_t
   return TOWR_OK;
 }
 
-// (XL NULL: the handle's bounds, one row — with X, after step_ready; after gn_ready)
+// (XL NULL: the handle's bounds, one row — with X, after step_ready; after gn_ready; a.PC: the preconditioned kernel)
 int launch_gn(towr_gpu_handle h, int B, GnArgs a, hipStream_t s) {
   if (a.X && !a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
   a.jp = h->al.jp;   // the tables (products_ready)
   void* args[] = {&a};
-  HIPCHK(h, launch_kernel(gn_direction_kernel(), dim3((unsigned)B), dim3(kGnBlock), args, gn_direction_lds(a.jp.n, a.jp.m), s));
+  HIPCHK(h, launch_kernel(a.PC ? gn_direction_pc_kernel() : gn_direction_kernel(), dim3((unsigned)B), dim3(kGnBlock), args,
+                          gn_direction_lds(a.jp.n, a.jp.m), s));
   return TOWR_OK;
 }
 
@@ -406,6 +425,7 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
       g.RUN = row_at(gn->RUN, c0, gn->run_stride);
       g.D = gn->D + (int64_t)c0 * gn->ldd;
       g.SUM = gn->SUM + (int64_t)c0 * gn->lds;
+      if (gn->PC) g.PC = gn->PC + (int64_t)c0 * gn->ldpc;
       rc = launch_gn(h, cb, g, b.s);
     }
   }
@@ -742,14 +762,23 @@ int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t 
 }
 
 // ---- the Gauss-Newton direction (jprod.hip) and the resident loop that uses it ------------------------------------------
-int towr_gpu_gn_direction_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, const double* V, int64_t ldv,
-                                       const double* LAMP, int64_t ldlp, const double* RHO, double rho, const double* X,
-                                       int64_t ldx, const double* GR, int64_t ldgr, const double* XL, const double* XU,
-                                       int64_t ldb, const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd, double* SUM,
-                                       int64_t lds, void* stream) {
+// both direction entries; PC NULL: the plain recursion (pc: the preconditioned entry's checks run)
+static int gn_direction(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, const double* V, int64_t ldv,
+                        const double* LAMP, int64_t ldlp, const double* RHO, double rho, const double* X, int64_t ldx,
+                        const double* GR, int64_t ldgr, const double* XL, const double* XU, int64_t ldb, const int32_t* RUN,
+                        int32_t run_stride, double* D, int64_t ldd, double* SUM, int64_t lds, bool pc, int32_t precond, double* PC,
+                        int64_t ldpc, void* stream) {
   if (!h || B < 0 || !V || !LAMP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null V, LAMP or GR, or B < 0)");
   if (int rc = gn_params(h, gn, D, SUM, lds)) return rc;
   const Layout& L = h->L;
+  if (pc) {
+    if (int rc = gn_pc_params(h, precond, PC, ldpc, lds)) return rc;
+    if (precond != TOWR_GN_PC_JACOBI) PC = nullptr;
+    if (rows_overlap(B, PC, ldpc, L.n, D, ldd, L.n) || rows_overlap(B, PC, ldpc, L.n, GR, ldgr, L.n) ||
+        rows_overlap(B, PC, ldpc, L.n, X, ldx, L.n) || rows_overlap(B, PC, ldpc, L.n, V, ldv, L.nnz) ||
+        rows_overlap(B, PC, ldpc, L.n, LAMP, ldlp, L.m))
+      return fail(h, TOWR_ERR_INVALID, "gn: PC overlaps V, LAMP, X, GR or D");
+  }
   if (!RHO && !(rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 without RHO");
   if (ldv < L.nnz || ldlp < L.m || (X && ldx < L.n) || ldgr < L.n || ldd < L.n)
     return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAMP) / n (X, GR, D)");
@@ -761,21 +790,49 @@ int towr_gpu_gn_direction_batch_device(towr_gpu_handle h, int32_t B, const towr_
   if (X && !XL)
     if (int rc = step_ready(h)) return rc;
   GnArgs a{V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN, run_stride, D, ldd, SUM, lds, gn->mu, gn->tol, gn->ncg, 0};
+  a.PC = PC; a.ldpc = ldpc;
   return launch_gn(h, B, a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_gn_direction_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, const double* V, int64_t ldv,
+                                       const double* LAMP, int64_t ldlp, const double* RHO, double rho, const double* X,
+                                       int64_t ldx, const double* GR, int64_t ldgr, const double* XL, const double* XU,
+                                       int64_t ldb, const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd, double* SUM,
+                                       int64_t lds, void* stream) {
+  return gn_direction(h, B, gn, V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN, run_stride, D, ldd, SUM, lds,
+                      false, TOWR_GN_PC_NONE, nullptr, 0, stream);
+}
+
+int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, int32_t precond,
+                                          const double* V, int64_t ldv, const double* LAMP, int64_t ldlp, const double* RHO,
+                                          double rho, const double* X, int64_t ldx, const double* GR, int64_t ldgr,
+                                          const double* XL, const double* XU, int64_t ldb, const int32_t* RUN, int32_t run_stride,
+                                          double* D, int64_t ldd, double* SUM, int64_t lds, double* PC, int64_t ldpc,
+                                          void* stream) {
+  return gn_direction(h, B, gn, V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN, run_stride, D, ldd, SUM, lds,
+                      true, precond, PC, ldpc, stream);
 }
 
 // Per iteration what the public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag chunks
 // with the per-problem RHO accumulated onto GRC and, per chunk, the GN direction at (XC, GRC) into DC on the values still
 // in handle scratch (RUN = the phases: frozen problems are skipped), the line search, the outer update, the select
 // (D <- DC or GR by the flags) and the step.
-int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
-                                             const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC,
-                                             double* GSUM, int64_t ldgs, const double* GL, const double* GU, int64_t ldgb,
-                                             const double* XL, const double* XU, int64_t ldxb, void* stream) {
+static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                              const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC, double* GSUM,
+                              int64_t ldgs, bool pc, int32_t precond, double* PC, const double* GL, const double* GU, int64_t ldgb,
+                              const double* XL, const double* XU, int64_t ldxb, void* stream) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   if (int rc = gn_params(h, gn, DC, GSUM, ldgs)) return rc;
   const towr_alsolve_state_t& st = *state;
+  if (pc) {
+    if (int rc = gn_pc_params(h, precond, PC, st.ldx, ldgs)) return rc;
+    if (precond != TOWR_GN_PC_JACOBI) PC = nullptr;
+    const int64_t n = h->L.n;
+    if (rows_overlap(B, PC, st.ldx, n, DC, st.ldx, n) || rows_overlap(B, PC, st.ldx, n, st.XC, st.ldx, n) ||
+        rows_overlap(B, PC, st.ldx, n, st.GRC, st.ldx, n) || rows_overlap(B, PC, st.ldx, n, st.LAMP, st.ldl, h->L.m))
+      return fail(h, TOWR_ERR_INVALID, "gn: PC overlaps LAMP, XC, GRC or DC");
+  }
   ResArgs r{nullptr, 0, GL, GU, ldgb, st.LAM, st.ldl, st.LAMP, st.ldl, st.RSUM, st.ldrs};
   r.rho = 1.0;
   r.RHO = st.RHO;
@@ -783,6 +840,7 @@ int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32
   g.XL = XL; g.XU = XU; g.ldb = ldxb;
   g.RUN = st.ISTATE; g.run_stride = 4;
   g.D = DC; g.ldd = st.ldx; g.SUM = GSUM; g.lds = ldgs;
+  g.PC = PC; g.ldpc = st.ldx;
   g.mu = gn->mu; g.tol = gn->tol; g.ncg = gn->ncg;
   const StepArgs step{st.X, st.ldx, st.D, st.ldx, st.ALPHA, 0.0, XL, XU, ldxb, st.XC, st.ldx, st.SSUM, st.ldss};
   if (int rc = bind(h)) return rc;
@@ -802,6 +860,22 @@ int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32
     }
     return rc;
   });
+}
+
+int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                             const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC,
+                                             double* GSUM, int64_t ldgs, const double* GL, const double* GU, int64_t ldgb,
+                                             const double* XL, const double* XU, int64_t ldxb, void* stream) {
+  return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, false, TOWR_GN_PC_NONE, nullptr, GL, GU, ldgb, XL, XU,
+                            ldxb, stream);
+}
+
+int towr_gpu_alsolve_gn_pc_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                                const towr_alsolve_state_t* state, const towr_gn_params_t* gn, int32_t precond,
+                                                double* DC, double* GSUM, int64_t ldgs, double* PC, const double* GL,
+                                                const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb,
+                                                void* stream) {
+  return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, true, precond, PC, GL, GU, ldgb, XL, XU, ldxb, stream);
 }
 
 }  // extern "C"

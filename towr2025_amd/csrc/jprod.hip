@@ -12,8 +12,8 @@
 //           the chunk's partial is added to the column's running sum in LDS, chunks in ascending order.
 // Every output element is one fixed tree of IEEE additions over exactly its own entries — no atomics, nothing that
 // depends on B, the block's place in the grid, the stream or timing — so the bits are a function of the problem alone.
-// Behind them: the Gauss-Newton direction (towr_gpu_gn_direction_batch_device), a whole CG solve per block on the same
-// walk and trees.
+// Behind them: the Gauss-Newton direction (towr_gpu_gn_direction_batch_device, and its Jacobi-preconditioned form
+// towr_gpu_gn_direction_pc_batch_device), a whole CG solve per block on the same walk and trees.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -250,9 +250,11 @@ __device__ inline void gn_jp_pass(const JpArgs& a, const double* Vb, const doubl
 }
 
 // z += J^T t: towr_jac_tvec_kernel's walk with t and the columns' running sums z in LDS (z zeroed by the caller, before
-// a barrier). Ends behind its own last barrier.
+// a barrier). Ends behind its own last barrier. DIAG: the same walk with the tile filled by w_i * (v * v) (w from act;
+// t is not read): z += diag(J^T W J), on the sums towr_jac_tvec_kernel would form on the squared values.
+template <bool DIAG>
 __device__ inline void gn_jtt_pass(const JpArgs& a, const double* Vb, const double* t, double* z, double* tile, uint16_t* cidx,
-                                   int tid) {
+                                   const uint8_t* act, int tid) {
 #pragma clang fp contract(off)
   double v[kGnPer];
   int32_t r[kGnPer];
@@ -271,7 +273,10 @@ __device__ inline void gn_jtt_pass(const JpArgs& a, const double* Vb, const doub
     const int64_t k0 = (int64_t)ci * kJpChunk;
 #pragma unroll
     for (int i = 0; i < kGnPer; ++i)
-      if (k0 + i * kGnBlock + tid < a.nnz) tile[i * kGnBlock + tid] = v[i] * t[r[i]];
+      if (k0 + i * kGnBlock + tid < a.nnz) {
+        if (DIAG) tile[i * kGnBlock + tid] = (act[r[i]] ? 1.0 : 0.0) * (v[i] * v[i]);
+        else tile[i * kGnBlock + tid] = v[i] * t[r[i]];
+      }
     reinterpret_cast<GnCx*>(cidx)[tid] = cx;
 #pragma unroll
     for (int i = 0; i < kGnPer; ++i) {
@@ -296,7 +301,12 @@ __device__ inline void gn_jtt_pass(const JpArgs& a, const double* Vb, const doub
   }
 }
 
-__global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
+// PCG: the Jacobi-preconditioned recursion of towr_gpu_gn_direction_pc_batch_device. M = rho diag(J^T W J) + mu (1.0
+// where that is exactly 0) lives in the problem's PC row as d lives in D: the lane that owns a column writes and reads
+// it. z = r ./ M is formed where r is updated and kept in the column accumulator (free between the passes) for the
+// update of p behind the sums; rn and rzn share one block_sums, so a step has the barriers of the plain one.
+template <bool PCG>
+__device__ __forceinline__ void gn_direction_body(const GnArgs& a) {
 #pragma clang fp contract(off)
   __shared__ double s_part[2][kGnWaves], s_bc[2];
   const int tid = threadIdx.x;
@@ -317,6 +327,7 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
   const double* Gb = a.GR + b * a.ldgr;
   const double* LPb = a.LAMP + b * a.ldlp;
   double* Db = a.D + b * a.ldd;
+  double* PCb = PCG ? a.PC + b * a.ldpc : nullptr;
   const double rho = a.RHO ? a.RHO[b] : a.rho;
   const double mu = a.mu;
   const double tol2 = a.tol * a.tol;
@@ -347,12 +358,32 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
         p[j] = g;
         r[j] = g;
       }
+      if (PCG) z[j] = 0.0;
     }
   }
   for (int i = tid; i < m; i += kGnBlock) act[i] = LPb[i] != 0.0;   // (a NaN is active)
   for (int i = tid; i < T.n_empty; i += kGnBlock) t[T.empty_rows[i]] = 0.0;   // rows without entries: never written again
   gn_block_sums<2>(v2, s_part, s_bc, tid);   // (its barriers: p, act and t are complete)
   const double bb = v2[0], nheld = v2[1];
+
+  // the diagonal on the J^T t walk, M into the PC row, z = r ./ M, p = z, rz = sum_free r z
+  double rz = 0.0, nzero = 0.0;
+  if (PCG) {
+    gn_jtt_pass<true>(T, Vb, nullptr, z, tile, cidx, act, tid);
+    double v3[2] = {0.0, 0.0};   // rz, the replaced count (exact)
+    int k = 0;
+    for (int j = tid; j < n; j += kGnBlock, ++k) {
+      if ((held >> k) & 1u) { PCb[j] = 0.0; continue; }
+      double mj = rho * z[j] + mu;
+      if (mj == 0.0) { mj = 1.0; v3[1] += 1.0; }
+      PCb[j] = mj;
+      const double rj = r[j], zj = rj / mj;
+      p[j] = zj;
+      v3[0] += rj * zj;
+    }
+    gn_block_sums<2>(v3, s_part, s_bc, tid);   // (its barriers: p is complete)
+    rz = v3[0]; nzero = v3[1];
+  }
 
   double rr = bb;
   int steps = 0, code = 0;
@@ -363,7 +394,7 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
       for (int j = tid; j < n; j += kGnBlock) z[j] = 0.0;
       gn_jp_pass(T, Vb, p, tile, carry, t, act, tid);
       __syncthreads();   // (also without a chunk: z is zero before the sums below)
-      gn_jtt_pass(T, Vb, t, z, tile, cidx, tid);
+      gn_jtt_pass<false>(T, Vb, t, z, tile, cidx, act, tid);
       double s1[1] = {0.0};   // sum_free p Hp
       int k = 0;
       for (int j = tid; j < n; j += kGnBlock, ++k) {
@@ -377,8 +408,8 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
       }
       gn_block_sums<1>(s1, s_part, s_bc, tid);
       if (!(s1[0] > 0.0)) { code = 2; break; }   // (a NaN anywhere ends here)
-      const double al = rr / s1[0];
-      double s2[1] = {0.0};   // sum_free r r
+      const double al = (PCG ? rz : rr) / s1[0];
+      double s2[PCG ? 2 : 1] = {};   // sum_free r r (and sum_free r z)
       k = 0;
       for (int j = tid; j < n; j += kGnBlock, ++k) {
         if ((held >> k) & 1u) continue;
@@ -387,12 +418,18 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
         const double rj = r[j] - al * z[j];
         r[j] = rj;
         s2[0] += rj * rj;
+        if (PCG) {
+          const double zj = rj / PCb[j];
+          z[j] = zj;
+          s2[PCG ? 1 : 0] += rj * zj;
+        }
       }
-      gn_block_sums<1>(s2, s_part, s_bc, tid);
-      const double beta = s2[0] / rr;
+      gn_block_sums<PCG ? 2 : 1>(s2, s_part, s_bc, tid);
+      const double beta = PCG ? s2[PCG ? 1 : 0] / rz : s2[0] / rr;
       k = 0;
       for (int j = tid; j < n; j += kGnBlock, ++k)
-        if (!((held >> k) & 1u)) p[j] = r[j] + beta * p[j];
+        if (!((held >> k) & 1u)) p[j] = (PCG ? z[j] : r[j]) + beta * p[j];
+      if (PCG) rz = s2[PCG ? 1 : 0];
       rr = s2[0];
       ++steps;
       __syncthreads();   // p is complete before the next pass reads it
@@ -420,8 +457,12 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) {
     Sb[3] = w[0];
     Sb[4] = nheld;
     Sb[5] = (double)code;
+    if (PCG) { Sb[6] = rz; Sb[7] = nzero; }
   }
 }
+
+__global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) { gn_direction_body<false>(a); }
+__global__ void __launch_bounds__(kGnBlock) towr_gn_direction_pc_kernel(GnArgs a) { gn_direction_body<true>(a); }
 
 }  // namespace
 
@@ -430,6 +471,7 @@ size_t gn_direction_lds(int n, int m) {
          (size_t)((m + 15) & ~15);
 }
 const void* gn_direction_kernel() { return reinterpret_cast<const void*>(&towr_gn_direction_kernel); }
+const void* gn_direction_pc_kernel() { return reinterpret_cast<const void*>(&towr_gn_direction_pc_kernel); }
 
 size_t jp_vec_lds(int n, int m) { return sizeof(double) * (size_t)(((n + 1) & ~1) + kJpChunk + 2); }
 size_t jp_tvec_lds(int n, int m) {

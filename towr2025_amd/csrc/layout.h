@@ -478,11 +478,13 @@ struct GnArgs {
   double mu, tol;
   int32_t ncg, reserved;
   JpArgs jp;
+  double* PC; int64_t ldpc;   // the preconditioned kernel's M rows (gn_direction_pc_kernel; the plain one reads neither)
 };
 constexpr int kGnBlock = 512;            // twice the product kernels' block: its LDS admits two blocks per CU
 constexpr int kGnMaxN = 32 * kGnBlock;   // the held mask is one 32-bit word per lane
 size_t gn_direction_lds(int n, int m);   // dynamic LDS (bytes)
 const void* gn_direction_kernel();
+const void* gn_direction_pc_kernel();   // the Jacobi-preconditioned recursion: the same block, walk and LDS
 
 // The resident GN loop's select (lbfgs.hip): per problem by the flags the line search wrote, D <- DC (bit 0), else
 // D <- GR (bit 2), else nothing; one block of kLbfgsBlock threads per problem.

@@ -196,6 +196,22 @@ class Engine {
     return towr_gpu_alsolve_gn_iterate_batch_device(h_, B, iters, &params, &state, &gn, DC, GSUM, ldgs, GL, GU, ldgb, XL, XU,
                                                     ldxb, stream);
   }
+  // the same two with a preconditioner (TOWR_GN_PC_NONE / TOWR_GN_PC_JACOBI): M into PC, SUM / GSUM of 8 entries
+  int GnDirectionPcBatchDevice(int B, const towr_gn_params_t& gn, int32_t precond, const double* V, int64_t ldv,
+                               const double* LAMP, int64_t ldlp, const double* RHO, double rho, const double* X, int64_t ldx,
+                               const double* GR, int64_t ldgr, const double* XL, const double* XU, int64_t ldb,
+                               const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd, double* SUM, int64_t lds,
+                               double* PC, int64_t ldpc, void* stream) const {
+    return towr_gpu_gn_direction_pc_batch_device(h_, B, &gn, precond, V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU,
+                                                 ldb, RUN, run_stride, D, ldd, SUM, lds, PC, ldpc, stream);
+  }
+  int AlsolveGnPcIterate(int B, int iters, const towr_alsolve_params_t& params, const towr_alsolve_state_t& state,
+                         const towr_gn_params_t& gn, int32_t precond, double* DC, double* GSUM, int64_t ldgs, double* PC,
+                         const double* GL, const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb,
+                         void* stream) const {
+    return towr_gpu_alsolve_gn_pc_iterate_batch_device(h_, B, iters, &params, &state, &gn, precond, DC, GSUM, ldgs, PC, GL, GU,
+                                                       ldgb, XL, XU, ldxb, stream);
+  }
   void SetProductsChunk(int problems) const { Check(towr_gpu_set_products_chunk(h_, problems)); }   // 0 = automatic
   // the objective kernel's persistent grid (towr_gpu_set_cost_grid / towr_gpu_cost_grid); 0 = automatic
   void SetCostGrid(int blocks) const { Check(towr_gpu_set_cost_grid(h_, blocks)); }

@@ -677,13 +677,20 @@ class TowrGpuProblem:
         or a 1-D tensor of B values. X None: every column is free. XL / XU: None (the handle's bounds), 1-D (shared) or
         (B, >= n). RUN: None, or an int32 tensor; problem b is skipped when RUN[b * run_stride] >= 2. SUM (B, >= 6):
         steps, bb, rr, slope sum g D, held columns, stop code (towr_gpu.h)."""
-        import torch
         B = GR.shape[0]
         ops = [(V, "V", self.nnz), (LAMP, "LAMP", self.m), (GR, "GR", self.n), (D, "D", self.n), (SUM, "SUM", 6)]
         if X is not None:
             ops.append((X, "X", self.n))
         self._check_rows(B, *ops)
         xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        rp, r, run = self._gn_rho_run(B, rho, RUN, run_stride)
+        self._check(self._lib.towr_gpu_gn_direction_batch_device(
+            self._h, B, C.byref(gn), *_opt(V), *_opt(LAMP), rp, r, *_opt(X), *_opt(GR), xl, xu, ldb, run, int(run_stride),
+            *_opt(D), *_opt(SUM), self._stream(stream, GR)))
+
+    def _gn_rho_run(self, B, rho, RUN, run_stride):
+        """(RHO pointer, scalar rho, RUN pointer) of a GN direction call."""
+        import torch
         if isinstance(rho, (int, float)):
             rp, r = C.c_void_p(None), float(rho)
         else:
@@ -695,9 +702,26 @@ class TowrGpuProblem:
                     or run_stride < 1 or RUN.numel() < (B - 1) * run_stride + 1:
                 raise TowrGpuError("RUN: expected a contiguous int32 tensor of >= (B - 1) run_stride + 1 entries on the handle's device")
             run = C.c_void_p(RUN.data_ptr())
-        self._check(self._lib.towr_gpu_gn_direction_batch_device(
-            self._h, B, C.byref(gn), *_opt(V), *_opt(LAMP), rp, r, *_opt(X), *_opt(GR), xl, xu, ldb, run, int(run_stride),
-            *_opt(D), *_opt(SUM), self._stream(stream, GR)))
+        return rp, r, run
+
+    def gn_pc_direction_batch_device(self, gn, V, LAMP, GR, D, SUM, PC=None, precond=capi.GN_PC_JACOBI, rho=1.0, X=None, XL=None,
+                                     XU=None, RUN=None, run_stride=1, stream=None):
+        """gn_direction_batch_device with a preconditioner: capi.GN_PC_JACOBI (the default) runs the CG recursion
+        preconditioned by M = rho_b diag(J^T W J) + mu (1 where that is exactly 0), which it writes to PC (B, >= n; 0 on
+        held columns); capi.GN_PC_NONE is gn_direction_batch_device bit for bit (PC may be None). SUM (B, >= 8): as
+        there, then [6] the final r.z and [7] the number of free columns whose M was replaced by 1 (towr_gpu.h)."""
+        B = GR.shape[0]
+        ops = [(V, "V", self.nnz), (LAMP, "LAMP", self.m), (GR, "GR", self.n), (D, "D", self.n), (SUM, "SUM", 8)]
+        if X is not None:
+            ops.append((X, "X", self.n))
+        if PC is not None:
+            ops.append((PC, "PC", self.n))
+        self._check_rows(B, *ops)
+        xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        rp, r, run = self._gn_rho_run(B, rho, RUN, run_stride)
+        self._check(self._lib.towr_gpu_gn_direction_pc_batch_device(
+            self._h, B, C.byref(gn), int(precond), *_opt(V), *_opt(LAMP), rp, r, *_opt(X), *_opt(GR), xl, xu, ldb, run,
+            int(run_stride), *_opt(D), *_opt(SUM), *_opt(PC), self._stream(stream, GR)))
 
     def alsolve_gn_iterate(self, params, st, gn, DC, GSUM, iters=1, GL=None, GU=None, XL=None, XU=None, stream=None):
         """alsolve_iterate with the Gauss-Newton direction: per iteration the evaluation, the CG solve at the candidate
@@ -713,6 +737,23 @@ class TowrGpuProblem:
         self._check(self._lib.towr_gpu_alsolve_gn_iterate_batch_device(
             self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
             gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
+
+    def alsolve_gn_pc_iterate(self, params, st, gn, DC, GSUM, PC=None, precond=capi.GN_PC_JACOBI, iters=1, GL=None, GU=None,
+                              XL=None, XU=None, stream=None):
+        """alsolve_gn_iterate with the direction of gn_pc_direction_batch_device: PC (B, the leading dimension of st.X)
+        takes the preconditioner of every CG solve, GSUM is (B, >= 8). precond = capi.GN_PC_NONE is alsolve_gn_iterate
+        bit for bit (towr_gpu.h)."""
+        c = self._alsolve_state(st, params)
+        ops = [(DC, "DC", self.n), (GSUM, "GSUM", 8)] + ([(PC, "PC", self.n)] if PC is not None else [])
+        self._check_rows(st.B, *ops)
+        if DC.stride(0) != st.X.stride(0) or (PC is not None and PC.stride(0) != st.X.stride(0)):
+            raise TowrGpuError("X, DC and PC: they share one leading dimension")
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        self._check(self._lib.towr_gpu_alsolve_gn_pc_iterate_batch_device(
+            self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), int(precond), C.c_void_p(DC.data_ptr()),
+            *_opt(GSUM), C.c_void_p(None if PC is None else PC.data_ptr()), gl, gu, ldgb, xl, xu, ldxb,
+            self._stream(stream, st.X)))
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
