@@ -821,6 +821,71 @@ int towr_gpu_alsolve_gn_pc_iterate_batch_device(towr_gpu_handle h, int32_t B, in
                                                 int64_t ldgs, double* PC, const double* GL, const double* GU, int64_t ldgb,
                                                 const double* XL, const double* XU, int64_t ldxb, void* stream);
 
+/* ---- a direct Gauss-Newton direction: batched envelope Cholesky of rho J^T W J + mu I ------------------------------- */
+#define TOWR_GN_ORDER_RCM 1
+
+/* The symbolic phase, on the host, once per handle (a layout-only handle answers too). The ordering is reverse
+ * Cuthill-McKee on the graph of J^T J (two columns are adjacent when a row of the pattern holds both), a function of the
+ * pattern alone: connected components in the order of their (degree, index)-smallest column; a breadth-first search that
+ * appends a node's unvisited neighbours by ascending (degree, index); the whole sequence reversed. It is run from two
+ * starts per component — that column itself, and the George-Liu pseudo-peripheral node found from it — and the ordering
+ * with the smaller envelope is kept (the pseudo-peripheral one on a tie). *ordering = TOWR_GN_ORDER_RCM. pos[j] (n ints) is
+ * the permuted position of column j; first[q] (n ints) the permuted position of the first entry of permuted row q of
+ * the lower triangle, first[q] <= q: every structural nonzero (q, c) of the permuted J^T J has first[q] <= c <= q.
+ * *envelope = sum_q (q - first[q] + 1), *bandwidth = max_q (q - first[q]), *ldw_min = the workspace doubles per problem
+ * of the entry below (the envelope: everything else the kernel needs lives in LDS). Any output pointer may be NULL.  */
+int towr_gpu_gn_factor_info(towr_gpu_handle h, int32_t* ordering, int32_t* pos, int32_t* first, int64_t* envelope,
+                            int64_t* bandwidth, int64_t* ldw_min);
+
+/* Per problem an exact solve of H d = g on the free columns, H = rho_b (J^T diag(w) J)_ff + mu I, by a Cholesky
+ * factorisation inside the envelope of towr_gpu_gn_factor_info. V, LAMP, w, RHO / rho, X, GR, XL, XU, ldb, the held
+ * columns, RUN / run_stride, D as for towr_gpu_gn_direction_batch_device; of gn only mu >= 0 is read (mu = 0 is valid).
+ * W is caller-owned DEVICE workspace of min(B, wrows) rows, ldw >= ldw_min, wrows >= 1: the call runs ceil(B / wrows)
+ * launches in sequence on the stream and problem b uses row b mod wrows; its contents after the call are unspecified.
+ * With q = pos[j], c = pos[k] the permuted positions of columns j, k:
+ *   assembly, into the envelope: H_qc = rho_b * a, a = sum_i w_i * (v_ij * v_ik) over the rows i that hold both columns in
+ *   ascending row order from 0.0 (two rounded products per term: a NaN or infinity in an inactive row still gives NaN);
+ *   the diagonal is rho_b * a + mu; an off-diagonal entry of the envelope whose columns share no row is +0.0; where j or
+ *   k is held the entry is 1.0 on the diagonal and 0.0 elsewhere;
+ *   factorisation L L^T in place, permuted columns c ascending: piv_c = H_cc - sum_k L_ck^2 (k ascending from first[c],
+ *   the sum from 0.0), L_cc = sqrt(piv_c), L_rc = (H_rc - sum_k L_rk L_ck) / L_cc for the rows r > c with first[r] <= c,
+ *   k ascending from max(first[r], first[c]) to c - 1, the sum from 0.0. The first column whose pivot is not > 0 (a NaN
+ *   counts) ends the problem: code 2, D = GR bit for bit, no other problem is affected;
+ *   L y = g~ (g~_q = g_j): y_q = (g~_q - sum_k L_qk y_k) / L_qq, k ascending from first[q], the sum from 0.0;
+ *   L^T d~ = y: d~_c = (y_c - sum_r L_rc d~_r) / L_cc over the rows r > c of the envelope in descending r, from 0.0;
+ *   D_j = d~_q on free columns, g_j bit for bit on held ones.
+ * Every square root and division is IEEE's; no product is contracted with a sum. bb = sum_free g^2 (the sum of the entry
+ * above); bb == 0 ends at once with code 3 and D = GR, without factorising. SUM[b*lds + ..] holds 8 doubles (lds >= 8):
+ * [0] 1.0 when solved, else 0.0; [1] bb; [2] the smallest and [6] the largest accepted pivot over the free columns
+ * (both 0.0 when there is none); [3] sum_j g_j D_j over all columns; [4] the number of held columns; [5] the code: 1
+ * solved, 2 breakdown, 3 bb == 0; [7] the permuted index of the breakdown column, or -1.0. A problem skipped by RUN has
+ * no byte of its D or SUM row touched. Every sum has one fixed order, so problem b's outputs are a function of its own
+ * operands alone: the same bits for any B, position, wrows, stream and run. No handle scratch is used and the kept
+ * Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for: NULL gn, V, LAMP, GR, D, SUM or W, mu negative or
+ * NaN, rho <= 0 or NaN with RHO == NULL, ldv < nnz, ldlp < m, ldx (with X) / ldgr / ldd < n, lds < 8, only one of
+ * XL / XU, 0 < ldb < n, ldw < ldw_min, wrows < 1, and a used W row that overlaps V, LAMP, X, GR, D or SUM.
+ * TOWR_ERR_UNSUPPORTED at the call when the envelope has 2^31 entries or more (the kernel's offsets are 32-bit) or the
+ * kernel's LDS (32 n + 16 bandwidth + m + n bytes and padding) does not fit the workgroup's 160 KiB less 1 KiB.     */
+int towr_gpu_gn_direction_direct_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn,
+                                              const double* V, int64_t ldv, const double* LAMP, int64_t ldlp,
+                                              const double* RHO, double rho, const double* X, int64_t ldx,
+                                              const double* GR, int64_t ldgr, const double* XL, const double* XU, int64_t ldb,
+                                              const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd,
+                                              double* SUM, int64_t lds, double* W, int64_t ldw, int32_t wrows, void* stream);
+
+/* towr_gpu_alsolve_gn_iterate_batch_device with that direction: step 2 calls towr_gpu_gn_direction_direct_batch_device
+ * on the chunk's values with W, ldw and wrows (wrows applies within each products chunk: a chunk of cb problems uses
+ * min(cb, wrows) rows); ldgs >= 8. Everything else is that entry's: the select, the line search, the outer update.
+ * Bit-identical to the public calls in sequence, whatever the products chunk. TOWR_ERR_INVALID before anything runs for
+ * what that entry refuses except gn's ncg and tol (not read), NULL W, ldw < ldw_min, wrows < 1, ldgs < 8, and a used W
+ * row that overlaps LAMP, XC, GRC, DC or GSUM. TOWR_ERR_UNSUPPORTED as for the L-BFGS kernels and the direct direction. */
+int towr_gpu_alsolve_gn_direct_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters,
+                                                    const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                                    const towr_gn_params_t* gn, double* DC, double* GSUM, int64_t ldgs,
+                                                    double* W, int64_t ldw, int32_t wrows,
+                                                    const double* GL, const double* GU, int64_t ldgb,
+                                                    const double* XL, const double* XU, int64_t ldxb, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

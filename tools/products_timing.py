@@ -30,6 +30,9 @@
   (x) gn_pc_direction_batch_device (the Jacobi-preconditioned recursion) on the operands of (v) at ncg = NCG and (x1) at
       ncg = 1, beside v and v1: x1 - v1 is the diagonal pass with the PC row's write, (x - x1) - (v - v1) what the
       division and the PC row's read add to NCG - 1 steps,
+  (y) gn_direct_direction_batch_device (the envelope Cholesky solve of the same system, mu = 1e-2) on the operands of (v)
+      with a workspace of WROWS rows (default: B), beside x: with NCG=100 ONLY=x,y,z the comparison of DESIGN 4m;
+  (z) alsolve_gn_direct_iterate(iters = 1) in a running solve of its own from X (mu = 1e-2), beside (w),
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -52,6 +55,7 @@ ROUNDS = int(os.environ.get("ROUNDS", "5"))
 MEM = int(os.environ.get("MEM", "8"))
 NCG = int(os.environ.get("NCG", "8"))
 ONLY = set(os.environ.get("ONLY", "").split(",")) - {""}
+WROWS = int(os.environ.get("WROWS", "0"))   # rows of the direct direction's workspace (0: B)
 PEAK = 8.0e12
 
 
@@ -154,6 +158,16 @@ def run(name, f, B):
     DCg, GSg = torch.empty_like(stg.X), torch.empty((B, 8), dtype=torch.float64, device=dev)
     codes_g, steps_g = [], []
     codes = []
+    # the direct direction's workspace, its outputs and a running solve of its own
+    info = p.gn_factor_info()
+    wrows = min(B, WROWS) if WROWS > 0 else B
+    Wd = torch.empty((wrows, ld(info["ldw_min"])), dtype=torch.float64, device=dev)
+    Dy, YSUM = torch.empty_like(P), torch.empty((B, 16), dtype=torch.float64, device=dev)
+    sty = AlSolveState.allocate(p, B, mem)
+    sty.X.copy_(Xs[:, :p.n])
+    p.alsolve_init(part, sty, stream=stream)
+    DCy, GSy = torch.empty_like(sty.X), torch.empty((B, 8), dtype=torch.float64, device=dev)
+    codes_y, dcodes_y = [], []
     bytes_ls = 8 * (10 * p.n + 30) * B
     bytes_out = 8 * 2 * p.m * B
     for key, nb in (("r", bytes_ls), ("u", bytes_out)):
@@ -171,6 +185,10 @@ def run(name, f, B):
     gn_iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_gn_iterate_batch_device(
         p._h, B, 1, C.byref(part), C.byref(cg), C.byref(gnw), C.c_void_p(DCg.data_ptr()), C.c_void_p(GSg.data_ptr()), GSg.stride(0),
         None, None, 0, None, None, 0, sp))
+    cy = p._alsolve_state(sty, part)
+    direct_iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_gn_direct_iterate_batch_device(
+        p._h, B, 1, C.byref(part), C.byref(cy), C.byref(gnw), C.c_void_p(DCy.data_ptr()), C.c_void_p(GSy.data_ptr()), GSy.stride(0),
+        C.c_void_p(Wd.data_ptr()), Wd.stride(0), wrows, None, None, 0, None, None, 0, sp))
     iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_iterate_batch_device(p._h, B, 1, C.byref(part), C.byref(ct), None, None, 0,
                                                                               None, None, 0, sp))
 
@@ -218,7 +236,11 @@ def run(name, f, B):
                 (f"x gn pc direction ncg={NCG}", lambda: p.gn_pc_direction_batch_device(gnv, V, LAMP, GRg, Dx, XSUM, PC=PCx, rho=rho, X=Xs,
                                                                                        stream=stream)),
                 ("x1 gn pc direction ncg=1", lambda: p.gn_pc_direction_batch_device(gnv1, V, LAMP, GRg, Dx, XSUM, PC=PCx, rho=rho, X=Xs,
-                                                                                   stream=stream))]
+                                                                                   stream=stream)),
+                (f"y gn direct wrows={wrows}", lambda: p.gn_direct_direction_batch_device(gnv, V, LAMP, GRg, Dy, YSUM, Wd, wrows=wrows, rho=rho,
+                                                                                         X=Xs, stream=stream)),
+                ("z alsolve gn direct iterate", lambda: (p.set_products_chunk(0), direct_iter_call(),
+                                                         codes_y.append(sty.LSUM[:, 0].clone()), dcodes_y.append(GSy[:, 5].clone())))]
     if ONLY:
         variants = [(k, fn) for k, fn in variants if k.split()[0] in ONLY]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
@@ -251,6 +273,16 @@ def run(name, f, B):
               f"vs v1 {mx['v1']:.4f} ms, x1 - v1 {mx['x1'] - mx['v1']:.4f} ms; per step (x - x1) / {NCG - 1} "
               f"{(mx['x'] - mx['x1']) / max(NCG - 1, 1):.4f} ms vs (v - v1) / {NCG - 1} {(mx['v'] - mx['v1']) / max(NCG - 1, 1):.4f} ms; "
               f"columns whose M was replaced {XSUM[:, 7].mean().item():.2f}", flush=True)
+    if not ONLY or {"x", "y"} <= ONLY:
+        my = {k.split()[0]: statistics.median(times[k]) for k, _ in variants if k.split()[0] in ("x", "y", "z", "w")}
+        line = (f"  gn direct: envelope {info['envelope']} entries ({8 * info['envelope'] / 1024:.0f} KiB per problem), bandwidth "
+                f"{info['bandwidth']}, wrows {wrows}: y {my['y']:.4f} ms vs x (ncg={NCG}) {my['x']:.4f} ms, ratio {my['y'] / my['x']:.3f}; "
+                f"solved {(YSUM[:, 5] == 1).double().mean().item():.3f} of the problems")
+        if "z" in my:
+            hist_y = torch.bincount(torch.stack(codes_y).flatten().to(torch.int64), minlength=6).tolist()
+            line += (f"; direct iteration z {my['z']:.4f} ms" + (f" vs w {my['w']:.4f} ms" if "w" in my else "") +
+                     f"; solved per timed iteration {(torch.stack(dcodes_y) == 1).double().mean().item():.3f}; LSUM[0] codes 0..5 {hist_y}")
+        print(line, flush=True)
     if ONLY:
         p.set_products_chunk(0)
         return

@@ -75,6 +75,7 @@ DATA_LINEAR_M, DATA_SOFT_BOUNDS, DATA_BOUNDS, DATA_VAR_BOUNDS = 0, 1, 2, 3
 MAX_COSTS = 128
 LBFGS_MAX_MEM = 16   # TOWR_LBFGS_MAX_MEM
 GN_PC_NONE, GN_PC_JACOBI = 0, 1   # TOWR_GN_PC_*: the preconditioner of towr_gpu_gn_direction_pc_batch_device
+GN_ORDER_RCM = 1                  # TOWR_GN_ORDER_RCM: the ordering towr_gpu_gn_factor_info reports
 
 
 AL_RESTART, AL_SEARCH, AL_CONVERGED, AL_STALLED, AL_MAXED = range(5)   # TOWR_AL_*: the phases of the resident loop
@@ -244,6 +245,17 @@ SYMBOLS = {
                                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                                C.c_void_p, C.c_void_p, C.c_int64,
                                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_gn_factor_info": (C.c_int, [_HANDLE, _IP, _IP, _IP, _LP, _LP, _LP]),
+    "towr_gpu_gn_direction_direct_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(GnParams), C.c_void_p, C.c_int64,
+                                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_int64,
+                                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                             C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "towr_gpu_alsolve_gn_direct_iterate_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.POINTER(AlSolveParams),
+                                                                   C.POINTER(AlSolveStateC), C.POINTER(GnParams), C.c_void_p,
+                                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                                   C.c_void_p, C.c_void_p, C.c_int64,
+                                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1,6 +1,7 @@
 // auglag.hip — the batched solver-step entry points of the C-ABI (include/towr_gpu.h), what a device-resident
 // augmented-Lagrangian loop calls between evaluations: Jacobian products (J p, J^T lam), constraint residuals and
-// multiplier updates, the projected step, the L-BFGS history and direction, the Gauss-Newton (CG) direction, and the
+// multiplier updates, the projected step, the L-BFGS history and direction, the Gauss-Newton direction (CG, or direct
+// with its ordering and envelope found here on the host), and the
 // fused sequences of these behind an evaluation. Host code only: the kernels live in jprod.hip, resid.hip, step.hip and lbfgs.hip, their argument
 // structs in layout.h. The evaluator (towr_gpu.hip) is used through handle.h alone: launch, launch_cost,
 // batch_terrain, bind and the scratch helpers.
@@ -24,6 +25,7 @@ using namespace tg::host;
 
 void towr_gpu_handle_s::AugLag::release() {
   for (void* p : d_jp) if (p) (void)hipFree(p);
+  for (void* p : d_gf) if (p) (void)hipFree(p);
   void* rest[] = {d_pv, d_set_row0, d_blo, d_bup, d_rg, d_rl, d_set_col0, d_xlo, d_xup, d_sd, d_sf};
   for (void* p : rest) if (p) (void)hipFree(p);
 }
@@ -110,6 +112,159 @@ int gn_ready(towr_gpu_handle h) {
     if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   al.gn_ready = true;
+  return TOWR_OK;
+}
+
+// ---- the direct GN direction's symbolic phase (towr_gpu_gn_factor_info) ------------------------------------------------
+// The ordering is reverse Cuthill-McKee on the graph of J^T J (two columns are adjacent when a row holds both): per
+// connected component, components taken in the order of their (degree, index)-smallest column, a breadth-first search
+// that appends a node's unvisited neighbours by ascending (degree, index); the whole sequence reversed. Two start rules
+// are run — the component's (degree, index)-smallest column itself, and the George-Liu pseudo-peripheral node found
+// from it (repeat: the (degree, index)-smallest node of the last level of the search from the current node, while the
+// depth grows) — and the ordering with the smaller envelope is kept (the pseudo-peripheral one on a tie). Everything is
+// a function of the pattern alone.
+using Adjacency = std::vector<std::vector<int32_t>>;
+
+Adjacency jtj_adjacency(const Layout& L) {
+  Adjacency adj(L.n);
+  std::vector<int32_t> mark(L.n, -1);
+  for (int j = 0; j < L.n; ++j) {
+    mark[j] = j;
+    for (int64_t p = L.col_ptr[j]; p < L.col_ptr[j + 1]; ++p) {
+      const int i = L.csc_row[p];
+      for (int64_t e = L.row_ptr[i]; e < L.row_ptr[i + 1]; ++e) {
+        const int k = L.col[e];
+        if (mark[k] != j) { mark[k] = j; adj[j].push_back(k); }
+      }
+    }
+    std::sort(adj[j].begin(), adj[j].end());
+  }
+  return adj;
+}
+
+// (degree, index) order
+struct ByDegree {
+  const Adjacency& adj;
+  bool operator()(int32_t u, int32_t v) const {
+    return adj[u].size() != adj[v].size() ? adj[u].size() < adj[v].size() : u < v;
+  }
+};
+
+int32_t pseudo_peripheral(const Adjacency& adj, int32_t s, std::vector<int32_t>& dist, std::vector<int32_t>& queue) {
+  const ByDegree less{adj};
+  int depth = -1;
+  for (;;) {
+    queue.assign(1, s);
+    dist[s] = 0;
+    for (size_t head = 0; head < queue.size(); ++head)
+      for (int32_t v : adj[queue[head]])
+        if (dist[v] < 0) { dist[v] = dist[queue[head]] + 1; queue.push_back(v); }
+    const int d = dist[queue.back()];
+    int32_t cand = queue.back();
+    for (int32_t v : queue)
+      if (dist[v] == d && less(v, cand)) cand = v;
+    for (int32_t v : queue) dist[v] = -1;
+    if (d <= depth || cand == s) return s;
+    depth = d;
+    s = cand;
+  }
+}
+
+// order[q] = the column at permuted position q
+std::vector<int32_t> reverse_cuthill_mckee(const Adjacency& adj, bool peripheral) {
+  const int n = (int)adj.size();
+  const ByDegree less{adj};
+  std::vector<int32_t> by_degree(n), order, dist(n, -1), queue;
+  for (int j = 0; j < n; ++j) by_degree[j] = j;
+  std::sort(by_degree.begin(), by_degree.end(), less);
+  std::vector<char> seen(n, 0);
+  order.reserve(n);
+  for (int32_t s : by_degree) {
+    if (seen[s]) continue;
+    if (peripheral) s = pseudo_peripheral(adj, s, dist, queue);
+    size_t head = order.size();
+    order.push_back(s);
+    seen[s] = 1;
+    for (; head < order.size(); ++head) {
+      const size_t a0 = order.size();
+      for (int32_t v : adj[order[head]])
+        if (!seen[v]) { seen[v] = 1; order.push_back(v); }
+      std::sort(order.begin() + a0, order.end(), less);
+    }
+  }
+  std::reverse(order.begin(), order.end());
+  return order;
+}
+
+// pos and first of an ordering; returns the envelope (entries of the lower triangle with the diagonal)
+int64_t envelope_of(const Adjacency& adj, const std::vector<int32_t>& order, std::vector<int32_t>& pos, std::vector<int32_t>& first) {
+  const int n = (int)adj.size();
+  pos.assign(n, 0);
+  first.assign(n, 0);
+  for (int q = 0; q < n; ++q) pos[order[q]] = q;
+  int64_t env = 0;
+  for (int q = 0; q < n; ++q) {
+    int32_t f = q;
+    for (int32_t v : adj[order[q]]) f = std::min(f, pos[v]);
+    first[q] = f;
+    env += q - f + 1;
+  }
+  return env;
+}
+
+// the host tables of the direct direction, once per handle (a layout-only handle too)
+void gn_factor_tables(towr_gpu_handle h) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.gf_built) return;
+  const int n = h->L.n;
+  const Adjacency adj = jtj_adjacency(h->L);
+  std::vector<int32_t> pos, first;
+  al.gf_inv = reverse_cuthill_mckee(adj, true);
+  al.gf_env = envelope_of(adj, al.gf_inv, al.gf_pos, al.gf_first);
+  const std::vector<int32_t> plain = reverse_cuthill_mckee(adj, false);
+  if (envelope_of(adj, plain, pos, first) < al.gf_env) {
+    al.gf_inv = plain;
+    al.gf_env = envelope_of(adj, plain, al.gf_pos, al.gf_first);
+  }
+  al.gf_last.assign(n, 0);
+  al.gf_row_off.assign(n + 1, 0);
+  al.gf_width = 0;
+  int64_t off = 0;
+  for (int q = 0; q < n; ++q) {
+    const int32_t f = al.gf_first[q];
+    al.gf_width = std::max(al.gf_width, q - f);
+    al.gf_last[q] = q;
+    for (int c = f; c < q; ++c) al.gf_last[c] = q;   // (q ascending: the last writer is the largest row)
+    al.gf_row_off[q] = (int32_t)std::min<int64_t>(off, INT32_MAX);
+    off += q - f + 1;
+  }
+  al.gf_row_off[n] = (int32_t)std::min<int64_t>(off, INT32_MAX);
+  al.gf_built = true;
+}
+
+// the direct direction's kernel: its offsets are 32-bit and its per-column state and pivot rows live in LDS (1 KiB kept
+// free beside it, as for the CG kernel)
+int gn_direct_fits(towr_gpu_handle h) {
+  gn_factor_tables(h);
+  if (h->al.gf_env > INT32_MAX || gn_direct_lds(h->L.n, h->L.m, h->al.gf_width) + 1024 > kLdsMax)
+    return fail(h, TOWR_ERR_UNSUPPORTED, "problem too large for the direct GN direction (envelope >= 2^31 entries, or its LDS)");
+  return TOWR_OK;
+}
+int gn_direct_ready(towr_gpu_handle h) {
+  if (int rc = products_ready(h)) return rc;
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.gnd_ready) return TOWR_OK;
+  if (int rc = gn_direct_fits(h)) return rc;
+  const size_t lds = gn_direct_lds(h->L.n, h->L.m, al.gf_width);
+  if (lds > 64 * 1024 && hipFuncSetAttribute(gn_direct_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  Uploads u{h};
+  const int32_t* d[7] = {};
+  u.add(&d[0], al.gf_pos); u.add(&d[1], al.gf_inv); u.add(&d[2], al.gf_first); u.add(&d[3], al.gf_last); u.add(&d[4], al.gf_row_off);
+  u.add(&d[5], h->L.csc_row); u.add(&d[6], h->L.csc_index);
+  if (int rc = u.commit()) return rc;
+  for (int i = 0; i < 7; ++i) al.d_gf[i] = const_cast<int32_t*>(d[i]);
+  al.gnd_ready = true;
   return TOWR_OK;
 }
 
@@ -219,6 +374,28 @@ int gn_pc_params(towr_gpu_handle h, int32_t precond, const double* PC, int64_t l
   if (PC && ldpc < h->L.n) return fail(h, TOWR_ERR_INVALID, "gn: leading dimension of PC (ldpc) smaller than n");
   if (lds < 8) return fail(h, TOWR_ERR_INVALID, "leading dimension of the GN summary smaller than 8");
   return TOWR_OK;
+}
+
+// the direct direction's own arguments: of gn only the damping is read; where its outputs go; the caller's workspace
+// (problem b of a call uses row b mod wrows)
+struct GnWorkspace { double* W; int64_t ldw; int32_t wrows; };
+int gn_direct_params(towr_gpu_handle h, const towr_gn_params_t* gn, const double* D, const double* SUM, int64_t lds, const GnWorkspace& ws) {
+  if (!gn) return fail(h, TOWR_ERR_INVALID, "null gn params");
+  if (!(gn->mu >= 0)) return fail(h, TOWR_ERR_INVALID, "gn: mu is negative or NaN");
+  if (!D || !SUM) return fail(h, TOWR_ERR_INVALID, "null GN direction or summary (D / SUM, DC / GSUM)");
+  if (lds < 8) return fail(h, TOWR_ERR_INVALID, "leading dimension of the GN summary smaller than 8");
+  if (!ws.W) return fail(h, TOWR_ERR_INVALID, "gn: null workspace W");
+  if (ws.wrows < 1) return fail(h, TOWR_ERR_INVALID, "gn: wrows must be >= 1");
+  gn_factor_tables(h);
+  if (ws.ldw < h->al.gf_env) return fail(h, TOWR_ERR_INVALID, "gn: ldw smaller than ldw_min (towr_gpu_gn_factor_info)");
+  return TOWR_OK;
+}
+// a workspace row in use shares a byte with [q, q + (B - 1) ld + len)
+bool ws_overlap(towr_gpu_handle h, int B, const GnWorkspace& ws, const double* q, int64_t ldq, int64_t lenq) {
+  if (!q || B < 1) return false;
+  const double* we = ws.W + (std::min<int64_t>(B, ws.wrows) - 1) * ws.ldw + h->al.gf_env;
+  const double* qe = q + (int64_t)(B - 1) * ldq + lenq;
+  return ws.W < qe && q < we;
 }
 
 // ---- the resident loop's parameters and state (towr_alsolve_params_t / towr_alsolve_state_t) ---------------------------
@@ -333,6 +510,30 @@ int launch_gn(towr_gpu_handle h, int B, GnArgs a, hipStream_t s) {
   return TOWR_OK;
 }
 
+// (XL NULL: the handle's bounds, one row — with X, after step_ready; after gn_direct_ready.) ceil(B / wrows) launches in
+// sequence: problem b of launch l is block b - l wrows and owns workspace row b mod wrows.
+int launch_gn_direct(towr_gpu_handle h, int B, GnDirectArgs a, int wrows, hipStream_t s) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (a.X && !a.XL) { a.XL = al.d_xlo; a.XU = al.d_xup; a.ldb = 0; }
+  const int32_t* const* t = reinterpret_cast<const int32_t* const*>(al.d_gf);
+  a.pos = t[0]; a.inv = t[1]; a.first = t[2]; a.last = t[3]; a.row_off = t[4]; a.csc_row = t[5]; a.csc_index = t[6];
+  a.col_ptr = al.jp.col_ptr;
+  a.n = h->L.n; a.m = h->L.m; a.env = (int32_t)al.gf_env; a.width = al.gf_width;
+  const size_t lds = gn_direct_lds(a.n, a.m, a.width);
+  const int step = std::min(wrows, B);
+  for (int c0 = 0; c0 < B; c0 += step) {
+    GnDirectArgs g = a;
+    g.V = a.V + (int64_t)c0 * a.ldv; g.LAMP = a.LAMP + (int64_t)c0 * a.ldlp; g.RHO = row_at(a.RHO, c0, 1);
+    g.X = row_at(a.X, c0, a.ldx); g.GR = a.GR + (int64_t)c0 * a.ldgr;
+    g.XL = row_at(a.XL, c0, a.ldb); g.XU = row_at(a.XU, c0, a.ldb);
+    g.RUN = row_at(a.RUN, c0, a.run_stride);
+    g.D = a.D + (int64_t)c0 * a.ldd; g.SUM = a.SUM + (int64_t)c0 * a.lds;
+    void* args[] = {&g};
+    HIPCHK(h, launch_kernel(gn_direct_kernel(), dim3((unsigned)std::min(step, B - c0)), dim3(kGnBlock), args, lds, s));
+  }
+  return TOWR_OK;
+}
+
 int launch_gn_select(towr_gpu_handle h, int B, const towr_alsolve_state_t& st, const double* DC, hipStream_t s) {
   GnSelectArgs a{st.ISTATE, DC, st.ldx, st.GR, st.ldx, st.D, st.ldx, h->L.n, 0};
   void* args[] = {&a};
@@ -391,10 +592,11 @@ int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> r
 // stay in handle scratch (d_rg / d_rl). e, r and z hold the whole batch's operands (r.G, z.V and z.Vec are not used); a
 // chunk launches with its rows of them. With gn (the resident GN loop): behind a chunk's product, while its values are
 // still in d_pv, the GN direction at (e.X, z.Out) with that lam+ and rho into the chunk's rows of gn->D / gn->SUM (of gn
-// the bounds, RUN, D, SUM and the CG parameters are used).
+// the bounds, RUN, D, SUM and the CG parameters are used); with gd the direct direction in its place (of gd the bounds,
+// RUN, D, SUM, the workspace and mu).
 struct EvalStage { const double* X; int64_t ldx; double* G; int64_t ldg; };
 int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r, const JpArgs& z, const Batch& b,
-                  const GnArgs* gn = nullptr) {
+                  const GnArgs* gn = nullptr, const GnDirectArgs* gd = nullptr, int wrows = 0) {
   towr_gpu_handle_s::AugLag& al = h->al;
   const int64_t ldv = ld16(h->L.nnz), ldr = ld16(h->L.m);
   const int C = chunk_plan(h, B);
@@ -427,6 +629,19 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
       g.SUM = gn->SUM + (int64_t)c0 * gn->lds;
       if (gn->PC) g.PC = gn->PC + (int64_t)c0 * gn->ldpc;
       rc = launch_gn(h, cb, g, b.s);
+    }
+    if (rc == TOWR_OK && gd) {   // (the direct direction: wrows applies within the chunk)
+      GnDirectArgs g = *gd;
+      g.V = al.d_pv; g.ldv = ldv;
+      g.LAMP = a.LAMP; g.ldlp = a.ldlp;
+      g.RHO = a.RHO; g.rho = r.rho;
+      g.X = e.X + (int64_t)c0 * e.ldx; g.ldx = e.ldx;
+      g.GR = z.Out + (int64_t)c0 * z.ldo; g.ldgr = z.ldo;
+      g.XL = row_at(gd->XL, c0, gd->ldb); g.XU = row_at(gd->XU, c0, gd->ldb);
+      g.RUN = row_at(gd->RUN, c0, gd->run_stride);
+      g.D = gd->D + (int64_t)c0 * gd->ldd;
+      g.SUM = gd->SUM + (int64_t)c0 * gd->lds;
+      rc = launch_gn_direct(h, cb, g, wrows, b.s);
     }
   }
   return rc;
@@ -820,11 +1035,17 @@ int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const to
 static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                               const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC, double* GSUM,
                               int64_t ldgs, bool pc, int32_t precond, double* PC, const double* GL, const double* GU, int64_t ldgb,
-                              const double* XL, const double* XU, int64_t ldxb, void* stream) {
+                              const double* XL, const double* XU, int64_t ldxb, void* stream, const GnWorkspace* ws = nullptr) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
-  if (int rc = gn_params(h, gn, DC, GSUM, ldgs)) return rc;
+  if (int rc = ws ? gn_direct_params(h, gn, DC, GSUM, ldgs, *ws) : gn_params(h, gn, DC, GSUM, ldgs)) return rc;
   const towr_alsolve_state_t& st = *state;
+  if (ws) {
+    const int64_t n = h->L.n;
+    if (ws_overlap(h, B, *ws, DC, st.ldx, n) || ws_overlap(h, B, *ws, st.XC, st.ldx, n) || ws_overlap(h, B, *ws, st.GRC, st.ldx, n) ||
+        ws_overlap(h, B, *ws, st.LAMP, st.ldl, h->L.m) || ws_overlap(h, B, *ws, GSUM, ldgs, 8))
+      return fail(h, TOWR_ERR_INVALID, "gn: W overlaps LAMP, XC, GRC, DC or GSUM");
+  }
   if (pc) {
     if (int rc = gn_pc_params(h, precond, PC, st.ldx, ldgs)) return rc;
     if (precond != TOWR_GN_PC_JACOBI) PC = nullptr;
@@ -842,17 +1063,24 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
   g.D = DC; g.ldd = st.ldx; g.SUM = GSUM; g.lds = ldgs;
   g.PC = PC; g.ldpc = st.ldx;
   g.mu = gn->mu; g.tol = gn->tol; g.ncg = gn->ncg;
+  GnDirectArgs gd{};   // (as g, for the direct direction)
+  gd.XL = XL; gd.XU = XU; gd.ldb = ldxb;
+  gd.RUN = st.ISTATE; gd.run_stride = 4;
+  gd.D = DC; gd.ldd = st.ldx; gd.SUM = GSUM; gd.lds = ldgs;
+  gd.mu = gn->mu;
+  if (ws) { gd.W = ws->W; gd.ldw = ws->ldw; }
   const StepArgs step{st.X, st.ldx, st.D, st.ldx, st.ALPHA, 0.0, XL, XU, ldxb, st.XC, st.ldx, st.SSUM, st.ldss};
   if (int rc = bind(h)) return rc;
   if (int rc = lbfgs_fits(h)) return rc;
-  if (int rc = gn_fits(h)) return rc;
+  if (int rc = ws ? gn_direct_fits(h) : gn_fits(h)) return rc;
   if (iters == 0) return TOWR_OK;
-  return fused(h, B, stream, {gn_ready, residual_ready, step_ready}, [&](const Batch& b) {
+  return fused(h, B, stream, {ws ? gn_direct_ready : gn_ready, residual_ready, step_ready}, [&](const Batch& b) {
     int rc = TOWR_OK;
     for (int it = 0; it < iters && rc == TOWR_OK; ++it) {
       rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
       if (rc == TOWR_OK)
-        rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b, &g);
+        rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b,
+                           ws ? nullptr : &g, ws ? &gd : nullptr, ws ? ws->wrows : 0);
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
       if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
       if (rc == TOWR_OK) rc = launch_gn_select(h, B, st, DC, b.s);
@@ -876,6 +1104,58 @@ int towr_gpu_alsolve_gn_pc_iterate_batch_device(towr_gpu_handle h, int32_t B, in
                                                 const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb,
                                                 void* stream) {
   return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, true, precond, PC, GL, GU, ldgb, XL, XU, ldxb, stream);
+}
+
+// ---- the direct Gauss-Newton direction (jprod.hip): envelope Cholesky of rho (J^T W J)_ff + mu I -----------------------
+int towr_gpu_gn_factor_info(towr_gpu_handle h, int32_t* ordering, int32_t* pos, int32_t* first, int64_t* envelope,
+                            int64_t* bandwidth, int64_t* ldw_min) {
+  if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
+  gn_factor_tables(h);
+  const towr_gpu_handle_s::AugLag& al = h->al;
+  if (ordering) *ordering = TOWR_GN_ORDER_RCM;
+  if (pos && h->L.n) std::memcpy(pos, al.gf_pos.data(), sizeof(int32_t) * al.gf_pos.size());
+  if (first && h->L.n) std::memcpy(first, al.gf_first.data(), sizeof(int32_t) * al.gf_first.size());
+  if (envelope) *envelope = al.gf_env;
+  if (bandwidth) *bandwidth = al.gf_width;
+  if (ldw_min) *ldw_min = al.gf_env;
+  return TOWR_OK;
+}
+
+int towr_gpu_gn_direction_direct_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, const double* V,
+                                              int64_t ldv, const double* LAMP, int64_t ldlp, const double* RHO, double rho,
+                                              const double* X, int64_t ldx, const double* GR, int64_t ldgr, const double* XL,
+                                              const double* XU, int64_t ldb, const int32_t* RUN, int32_t run_stride, double* D,
+                                              int64_t ldd, double* SUM, int64_t lds, double* W, int64_t ldw, int32_t wrows,
+                                              void* stream) {
+  if (!h || B < 0 || !V || !LAMP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null V, LAMP or GR, or B < 0)");
+  const GnWorkspace ws{W, ldw, wrows};
+  if (int rc = gn_direct_params(h, gn, D, SUM, lds, ws)) return rc;
+  const Layout& L = h->L;
+  if (ws_overlap(h, B, ws, V, ldv, L.nnz) || ws_overlap(h, B, ws, LAMP, ldlp, L.m) || ws_overlap(h, B, ws, X, ldx, L.n) ||
+      ws_overlap(h, B, ws, GR, ldgr, L.n) || ws_overlap(h, B, ws, D, ldd, L.n) || ws_overlap(h, B, ws, SUM, lds, 8))
+    return fail(h, TOWR_ERR_INVALID, "gn: W overlaps V, LAMP, X, GR, D or SUM");
+  if (!RHO && !(rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 without RHO");
+  if (ldv < L.nnz || ldlp < L.m || (X && ldx < L.n) || ldgr < L.n || ldd < L.n)
+    return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAMP) / n (X, GR, D)");
+  if (int rc = box_args(h, XL, XU, ldb, L.n, "XL / XU", "n")) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = gn_direct_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = gn_direct_ready(h)) return rc;
+  if (X && !XL)
+    if (int rc = step_ready(h)) return rc;
+  GnDirectArgs a{V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN, run_stride, D, ldd, SUM, lds, W, ldw, gn->mu};
+  return launch_gn_direct(h, B, a, wrows, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_alsolve_gn_direct_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                                    const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC,
+                                                    double* GSUM, int64_t ldgs, double* W, int64_t ldw, int32_t wrows,
+                                                    const double* GL, const double* GU, int64_t ldgb, const double* XL,
+                                                    const double* XU, int64_t ldxb, void* stream) {
+  const GnWorkspace ws{W, ldw, wrows};
+  return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, false, TOWR_GN_PC_NONE, nullptr, GL, GU, ldgb, XL, XU,
+                            ldxb, stream, &ws);
 }
 
 }  // extern "C"

@@ -148,6 +148,15 @@ struct towr_gpu_handle_s {
     int64_t pv_cap = 0;
     int32_t products_chunk = 0;
     bool gn_ready = false;   // the GN direction kernel's LDS fits and its limit is raised (gn_ready; after products_ready)
+    // The direct GN direction (towr_gpu_gn_factor_info): the ordering and the envelope of the lower triangle of the
+    // pattern of J^T J under it, built on the host by the first call that asks (a layout-only handle answers too), and
+    // their device copies with the pattern by column (gn_direct_ready; after products_ready)
+    bool gf_built = false;
+    std::vector<int32_t> gf_pos, gf_inv, gf_first, gf_last, gf_row_off;
+    int64_t gf_env = 0;
+    int32_t gf_width = 0;
+    bool gnd_ready = false;
+    void* d_gf[7] = {};
     // Residuals (resid.hip): the device copies of the constraint sets' row ranges and of the description bounds
     // (residual_ready), and the fused entries' g / lam+ scratch (a chunk of problems)
     bool res_ready = false;

@@ -13,7 +13,8 @@
 // Every output element is one fixed tree of IEEE additions over exactly its own entries — no atomics, nothing that
 // depends on B, the block's place in the grid, the stream or timing — so the bits are a function of the problem alone.
 // Behind them: the Gauss-Newton direction (towr_gpu_gn_direction_batch_device, and its Jacobi-preconditioned form
-// towr_gpu_gn_direction_pc_batch_device), a whole CG solve per block on the same walk and trees.
+// towr_gpu_gn_direction_pc_batch_device), a whole CG solve per block on the same walk and trees; and the direct
+// direction (towr_gpu_gn_direction_direct_batch_device), an envelope Cholesky solve of the same system per block.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -464,7 +465,190 @@ __device__ __forceinline__ void gn_direction_body(const GnArgs& a) {
 __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_kernel(GnArgs a) { gn_direction_body<false>(a); }
 __global__ void __launch_bounds__(kGnBlock) towr_gn_direction_pc_kernel(GnArgs a) { gn_direction_body<true>(a); }
 
+// ---- the direct Gauss-Newton direction (towr_gpu_gn_direction_direct_batch_device) -----------------------------------
+// One block of kGnBlock threads per problem, resident for the assembly, the factorisation and both solves. L lives in
+// the problem's workspace row in global memory (the envelope in permuted order, row by row, the diagonal last in its
+// row); per permuted column the running sums (sum_k L_qk^2, sum_k L_qk y_k), y and the diagonal of L live in LDS.
+//   assembly: one lane per envelope entry merges the two columns' sorted by-column row lists, rows ascending;
+//   factorisation, columns ascending: the pivot row's segment is staged in LDS (double-buffered: the segment of column
+//   c + 1 is staged during column c, its last entry put there by the lane that computes it), every lane forms the pivot
+//   and y_c on the same bits, lanes are spread over the rows r > c whose envelope reaches c; one barrier per column.
+//   The forward solve rides on it (y_c is known when column c starts; the lane of row r adds L_rc y_c to the row's sum);
+//   the backward solve, columns descending: d_c on the same bits in every lane, lanes spread over row c of L (contiguous
+//   in the workspace), each adding L_ck d_c to the running sum of column k; one barrier per column.
+// Every sum has one fixed order (ascending k in the factorisation and the forward solve, descending row in the backward
+// solve, ascending row in the assembly), so the stop decision (the first pivot that is not > 0) is block-uniform.
+__global__ void __launch_bounds__(kGnBlock) towr_gn_direct_kernel(GnDirectArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double s_part[2][kGnWaves], s_bc[2];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  if (a.RUN && a.RUN[b * a.run_stride] >= 2) return;   // (block-uniform: before any barrier)
+  const int n = a.n, m = a.m;
+  const int n2 = (n + 1) & ~1, w2 = (a.width + 2) & ~1;
+  double* dsum = jp_lds;          // n: sum_k L_qk^2 so far; in the backward solve sum_r L_rq d_r so far
+  double* zacc = dsum + n2;       // n: sum_k L_qk y_k so far
+  double* y = zacc + n2;          // n
+  double* diag = y + n2;          // n: L_qq
+  double* seg = diag + n2;        // 2 w2: the pivot rows of an even / odd column
+  uint8_t* act = reinterpret_cast<uint8_t*>(seg + 2 * w2);   // m: the row is active (w = 1)
+  uint8_t* heldq = act + ((m + 15) & ~15);                    // n: the column at permuted position q is held
+  const double* Vb = a.V + b * a.ldv;
+  const double* Gb = a.GR + b * a.ldgr;
+  const double* LPb = a.LAMP + b * a.ldlp;
+  double* Db = a.D + b * a.ldd;
+  double* Lb = a.W + b * a.ldw;
+  const double rho = a.RHO ? a.RHO[b] : a.rho;
+  const double mu = a.mu;
+
+  // the held columns (lbfgs.hip's rule) by permuted position, bb = sum_free g^2
+  double v2[2] = {0.0, 0.0};   // bb, the held count (exact)
+  {
+    const double* Xb = a.X ? a.X + b * a.ldx : nullptr;
+    const double* Lo = a.X ? a.XL + b * a.ldb : nullptr;
+    const double* Up = a.X ? a.XU + b * a.ldb : nullptr;
+    for (int j = tid; j < n; j += kGnBlock) {
+      const double g = Gb[j];
+      bool h = false;
+      if (Xb) {
+        const double x = Xb[j], l = Lo[j], u = Up[j];
+        const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+        h = (has_l && x <= l && g > 0.0) || (has_u && x >= u && g < 0.0) || (has_l && has_u && l == u);
+      }
+      heldq[a.pos[j]] = h;
+      if (h) v2[1] += 1.0;
+      else v2[0] += g * g;
+      dsum[j] = 0.0;
+      zacc[j] = 0.0;
+    }
+  }
+  for (int i = tid; i < m; i += kGnBlock) act[i] = LPb[i] != 0.0;   // (a NaN is active)
+  gn_block_sums<2>(v2, s_part, s_bc, tid);   // (its barriers: heldq, act and the running sums are complete)
+  const double bb = v2[0], nheld = v2[1];
+
+  int code = 1, bcol = -1;
+  double pmin = __builtin_inf(), pmax = 0.0;
+  if (bb == 0.0) code = 3;
+  else {
+    // assembly: entry e of the envelope is (q, c), c <= q; lane tid takes e = tid, tid + kGnBlock, ...
+    int q = 0;
+    for (int e = tid; e < a.env; e += kGnBlock) {
+      while (a.row_off[q + 1] <= e) ++q;
+      const int c = a.first[q] + (e - a.row_off[q]);
+      double val;
+      if (heldq[q] | heldq[c]) val = q == c ? 1.0 : 0.0;
+      else {
+        const int j = a.inv[q], k = a.inv[c];
+        int pa = a.col_ptr[j], pb = a.col_ptr[k];
+        const int ea = a.col_ptr[j + 1], eb = a.col_ptr[k + 1];
+        double acc = 0.0;
+        bool any = false;
+        if (pa < ea && pb < eb) {
+          int ra = a.csc_row[pa], rb = a.csc_row[pb];
+          for (;;) {
+            if (ra == rb) {
+              const double t = Vb[a.csc_index[pa]] * Vb[a.csc_index[pb]];
+              acc += (act[ra] ? 1.0 : 0.0) * t;
+              any = true;
+              ++pa; ++pb;
+              if (pa >= ea || pb >= eb) break;
+              ra = a.csc_row[pa]; rb = a.csc_row[pb];
+            } else if (ra < rb) {
+              if (++pa >= ea) break;
+              ra = a.csc_row[pa];
+            } else {
+              if (++pb >= eb) break;
+              rb = a.csc_row[pb];
+            }
+          }
+        }
+        if (q == c) val = rho * acc + mu;
+        else val = any ? rho * acc : 0.0;   // (no shared row: +0.0 as it stands)
+      }
+      Lb[e] = val;
+    }
+    __syncthreads();
+
+    // factorisation and forward solve, columns ascending
+    for (int c = 0; c < n; ++c) {
+      const double* buf = seg + (c & 1) * w2;
+      double* nbuf = seg + ((c + 1) & 1) * w2;
+      const int f = a.first[c];
+      const double piv = Lb[a.row_off[c + 1] - 1] - dsum[c];
+      if (!(piv > 0.0)) { code = 2; bcol = c; break; }   // (a NaN too; block-uniform, before this column's barrier)
+      if (!heldq[c]) {
+        if (piv < pmin) pmin = piv;
+        if (piv > pmax) pmax = piv;
+      }
+      const double lcc = __builtin_sqrt(piv);
+      const double yc = (Gb[a.inv[c]] - zacc[c]) / lcc;
+      if (tid == 0) { diag[c] = lcc; y[c] = yc; }
+      int f1 = 0;
+      if (c + 1 < n) {   // the next pivot row's entries left of c are final: stage them
+        f1 = a.first[c + 1];
+        const double* Ln = Lb + a.row_off[c + 1] - f1;
+        for (int k = f1 + tid; k < c; k += kGnBlock) nbuf[k - f1] = Ln[k];
+      }
+      const int lastc = a.last[c];
+      for (int r = c + 1 + tid; r <= lastc; r += kGnBlock) {
+        const int fr = a.first[r];
+        if (fr > c) continue;
+        double* Lr = Lb + a.row_off[r] - fr;   // Lr[k] = L_rk
+        double s = 0.0;
+        for (int k = fr > f ? fr : f; k < c; ++k) s += Lr[k] * buf[k - f];
+        const double l = (Lr[c] - s) / lcc;
+        Lr[c] = l;
+        dsum[r] += l * l;
+        zacc[r] += l * yc;
+        if (r == c + 1) nbuf[c - f1] = l;
+      }
+      __syncthreads();
+    }
+
+    // backward solve, columns descending: d_c = (y_c - sum_{r > c} L_rc d_r) / L_cc, the sum in descending r
+    if (code == 1) {
+      for (int j = tid; j < n; j += kGnBlock) dsum[j] = 0.0;
+      __syncthreads();
+      for (int c = n - 1; c >= 0; --c) {
+        const double dc = (y[c] - dsum[c]) / diag[c];
+        const int f = a.first[c];
+        const double* Lc = Lb + a.row_off[c] - f;
+        for (int k = f + tid; k < c; k += kGnBlock) dsum[k] += Lc[k] * dc;
+        if (tid == 0 && !heldq[c]) Db[a.inv[c]] = dc;
+        __syncthreads();
+      }
+    }
+  }
+
+  // D on the held columns (or everywhere unless solved) and the slope sum g D over all columns
+  double w[1] = {0.0};
+  for (int j = tid; j < n; j += kGnBlock) {
+    const double g = Gb[j];
+    double d = g;
+    if (code == 1 && !heldq[a.pos[j]]) d = Db[j];
+    else Db[j] = g;
+    w[0] += g * d;
+  }
+  gn_block_sums<1>(w, s_part, s_bc, tid);
+  if (tid == 0) {
+    double* Sb = a.SUM + b * a.lds;
+    Sb[0] = code == 1 ? 1.0 : 0.0;
+    Sb[1] = bb;
+    Sb[2] = pmin == __builtin_inf() ? 0.0 : pmin;
+    Sb[3] = w[0];
+    Sb[4] = nheld;
+    Sb[5] = (double)code;
+    Sb[6] = pmax;
+    Sb[7] = (double)bcol;
+  }
+}
+
 }  // namespace
+
+size_t gn_direct_lds(int n, int m, int width) {
+  return sizeof(double) * (size_t)(4 * ((n + 1) & ~1) + 2 * ((width + 2) & ~1)) + (size_t)((m + 15) & ~15) + (size_t)((n + 15) & ~15);
+}
+const void* gn_direct_kernel() { return reinterpret_cast<const void*>(&towr_gn_direct_kernel); }
 
 size_t gn_direction_lds(int n, int m) {
   return sizeof(double) * (size_t)(3 * ((n + 1) & ~1) + ((m + 1) & ~1) + kJpChunk + 2) + sizeof(uint16_t) * kJpChunk +

@@ -486,6 +486,32 @@ size_t gn_direction_lds(int n, int m);   // dynamic LDS (bytes)
 const void* gn_direction_kernel();
 const void* gn_direction_pc_kernel();   // the Jacobi-preconditioned recursion: the same block, walk and LDS
 
+// The direct Gauss-Newton direction (jprod.hip, towr_gpu_gn_direction_direct_batch_device): one block of kGnBlock
+// threads per problem assembles H = rho (J^T W J)_ff + mu I (identity on held columns) into the envelope of its lower
+// triangle under the handle's ordering, factorises it L L^T in place and solves. The envelope lives in the problem's
+// workspace row (W + blockIdx.x * ldw; the host offsets the other operands per launch): permuted row q holds the
+// entries of permuted columns first[q] .. q at row_off[q] .. row_off[q + 1] - 1, the diagonal last. inv[q] is the
+// column at permuted position q, last[c] the largest permuted row whose envelope reaches permuted column c; the
+// pattern by column (col_ptr of jp, csc_row, csc_index) feeds the assembly. width = max_q (q - first[q]).
+struct GnDirectArgs {
+  const double* V; int64_t ldv;
+  const double* LAMP; int64_t ldlp;
+  const double* RHO; double rho;
+  const double* X; int64_t ldx;
+  const double* GR; int64_t ldgr;
+  const double *XL, *XU; int64_t ldb;
+  const int32_t* RUN; int64_t run_stride;
+  double* D; int64_t ldd;
+  double* SUM; int64_t lds;
+  double* W; int64_t ldw;
+  double mu;
+  const int32_t *pos, *inv, *first, *last, *row_off;   // n, n, n, n, n + 1
+  const int32_t *col_ptr, *csc_row, *csc_index;        // n + 1, nnz, nnz
+  int32_t n, m, env, width;
+};
+size_t gn_direct_lds(int n, int m, int width);   // dynamic LDS (bytes)
+const void* gn_direct_kernel();
+
 // The resident GN loop's select (lbfgs.hip): per problem by the flags the line search wrote, D <- DC (bit 0), else
 // D <- GR (bit 2), else nothing; one block of kLbfgsBlock threads per problem.
 struct GnSelectArgs {

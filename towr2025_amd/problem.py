@@ -755,6 +755,63 @@ class TowrGpuProblem:
             *_opt(GSUM), C.c_void_p(None if PC is None else PC.data_ptr()), gl, gu, ldgb, xl, xu, ldxb,
             self._stream(stream, st.X)))
 
+    def gn_factor_info(self):
+        """The symbolic phase of the direct Gauss-Newton direction (a layout-only handle answers too): dict(ordering
+        (capi.GN_ORDER_RCM), pos (n; the permuted position of column j), first (n; the first permuted column of permuted
+        row q of the lower triangle of J^T J), envelope, bandwidth, ldw_min (workspace doubles per problem))."""
+        pos = np.zeros(self.n, dtype=np.int32)
+        first = np.zeros(self.n, dtype=np.int32)
+        o = C.c_int32(0)
+        env, bw, ldw = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.towr_gpu_gn_factor_info(self._h, C.byref(o), capi.iptr(pos), capi.iptr(first), C.byref(env),
+                                                      C.byref(bw), C.byref(ldw)))
+        return dict(ordering=o.value, pos=pos, first=first, envelope=env.value, bandwidth=bw.value, ldw_min=ldw.value)
+
+    def _gn_workspace(self, W, wrows, B):
+        """(pointer, ldw, wrows) of a direct direction's workspace W (rows, >= ldw_min): wrows None takes W's rows."""
+        _check_tensor(W, "W", 1, self.device)
+        if W.dim() != 2 or W.shape[0] < 1:
+            raise TowrGpuError("W: expected a 2-D tensor of >= 1 rows")
+        wrows = W.shape[0] if wrows is None else int(wrows)
+        if wrows > W.shape[0]:
+            raise TowrGpuError(f"W: {W.shape[0]} rows, wrows = {wrows}")
+        ldw = W.stride(0) if W.shape[0] > 1 else W.shape[1]
+        return C.c_void_p(W.data_ptr()), ldw, wrows
+
+    def gn_direct_direction_batch_device(self, gn, V, LAMP, GR, D, SUM, W, wrows=None, rho=1.0, X=None, XL=None, XU=None,
+                                         RUN=None, run_stride=1, stream=None):
+        """gn_direction_batch_device's system solved exactly: per problem the envelope Cholesky factorisation of
+        rho_b (J^T W J)_ff + mu I under gn_factor_info's ordering and two triangular solves; of gn only mu is read. W
+        (rows, >= ldw_min) is the workspace: the call runs ceil(B / wrows) launches and problem b uses row b mod wrows
+        (wrows None: every row of W). SUM (B, >= 8): solved, bb, smallest pivot, slope sum g D, held columns, code
+        (1 solved, 2 breakdown, 3 bb == 0), largest pivot, breakdown column or -1 (towr_gpu.h)."""
+        B = GR.shape[0]
+        ops = [(V, "V", self.nnz), (LAMP, "LAMP", self.m), (GR, "GR", self.n), (D, "D", self.n), (SUM, "SUM", 8)]
+        if X is not None:
+            ops.append((X, "X", self.n))
+        self._check_rows(B, *ops)
+        xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        rp, r, run = self._gn_rho_run(B, rho, RUN, run_stride)
+        wp, ldw, wr = self._gn_workspace(W, wrows, B)
+        self._check(self._lib.towr_gpu_gn_direction_direct_batch_device(
+            self._h, B, C.byref(gn), *_opt(V), *_opt(LAMP), rp, r, *_opt(X), *_opt(GR), xl, xu, ldb, run, int(run_stride),
+            *_opt(D), *_opt(SUM), wp, ldw, wr, self._stream(stream, GR)))
+
+    def alsolve_gn_direct_iterate(self, params, st, gn, DC, GSUM, W, wrows=None, iters=1, GL=None, GU=None, XL=None, XU=None,
+                                  stream=None):
+        """alsolve_gn_iterate with the direction of gn_direct_direction_batch_device: W / wrows its workspace (wrows
+        applies within each products chunk), GSUM is (B, >= 8) (towr_gpu.h)."""
+        c = self._alsolve_state(st, params)
+        self._check_rows(st.B, (DC, "DC", self.n), (GSUM, "GSUM", 8))
+        if DC.stride(0) != st.X.stride(0):
+            raise TowrGpuError("X and DC: they share one leading dimension")
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        wp, ldw, wr = self._gn_workspace(W, wrows, st.B)
+        self._check(self._lib.towr_gpu_alsolve_gn_direct_iterate_batch_device(
+            self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
+            wp, ldw, wr, gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
+
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
         self._check(self._lib.towr_gpu_set_products_chunk(self._h, int(k)))
