@@ -886,6 +886,72 @@ int towr_gpu_alsolve_gn_direct_iterate_batch_device(towr_gpu_handle h, int32_t B
                                                     const double* GL, const double* GU, int64_t ldgb,
                                                     const double* XL, const double* XU, int64_t ldxb, void* stream);
 
+/* ---- the direct Gauss-Newton direction on 16 x 16 tiles: a block Cholesky inside the tile envelope ------------------ */
+#define TOWR_GN_TILE 16
+
+/* The tile envelope of towr_gpu_gn_factor_info's ordering, on the host, once per handle (a layout-only handle answers
+ * too). *tile = TOWR_GN_TILE, *nt = ceil(n / 16) block rows; bfirst[I] (nt ints) = min over the permuted rows q in
+ * [16 I, min(n, 16 I + 16)) of first[q] / 16 (first of towr_gpu_gn_factor_info), bfirst[I] <= I: block row I stores the
+ * tiles (I, bfirst[I]) .. (I, I), which cover every entry of the scalar envelope in its rows. *tiles = sum_I (I -
+ * bfirst[I] + 1). A block envelope has no fill outside itself, so this is the whole symbolic phase. *ldw_min = 256 *
+ * *tiles exactly: the workspace doubles per problem of the entry below are its stored tiles and nothing else (everything
+ * else the kernel needs lives in LDS). Permuted rows and columns n .. 16 nt - 1 are padding: the identity on the diagonal,
+ * 0 elsewhere, nothing read from V. Any output pointer may be NULL.                                                   */
+int towr_gpu_gn_tile_info(towr_gpu_handle h, int32_t* tile, int32_t* nt, int32_t* bfirst, int64_t* tiles, int64_t* ldw_min);
+
+/* towr_gpu_gn_direction_direct_batch_device's system, arguments, held rule, codes and SUM slots, with the factorisation
+ * done as a block Cholesky on the stored tiles. Kept from that entry word for word: V, LAMP, w, RHO / rho, X, GR, XL, XU,
+ * ldb, RUN / run_stride (a skipped problem has no byte of its D or SUM row touched), mu, the launches (ceil(B / wrows) in
+ * sequence, problem b uses row b mod wrows of W, whose contents after the call are unspecified), bb and its sum, bb == 0
+ * giving code 3 without factorising, D = GR bit for bit on held columns and on every column under code 2 or 3, SUM[0..7]
+ * (pivots of padding columns are not counted in [2] and [6]); [7] is the scalar permuted column (16 J + k) of the first
+ * pivot that is not > 0 (a NaN counts), or -1.0.
+ *   assembly: every stored entry (q, c), c <= q < n, is the direct entry's H_qc by the same per-entry sum (rows ascending
+ *   from 0.0, +0.0 where the columns share no row — also everywhere left of the scalar envelope —, rho_b * a + mu on the
+ *   diagonal, the identity where j or k is held): bit-equal to that entry's H wherever both hold the entry. The rows of
+ *   every entry's sum are listed once per handle at the first device call: sum over the rows of J of len (len + 1) / 2
+ *   terms of 12 bytes of device memory (ANYmal trot: 4 MiB; with phase-duration optimisation: 158 MiB);
+ *   factorisation, left-looking by block column J ascending, on tiles A_IJ (I >= J, bfirst[I] <= J):
+ *     A_IJ <- H_IJ - sum_K L_IK L_JK^T, tile index K ascending from max(bfirst[I], bfirst[J]) to J - 1, and within a tile
+ *     k ascending in groups of four: one v_mfma_f64_16x16x4_f64 per group subtracts its four products from the running
+ *     tile (its first operand negated, which is exact), their inner order and rounding the instruction's;
+ *     the diagonal tile unblocked, k = 0 .. 15 ascending: piv = A_kk; the first pivot that is not > 0 ends the problem
+ *     (code 2); L_kk = sqrt(piv); L_rk = A_rk / L_kk for r > k; then A_rc <- A_rc - L_rk * L_ck for k < c <= r (a
+ *     rounded product, then a rounded difference);
+ *     the tiles under it, each row on its own: L_rc = (A_rc - L_r0 L_c0 - ... - L_r,c-1 L_c,c-1) / L_cc, c ascending,
+ *     the products subtracted one by one in ascending k, each rounded;
+ *   L y = g~ by blocks: for block J, s_r = sum over K ascending and k of L_rk y_k in four partial sums (k mod 4; each
+ *   from 0.0, k ascending), combined (p0 + p1) + (p2 + p3); t_r = g~_r - s_r; then with the diagonal tile, k ascending:
+ *   y_k = t_k / L_kk, t_r <- t_r - L_rk * y_k for r > k;
+ *   L^T d~ = y by blocks descending: t_c = y_c - acc_c; k = 15 .. 0: d~_k = t_k / L_kk, t_c <- t_c - L_kc * d~_k for c < k;
+ *   then for every stored tile (J, K), K < J: acc_c += sum_r L_rc d~_r, the sum from 0.0 in descending r; acc starts at
+ *   0.0 and receives the block rows in descending J;
+ *   D_j = d~_q on free columns, g_j bit for bit on held ones.
+ * Apart from the v_mfma_f64_16x16x4_f64 no product is contracted with a sum; every square root and division is IEEE's.
+ * This order is one fixed order per handle, so problem b's outputs are a function of its own operands alone: the same
+ * bits for any B, position, wrows, stream and run. They are NOT promised to equal the direct entry's bits, and no host
+ * restatement is promised to match them bit for bit (the instruction's inner order is not stated). No handle scratch is
+ * used and the kept Jacobian is not dropped. TOWR_ERR_INVALID as for the direct entry, with ldw_min that of
+ * towr_gpu_gn_tile_info. TOWR_ERR_UNSUPPORTED at the call when 256 * tiles or the number of the assembly's terms
+ * reaches 2^31 (the kernel's offsets are 32-bit) or the kernel's LDS (16 nt * 17 + 2048 + m bytes and padding: per-column state and one tile; the factor is read from
+ * the workspace, not held in LDS) does not fit the workgroup's 160 KiB less 1 KiB.                                    */
+int towr_gpu_gn_direction_tiled_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn,
+                                             const double* V, int64_t ldv, const double* LAMP, int64_t ldlp,
+                                             const double* RHO, double rho, const double* X, int64_t ldx,
+                                             const double* GR, int64_t ldgr, const double* XL, const double* XU, int64_t ldb,
+                                             const int32_t* RUN, int32_t run_stride, double* D, int64_t ldd,
+                                             double* SUM, int64_t lds, double* W, int64_t ldw, int32_t wrows, void* stream);
+
+/* towr_gpu_alsolve_gn_direct_iterate_batch_device with the tiled direction in step 2 (W rows of towr_gpu_gn_tile_info's
+ * ldw_min). Bit-identical to the public calls in sequence, whatever the products chunk. The refusals are that entry's,
+ * TOWR_ERR_UNSUPPORTED as for the L-BFGS kernels and the tiled direction.                                              */
+int towr_gpu_alsolve_gn_tiled_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters,
+                                                   const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                                   const towr_gn_params_t* gn, double* DC, double* GSUM, int64_t ldgs,
+                                                   double* W, int64_t ldw, int32_t wrows,
+                                                   const double* GL, const double* GU, int64_t ldgb,
+                                                   const double* XL, const double* XU, int64_t ldxb, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

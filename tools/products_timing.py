@@ -33,6 +33,9 @@
   (y) gn_direct_direction_batch_device (the envelope Cholesky solve of the same system, mu = 1e-2) on the operands of (v)
       with a workspace of WROWS rows (default: B), beside x: with NCG=100 ONLY=x,y,z the comparison of DESIGN 4m;
   (z) alsolve_gn_direct_iterate(iters = 1) in a running solve of its own from X (mu = 1e-2), beside (w),
+  (yt) gn_tiled_direction_batch_device (the block Cholesky on 16 x 16 tiles) on the operands and with the WROWS of (y), and
+  (zt) alsolve_gn_tiled_iterate(iters = 1) in a running solve of its own beside (z): with NCG=100 WROWS=1024
+      ONLY=x,y,z,w,yt,zt the comparison of DESIGN 4n (the letters t and u were taken),
 for ANYmal trot at B = 4096 and ANYmal stairs with phase-duration optimisation at B = 1024. Each product's achieved
 rate is 8 (nnz + n + m) B / time, printed against the 8 TB/s peak. HIP events around windows of REPS calls after a
 warm-up of every shape; the windows alternate between the variants and the median and the spread over ROUNDS are
@@ -168,6 +171,15 @@ def run(name, f, B):
     p.alsolve_init(part, sty, stream=stream)
     DCy, GSy = torch.empty_like(sty.X), torch.empty((B, 8), dtype=torch.float64, device=dev)
     codes_y, dcodes_y = [], []
+    # the tiled direction's workspace, its outputs and a running solve of its own
+    tinfo = p.gn_tile_info()
+    Wt = torch.empty((wrows, ld(tinfo["ldw_min"])), dtype=torch.float64, device=dev)
+    Dt, TSUM = torch.empty_like(P), torch.empty((B, 16), dtype=torch.float64, device=dev)
+    stz = AlSolveState.allocate(p, B, mem)
+    stz.X.copy_(Xs[:, :p.n])
+    p.alsolve_init(part, stz, stream=stream)
+    DCt, GSt = torch.empty_like(stz.X), torch.empty((B, 8), dtype=torch.float64, device=dev)
+    codes_t, dcodes_t = [], []
     bytes_ls = 8 * (10 * p.n + 30) * B
     bytes_out = 8 * 2 * p.m * B
     for key, nb in (("r", bytes_ls), ("u", bytes_out)):
@@ -189,6 +201,10 @@ def run(name, f, B):
     direct_iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_gn_direct_iterate_batch_device(
         p._h, B, 1, C.byref(part), C.byref(cy), C.byref(gnw), C.c_void_p(DCy.data_ptr()), C.c_void_p(GSy.data_ptr()), GSy.stride(0),
         C.c_void_p(Wd.data_ptr()), Wd.stride(0), wrows, None, None, 0, None, None, 0, sp))
+    cz = p._alsolve_state(stz, part)
+    tiled_iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_gn_tiled_iterate_batch_device(
+        p._h, B, 1, C.byref(part), C.byref(cz), C.byref(gnw), C.c_void_p(DCt.data_ptr()), C.c_void_p(GSt.data_ptr()), GSt.stride(0),
+        C.c_void_p(Wt.data_ptr()), Wt.stride(0), wrows, None, None, 0, None, None, 0, sp))
     iter_call = lambda: p._check(p._lib.towr_gpu_alsolve_iterate_batch_device(p._h, B, 1, C.byref(part), C.byref(ct), None, None, 0,
                                                                               None, None, 0, sp))
 
@@ -240,7 +256,11 @@ def run(name, f, B):
                 (f"y gn direct wrows={wrows}", lambda: p.gn_direct_direction_batch_device(gnv, V, LAMP, GRg, Dy, YSUM, Wd, wrows=wrows, rho=rho,
                                                                                          X=Xs, stream=stream)),
                 ("z alsolve gn direct iterate", lambda: (p.set_products_chunk(0), direct_iter_call(),
-                                                         codes_y.append(sty.LSUM[:, 0].clone()), dcodes_y.append(GSy[:, 5].clone())))]
+                                                         codes_y.append(sty.LSUM[:, 0].clone()), dcodes_y.append(GSy[:, 5].clone()))),
+                (f"yt gn tiled wrows={wrows}", lambda: p.gn_tiled_direction_batch_device(gnv, V, LAMP, GRg, Dt, TSUM, Wt, wrows=wrows, rho=rho,
+                                                                                        X=Xs, stream=stream)),
+                ("zt alsolve gn tiled iterate", lambda: (p.set_products_chunk(0), tiled_iter_call(),
+                                                         codes_t.append(stz.LSUM[:, 0].clone()), dcodes_t.append(GSt[:, 5].clone())))]
     if ONLY:
         variants = [(k, fn) for k, fn in variants if k.split()[0] in ONLY]
     for _, fn in variants:   # warm-up: every shape, the tables' upload, the scratch at its largest
@@ -282,6 +302,16 @@ def run(name, f, B):
             hist_y = torch.bincount(torch.stack(codes_y).flatten().to(torch.int64), minlength=6).tolist()
             line += (f"; direct iteration z {my['z']:.4f} ms" + (f" vs w {my['w']:.4f} ms" if "w" in my else "") +
                      f"; solved per timed iteration {(torch.stack(dcodes_y) == 1).double().mean().item():.3f}; LSUM[0] codes 0..5 {hist_y}")
+        print(line, flush=True)
+    if not ONLY or {"y", "yt"} <= ONLY:
+        mt = {k.split()[0]: statistics.median(times[k]) for k, _ in variants if k.split()[0] in ("y", "z", "yt", "zt")}
+        line = (f"  gn tiled: {tinfo['tiles']} tiles ({8 * tinfo['ldw_min'] / 1024:.0f} KiB per problem), wrows {wrows}: yt {mt['yt']:.4f} ms "
+                f"vs y {mt['y']:.4f} ms, yt / y {mt['yt'] / mt['y']:.4f}; code 1 on {(TSUM[:, 5] == 1).double().mean().item():.3f} (yt) and "
+                f"{(YSUM[:, 5] == 1).double().mean().item():.3f} (y) of the problems")
+        if "z" in mt and "zt" in mt:
+            hist_t = torch.bincount(torch.stack(codes_t).flatten().to(torch.int64), minlength=6).tolist()
+            line += (f"; tiled iteration zt {mt['zt']:.4f} ms vs z {mt['z']:.4f} ms, zt / z {mt['zt'] / mt['z']:.4f}; solved per timed "
+                     f"iteration {(torch.stack(dcodes_t) == 1).double().mean().item():.3f}; LSUM[0] codes 0..5 {hist_t}")
         print(line, flush=True)
     if ONLY:
         p.set_products_chunk(0)

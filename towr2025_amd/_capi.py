@@ -76,6 +76,7 @@ MAX_COSTS = 128
 LBFGS_MAX_MEM = 16   # TOWR_LBFGS_MAX_MEM
 GN_PC_NONE, GN_PC_JACOBI = 0, 1   # TOWR_GN_PC_*: the preconditioner of towr_gpu_gn_direction_pc_batch_device
 GN_ORDER_RCM = 1                  # TOWR_GN_ORDER_RCM: the ordering towr_gpu_gn_factor_info reports
+GN_TILE = 16                      # TOWR_GN_TILE: the tile edge towr_gpu_gn_tile_info reports
 
 
 AL_RESTART, AL_SEARCH, AL_CONVERGED, AL_STALLED, AL_MAXED = range(5)   # TOWR_AL_*: the phases of the resident loop
@@ -256,6 +257,17 @@ SYMBOLS = {
                                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                                                    C.c_void_p, C.c_void_p, C.c_int64,
                                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_gn_tile_info": (C.c_int, [_HANDLE, _IP, _IP, _IP, _LP, _LP]),
+    "towr_gpu_gn_direction_tiled_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(GnParams), C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "towr_gpu_alsolve_gn_tiled_iterate_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.POINTER(AlSolveParams),
+                                                                  C.POINTER(AlSolveStateC), C.POINTER(GnParams), C.c_void_p,
+                                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                                  C.c_void_p, C.c_void_p, C.c_int64,
+                                                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

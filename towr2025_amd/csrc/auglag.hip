@@ -26,6 +26,7 @@ using namespace tg::host;
 void towr_gpu_handle_s::AugLag::release() {
   for (void* p : d_jp) if (p) (void)hipFree(p);
   for (void* p : d_gf) if (p) (void)hipFree(p);
+  for (void* p : d_gt) if (p) (void)hipFree(p);
   void* rest[] = {d_pv, d_set_row0, d_blo, d_bup, d_rg, d_rl, d_set_col0, d_xlo, d_xup, d_sd, d_sf};
   for (void* p : rest) if (p) (void)hipFree(p);
 }
@@ -268,6 +269,102 @@ int gn_direct_ready(towr_gpu_handle h) {
   return TOWR_OK;
 }
 
+// ---- the tiled direct direction's symbolic phase (towr_gpu_gn_tile_info) -------------------------------------------------
+// The 16 x 16 tile envelope of the ordering above: block row I stores the tiles bfirst[I] .. I. A block envelope has no
+// fill outside itself, so this is the whole symbolic phase. Once per handle (a layout-only handle too).
+void gn_tile_tables(towr_gpu_handle h) {
+  gn_factor_tables(h);
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.gt_built) return;
+  const int n = h->L.n, nt = (n + kGnTile - 1) / kGnTile;
+  al.gt_bfirst.assign(nt, 0);
+  al.gt_tile_off.assign(nt + 1, 0);
+  std::vector<std::vector<int32_t>> below(nt);   // per block column the block rows under its diagonal tile
+  int64_t off = 0;
+  for (int I = 0; I < nt; ++I) {
+    int32_t bf = I;
+    for (int q = kGnTile * I; q < std::min(n, kGnTile * (I + 1)); ++q) bf = std::min(bf, al.gf_first[q] / kGnTile);
+    al.gt_bfirst[I] = bf;
+    al.gt_tile_off[I] = (int32_t)std::min<int64_t>(off, INT32_MAX);
+    off += I - bf + 1;
+    for (int K = bf; K < I; ++K) below[K].push_back(I);   // (I ascending)
+  }
+  al.gt_tile_off[nt] = (int32_t)std::min<int64_t>(off, INT32_MAX);
+  al.gt_tiles = off;
+  al.gt_col_ptr.assign(nt + 1, 0);
+  al.gt_col_rows.clear();
+  for (int J = 0; J < nt; ++J) {
+    al.gt_col_ptr[J] = (int32_t)al.gt_col_rows.size();
+    al.gt_col_rows.insert(al.gt_col_rows.end(), below[J].begin(), below[J].end());
+  }
+  al.gt_col_ptr[nt] = (int32_t)al.gt_col_rows.size();
+  al.gt_terms = 0;   // one per row and pair of its columns, the diagonal included
+  for (int i = 0; i < h->L.m; ++i) {
+    const int64_t len = h->L.row_ptr[i + 1] - h->L.row_ptr[i];
+    al.gt_terms += len * (len + 1) / 2;
+  }
+  al.gt_built = true;
+}
+
+// The assembly's terms (layout.h GnAsmTerm), for the upload: per stored entry (q, c), c <= q, the rows of J that hold
+// both columns, ascending, with the two CSR entries — column inv[q]'s first, as the direct kernel multiplies them.
+void gn_tile_assembly(towr_gpu_handle h, std::vector<int32_t>& ptr, std::vector<GnAsmTerm>& terms) {
+  const Layout& L = h->L;
+  const towr_gpu_handle_s::AugLag& al = h->al;
+  auto slot = [&](int q, int c) {
+    const int I = q / kGnTile, K = c / kGnTile;
+    return 256 * (al.gt_tile_off[I] + K - al.gt_bfirst[I]) + kGnTile * (c % kGnTile) + q % kGnTile;
+  };
+  ptr.assign((size_t)(256 * al.gt_tiles + 1), 0);
+  std::vector<int32_t> fill;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int i = 0; i < L.m; ++i)
+      for (int64_t x = L.row_ptr[i]; x < L.row_ptr[i + 1]; ++x)
+        for (int64_t y = L.row_ptr[i]; y < L.row_ptr[i + 1]; ++y) {
+          const int q = al.gf_pos[L.col[x]], c = al.gf_pos[L.col[y]];
+          if (c > q) continue;
+          const int e = slot(q, c);
+          if (pass == 0) ++ptr[e + 1];
+          else terms[fill[e]++] = GnAsmTerm{(int32_t)x, (int32_t)y, i};
+        }
+    if (pass == 0) {
+      for (size_t e = 1; e < ptr.size(); ++e) ptr[e] += ptr[e - 1];
+      fill.assign(ptr.begin(), ptr.end() - 1);
+      terms.resize((size_t)ptr.back());
+    }
+  }
+}
+
+// the tiled kernel: its offsets into a workspace row are 32-bit; its LDS holds per-column state only
+int gn_tiled_fits(towr_gpu_handle h) {
+  gn_tile_tables(h);
+  if (256 * h->al.gt_tiles > INT32_MAX || h->al.gt_terms > INT32_MAX || gn_tiled_lds(h->L.n, h->L.m) + 1024 > kLdsMax)
+    return fail(h, TOWR_ERR_UNSUPPORTED, "problem too large for the tiled GN direction (256 tiles or the assembly's terms >= 2^31, or its LDS)");
+  return TOWR_OK;
+}
+int gn_tiled_ready(towr_gpu_handle h) {
+  if (int rc = products_ready(h)) return rc;
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (al.gnt_ready) return TOWR_OK;
+  if (int rc = gn_tiled_fits(h)) return rc;
+  const size_t lds = gn_tiled_lds(h->L.n, h->L.m);
+  if (lds > 64 * 1024 && hipFuncSetAttribute(gn_tiled_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(h, TOWR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+  std::vector<int32_t> asm_ptr;
+  std::vector<GnAsmTerm> asm_terms;
+  gn_tile_assembly(h, asm_ptr, asm_terms);
+  Uploads u{h};
+  const int32_t* d[7] = {};
+  const GnAsmTerm* dt = nullptr;
+  u.add(&d[0], al.gt_bfirst); u.add(&d[1], al.gt_tile_off); u.add(&d[2], al.gt_col_ptr); u.add(&d[3], al.gt_col_rows);
+  u.add(&d[4], al.gf_pos); u.add(&d[5], al.gf_inv); u.add(&d[6], asm_ptr); u.add(&dt, asm_terms);
+  if (int rc = u.commit()) return rc;
+  for (int i = 0; i < 7; ++i) al.d_gt[i] = const_cast<int32_t*>(d[i]);
+  al.d_gt[7] = const_cast<GnAsmTerm*>(dt);
+  al.gnt_ready = true;
+  return TOWR_OK;
+}
+
 // the residual kernel's tables: the sets' row ranges and, when every set's bounds are known, the description bounds
 int residual_ready(towr_gpu_handle h) {
   towr_gpu_handle_s::AugLag& al = h->al;
@@ -378,7 +475,9 @@ int gn_pc_params(towr_gpu_handle h, int32_t precond, const double* PC, int64_t l
 
 // the direct direction's own arguments: of gn only the damping is read; where its outputs go; the caller's workspace
 // (problem b of a call uses row b mod wrows)
-struct GnWorkspace { double* W; int64_t ldw; int32_t wrows; };
+// (tiled: the tiled direction's row of 256 doubles per stored tile instead of the envelope)
+struct GnWorkspace { double* W; int64_t ldw; int32_t wrows; bool tiled = false; };
+int64_t ws_used(towr_gpu_handle h, const GnWorkspace& ws) { return ws.tiled ? 256 * h->al.gt_tiles : h->al.gf_env; }
 int gn_direct_params(towr_gpu_handle h, const towr_gn_params_t* gn, const double* D, const double* SUM, int64_t lds, const GnWorkspace& ws) {
   if (!gn) return fail(h, TOWR_ERR_INVALID, "null gn params");
   if (!(gn->mu >= 0)) return fail(h, TOWR_ERR_INVALID, "gn: mu is negative or NaN");
@@ -386,14 +485,16 @@ int gn_direct_params(towr_gpu_handle h, const towr_gn_params_t* gn, const double
   if (lds < 8) return fail(h, TOWR_ERR_INVALID, "leading dimension of the GN summary smaller than 8");
   if (!ws.W) return fail(h, TOWR_ERR_INVALID, "gn: null workspace W");
   if (ws.wrows < 1) return fail(h, TOWR_ERR_INVALID, "gn: wrows must be >= 1");
-  gn_factor_tables(h);
-  if (ws.ldw < h->al.gf_env) return fail(h, TOWR_ERR_INVALID, "gn: ldw smaller than ldw_min (towr_gpu_gn_factor_info)");
+  if (ws.tiled) gn_tile_tables(h); else gn_factor_tables(h);
+  if (ws.ldw < ws_used(h, ws))
+    return fail(h, TOWR_ERR_INVALID, ws.tiled ? "gn: ldw smaller than ldw_min (towr_gpu_gn_tile_info)"
+                                              : "gn: ldw smaller than ldw_min (towr_gpu_gn_factor_info)");
   return TOWR_OK;
 }
 // a workspace row in use shares a byte with [q, q + (B - 1) ld + len)
 bool ws_overlap(towr_gpu_handle h, int B, const GnWorkspace& ws, const double* q, int64_t ldq, int64_t lenq) {
   if (!q || B < 1) return false;
-  const double* we = ws.W + (std::min<int64_t>(B, ws.wrows) - 1) * ws.ldw + h->al.gf_env;
+  const double* we = ws.W + (std::min<int64_t>(B, ws.wrows) - 1) * ws.ldw + ws_used(h, ws);
   const double* qe = q + (int64_t)(B - 1) * ldq + lenq;
   return ws.W < qe && q < we;
 }
@@ -534,6 +635,29 @@ int launch_gn_direct(towr_gpu_handle h, int B, GnDirectArgs a, int wrows, hipStr
   return TOWR_OK;
 }
 
+// the tiled direction: launch_gn_direct's launches and rows (after gn_tiled_ready)
+int launch_gn_tiled(towr_gpu_handle h, int B, GnTiledArgs a, int wrows, hipStream_t s) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (a.X && !a.XL) { a.XL = al.d_xlo; a.XU = al.d_xup; a.ldb = 0; }
+  const int32_t* const* t = reinterpret_cast<const int32_t* const*>(al.d_gt);
+  a.bfirst = t[0]; a.tile_off = t[1]; a.tcol_ptr = t[2]; a.tcol_rows = t[3];
+  a.pos = t[4]; a.inv = t[5]; a.asm_ptr = t[6]; a.asm_terms = reinterpret_cast<const GnAsmTerm*>(al.d_gt[7]);
+  a.n = h->L.n; a.m = h->L.m; a.nt = (int32_t)al.gt_bfirst.size(); a.tiles = (int32_t)al.gt_tiles;
+  const size_t lds = gn_tiled_lds(a.n, a.m);
+  const int step = std::min(wrows, B);
+  for (int c0 = 0; c0 < B; c0 += step) {
+    GnTiledArgs g = a;
+    g.V = a.V + (int64_t)c0 * a.ldv; g.LAMP = a.LAMP + (int64_t)c0 * a.ldlp; g.RHO = row_at(a.RHO, c0, 1);
+    g.X = row_at(a.X, c0, a.ldx); g.GR = a.GR + (int64_t)c0 * a.ldgr;
+    g.XL = row_at(a.XL, c0, a.ldb); g.XU = row_at(a.XU, c0, a.ldb);
+    g.RUN = row_at(a.RUN, c0, a.run_stride);
+    g.D = a.D + (int64_t)c0 * a.ldd; g.SUM = a.SUM + (int64_t)c0 * a.lds;
+    void* args[] = {&g};
+    HIPCHK(h, launch_kernel(gn_tiled_kernel(), dim3((unsigned)std::min(step, B - c0)), dim3(kGnBlock), args, lds, s));
+  }
+  return TOWR_OK;
+}
+
 int launch_gn_select(towr_gpu_handle h, int B, const towr_alsolve_state_t& st, const double* DC, hipStream_t s) {
   GnSelectArgs a{st.ISTATE, DC, st.ldx, st.GR, st.ldx, st.D, st.ldx, h->L.n, 0};
   void* args[] = {&a};
@@ -593,10 +717,10 @@ int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> r
 // chunk launches with its rows of them. With gn (the resident GN loop): behind a chunk's product, while its values are
 // still in d_pv, the GN direction at (e.X, z.Out) with that lam+ and rho into the chunk's rows of gn->D / gn->SUM (of gn
 // the bounds, RUN, D, SUM and the CG parameters are used); with gd the direct direction in its place (of gd the bounds,
-// RUN, D, SUM, the workspace and mu).
+// RUN, D, SUM, the workspace and mu); with gt the tiled direct direction, as gd.
 struct EvalStage { const double* X; int64_t ldx; double* G; int64_t ldg; };
 int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r, const JpArgs& z, const Batch& b,
-                  const GnArgs* gn = nullptr, const GnDirectArgs* gd = nullptr, int wrows = 0) {
+                  const GnArgs* gn = nullptr, const GnDirectArgs* gd = nullptr, int wrows = 0, const GnTiledArgs* gt = nullptr) {
   towr_gpu_handle_s::AugLag& al = h->al;
   const int64_t ldv = ld16(h->L.nnz), ldr = ld16(h->L.m);
   const int C = chunk_plan(h, B);
@@ -642,6 +766,19 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
       g.D = gd->D + (int64_t)c0 * gd->ldd;
       g.SUM = gd->SUM + (int64_t)c0 * gd->lds;
       rc = launch_gn_direct(h, cb, g, wrows, b.s);
+    }
+    if (rc == TOWR_OK && gt) {   // (the tiled direction, as gd)
+      GnTiledArgs g = *gt;
+      g.V = al.d_pv; g.ldv = ldv;
+      g.LAMP = a.LAMP; g.ldlp = a.ldlp;
+      g.RHO = a.RHO; g.rho = r.rho;
+      g.X = e.X + (int64_t)c0 * e.ldx; g.ldx = e.ldx;
+      g.GR = z.Out + (int64_t)c0 * z.ldo; g.ldgr = z.ldo;
+      g.XL = row_at(gt->XL, c0, gt->ldb); g.XU = row_at(gt->XU, c0, gt->ldb);
+      g.RUN = row_at(gt->RUN, c0, gt->run_stride);
+      g.D = gt->D + (int64_t)c0 * gt->ldd;
+      g.SUM = gt->SUM + (int64_t)c0 * gt->lds;
+      rc = launch_gn_tiled(h, cb, g, wrows, b.s);
     }
   }
   return rc;
@@ -1069,18 +1206,25 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
   gd.D = DC; gd.ldd = st.ldx; gd.SUM = GSUM; gd.lds = ldgs;
   gd.mu = gn->mu;
   if (ws) { gd.W = ws->W; gd.ldw = ws->ldw; }
+  GnTiledArgs gt{};   // (as gd, for the tiled direction)
+  gt.XL = XL; gt.XU = XU; gt.ldb = ldxb;
+  gt.RUN = st.ISTATE; gt.run_stride = 4;
+  gt.D = DC; gt.ldd = st.ldx; gt.SUM = GSUM; gt.lds = ldgs;
+  gt.mu = gn->mu;
+  if (ws) { gt.W = ws->W; gt.ldw = ws->ldw; }
+  const bool tiled = ws && ws->tiled;
   const StepArgs step{st.X, st.ldx, st.D, st.ldx, st.ALPHA, 0.0, XL, XU, ldxb, st.XC, st.ldx, st.SSUM, st.ldss};
   if (int rc = bind(h)) return rc;
   if (int rc = lbfgs_fits(h)) return rc;
-  if (int rc = ws ? gn_direct_fits(h) : gn_fits(h)) return rc;
+  if (int rc = tiled ? gn_tiled_fits(h) : ws ? gn_direct_fits(h) : gn_fits(h)) return rc;
   if (iters == 0) return TOWR_OK;
-  return fused(h, B, stream, {ws ? gn_direct_ready : gn_ready, residual_ready, step_ready}, [&](const Batch& b) {
+  return fused(h, B, stream, {tiled ? gn_tiled_ready : ws ? gn_direct_ready : gn_ready, residual_ready, step_ready}, [&](const Batch& b) {
     int rc = TOWR_OK;
     for (int it = 0; it < iters && rc == TOWR_OK; ++it) {
       rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
       if (rc == TOWR_OK)
         rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b,
-                           ws ? nullptr : &g, ws ? &gd : nullptr, ws ? ws->wrows : 0);
+                           ws ? nullptr : &g, ws && !tiled ? &gd : nullptr, ws ? ws->wrows : 0, tiled ? &gt : nullptr);
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
       if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
       if (rc == TOWR_OK) rc = launch_gn_select(h, B, st, DC, b.s);
@@ -1154,6 +1298,56 @@ int towr_gpu_alsolve_gn_direct_iterate_batch_device(towr_gpu_handle h, int32_t B
                                                     const double* GL, const double* GU, int64_t ldgb, const double* XL,
                                                     const double* XU, int64_t ldxb, void* stream) {
   const GnWorkspace ws{W, ldw, wrows};
+  return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, false, TOWR_GN_PC_NONE, nullptr, GL, GU, ldgb, XL, XU,
+                            ldxb, stream, &ws);
+}
+
+// ---- the tiled direct Gauss-Newton direction (jprod.hip): block Cholesky on the 16 x 16 tile envelope ---------------------
+int towr_gpu_gn_tile_info(towr_gpu_handle h, int32_t* tile, int32_t* nt, int32_t* bfirst, int64_t* tiles, int64_t* ldw_min) {
+  if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
+  gn_tile_tables(h);
+  const towr_gpu_handle_s::AugLag& al = h->al;
+  if (tile) *tile = TOWR_GN_TILE;
+  if (nt) *nt = (int32_t)al.gt_bfirst.size();
+  if (bfirst && !al.gt_bfirst.empty()) std::memcpy(bfirst, al.gt_bfirst.data(), sizeof(int32_t) * al.gt_bfirst.size());
+  if (tiles) *tiles = al.gt_tiles;
+  if (ldw_min) *ldw_min = 256 * al.gt_tiles;
+  return TOWR_OK;
+}
+
+int towr_gpu_gn_direction_tiled_batch_device(towr_gpu_handle h, int32_t B, const towr_gn_params_t* gn, const double* V,
+                                             int64_t ldv, const double* LAMP, int64_t ldlp, const double* RHO, double rho,
+                                             const double* X, int64_t ldx, const double* GR, int64_t ldgr, const double* XL,
+                                             const double* XU, int64_t ldb, const int32_t* RUN, int32_t run_stride, double* D,
+                                             int64_t ldd, double* SUM, int64_t lds, double* W, int64_t ldw, int32_t wrows,
+                                             void* stream) {
+  if (!h || B < 0 || !V || !LAMP || !GR) return fail(h, TOWR_ERR_INVALID, "bad argument (null V, LAMP or GR, or B < 0)");
+  const GnWorkspace ws{W, ldw, wrows, true};
+  if (int rc = gn_direct_params(h, gn, D, SUM, lds, ws)) return rc;
+  const Layout& L = h->L;
+  if (ws_overlap(h, B, ws, V, ldv, L.nnz) || ws_overlap(h, B, ws, LAMP, ldlp, L.m) || ws_overlap(h, B, ws, X, ldx, L.n) ||
+      ws_overlap(h, B, ws, GR, ldgr, L.n) || ws_overlap(h, B, ws, D, ldd, L.n) || ws_overlap(h, B, ws, SUM, lds, 8))
+    return fail(h, TOWR_ERR_INVALID, "gn: W overlaps V, LAMP, X, GR, D or SUM");
+  if (!RHO && !(rho > 0)) return fail(h, TOWR_ERR_INVALID, "rho must be > 0 without RHO");
+  if (ldv < L.nnz || ldlp < L.m || (X && ldx < L.n) || ldgr < L.n || ldd < L.n)
+    return fail(h, TOWR_ERR_INVALID, "leading dimension smaller than nnz (V) / m (LAMP) / n (X, GR, D)");
+  if (int rc = box_args(h, XL, XU, ldb, L.n, "XL / XU", "n")) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = gn_tiled_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  if (int rc = gn_tiled_ready(h)) return rc;
+  if (X && !XL)
+    if (int rc = step_ready(h)) return rc;
+  GnTiledArgs a{V, ldv, LAMP, ldlp, RHO, rho, X, ldx, GR, ldgr, XL, XU, ldb, RUN, run_stride, D, ldd, SUM, lds, W, ldw, gn->mu};
+  return launch_gn_tiled(h, B, a, wrows, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_alsolve_gn_tiled_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                                   const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC,
+                                                   double* GSUM, int64_t ldgs, double* W, int64_t ldw, int32_t wrows,
+                                                   const double* GL, const double* GU, int64_t ldgb, const double* XL,
+                                                   const double* XU, int64_t ldxb, void* stream) {
+  const GnWorkspace ws{W, ldw, wrows, true};
   return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, false, TOWR_GN_PC_NONE, nullptr, GL, GU, ldgb, XL, XU,
                             ldxb, stream, &ws);
 }

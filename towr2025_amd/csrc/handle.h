@@ -157,6 +157,15 @@ struct towr_gpu_handle_s {
     int32_t gf_width = 0;
     bool gnd_ready = false;
     void* d_gf[7] = {};
+    // The tiled direct direction (towr_gpu_gn_tile_info): the 16 x 16 tile envelope of that ordering, built on the host
+    // by the first call that asks, and the device copies (gn_tiled_ready; after products_ready): bfirst, tile_off,
+    // tcol_ptr, tcol_rows (layout.h GnTiledArgs), pos, inv, and the assembly's terms (gt_terms of them; built for the
+    // upload only)
+    bool gt_built = false;
+    std::vector<int32_t> gt_bfirst, gt_tile_off, gt_col_ptr, gt_col_rows;
+    int64_t gt_tiles = 0, gt_terms = 0;
+    bool gnt_ready = false;
+    void* d_gt[8] = {};
     // Residuals (resid.hip): the device copies of the constraint sets' row ranges and of the description bounds
     // (residual_ready), and the fused entries' g / lam+ scratch (a chunk of problems)
     bool res_ready = false;

@@ -643,7 +643,285 @@ __global__ void __launch_bounds__(kGnBlock) towr_gn_direct_kernel(GnDirectArgs a
   }
 }
 
+// ---- the tiled direct Gauss-Newton direction (towr_gpu_gn_direction_tiled_batch_device) ------------------------------
+// The direct direction's system, held rule and summary, factorised as a block Cholesky on 16 x 16 tiles inside the tile
+// envelope (layout.h GnTiledArgs: the tiles block row by block row in the workspace row, a tile column-major, so that
+// lane l of a wave reads double 64 kk + l of a tile as its operand of the kk-th v_mfma_f64_16x16x4_f64 of a tile product
+// and holds doubles 64 i + l of the result tile in its accumulator: every tile access of a wave is 512 contiguous bytes).
+//   assembly: one lane per stored entry sums the entry's terms — the rows the direct kernel's merge of the two columns'
+//   lists finds, in its order, listed once per handle (GnAsmTerm), so the loads of a sum do not depend on one another;
+//   factorisation, left-looking by block column J, two barriers per block column:
+//     wave 0 forms H_JJ - sum_K L_JK L_JK^T, takes the tile's rows into registers (lane r: row r) and factorises it
+//     unblocked by shuffles, the forward solve of the block's 16 unknowns riding on it (sum_K L_JK y_K is formed on the
+//     operands the tile products load); waves 1 .. 7 form H_IJ - sum_K L_IK L_JK^T for the rows I > J that reach J, a
+//     tile per wave at a time; barrier; the stop decision on a word of LDS every lane reads; one lane per row of the
+//     panel solves it against L_JJ^T (in LDS); barrier;
+//   backward solve, block columns descending: wave 0 solves L_JJ^T d_J = y_J - acc_J by shuffles; barrier; one lane per
+//   column of block row J's tiles adds L_JK^T d_J to acc_K; barrier.
+// The summation order is the header's (towr_gpu_gn_direction_tiled_batch_device); nothing depends on B, the block's
+// place, the stream or timing.
+typedef double gn_v4f64 __attribute__((ext_vector_type(4)));
+
+// acc - A B^T on two tiles' operands of this lane (a: the tile that gives the result's columns, b: its rows)
+__device__ __forceinline__ gn_v4f64 gn_tile_msub(gn_v4f64 acc, const double (&va)[4], const double (&vb)[4]) {
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-va[kk], vb[kk], acc, 0, 0, 0);
+  return acc;
+}
+
+// (4 waves per SIMD asked for: within 128 registers two blocks share a CU)
+__global__ void __launch_bounds__(kGnBlock, 4) towr_gn_tiled_kernel(GnTiledArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double s_part[2][kGnWaves], s_bc[2];
+  __shared__ int s_bad;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x;
+  if (a.RUN && a.RUN[b * a.run_stride] >= 2) return;   // (block-uniform: before any barrier)
+  const int n = a.n, m = a.m, nt = a.nt, np = kGnTile * nt;
+  double* y = jp_lds;            // 16 nt: g~ by permuted position, then y, then d~ (0 in the padding)
+  double* bacc = y + np;         // 16 nt: the backward solve's sum_r L_rq d_r so far
+  double* sL = bacc + np;        // 256: L_JJ, column-major
+  uint8_t* act = reinterpret_cast<uint8_t*>(sL + 256);   // m: the row is active (w = 1)
+  uint8_t* heldq = act + ((m + 15) & ~15);                // 16 nt: 1 held, 0 free, 2 padding
+  const double* Vb = a.V + b * a.ldv;
+  const double* Gb = a.GR + b * a.ldgr;
+  const double* LPb = a.LAMP + b * a.ldlp;
+  double* Db = a.D + b * a.ldd;
+  double* Lb = a.W + b * a.ldw;
+  const double rho = a.RHO ? a.RHO[b] : a.rho;
+  const double mu = a.mu;
+
+  // the held columns (lbfgs.hip's rule) by permuted position, bb = sum_free g^2 (the direct kernel's sums)
+  double v2[2] = {0.0, 0.0};   // bb, the held count (exact)
+  {
+    const double* Xb = a.X ? a.X + b * a.ldx : nullptr;
+    const double* Lo = a.X ? a.XL + b * a.ldb : nullptr;
+    const double* Up = a.X ? a.XU + b * a.ldb : nullptr;
+    for (int j = tid; j < n; j += kGnBlock) {
+      const double g = Gb[j];
+      bool h = false;
+      if (Xb) {
+        const double x = Xb[j], l = Lo[j], u = Up[j];
+        const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+        h = (has_l && x <= l && g > 0.0) || (has_u && x >= u && g < 0.0) || (has_l && has_u && l == u);
+      }
+      const int q = a.pos[j];
+      heldq[q] = h;
+      y[q] = g;
+      bacc[q] = 0.0;
+      if (h) v2[1] += 1.0;
+      else v2[0] += g * g;
+    }
+    for (int q = n + tid; q < np; q += kGnBlock) { heldq[q] = 2; y[q] = 0.0; bacc[q] = 0.0; }
+  }
+  for (int i = tid; i < m; i += kGnBlock) act[i] = LPb[i] != 0.0;   // (a NaN is active)
+  gn_block_sums<2>(v2, s_part, s_bc, tid);   // (its barriers: heldq, act, y and bacc are complete)
+  const double bb = v2[0], nheld = v2[1];
+
+  int code = 1, bcol = -1;
+  double pmin = __builtin_inf(), pmax = 0.0;   // (kept by wave 0, every lane of it on the same bits)
+  if (bb == 0.0) code = 3;
+  else {
+    // assembly: stored entry e is entry (r, c) = (e & 15, (e >> 4) & 15) of stored tile e >> 8
+    {
+      int I = 0;
+      const int total = 256 * a.tiles;
+      for (int e = tid; e < total; e += kGnBlock) {
+        const int t = e >> 8;
+        while (a.tile_off[I + 1] <= t) ++I;
+        const int q = kGnTile * I + (e & 15), c = kGnTile * (a.bfirst[I] + (t - a.tile_off[I])) + ((e >> 4) & 15);
+        double val;
+        if (c > q) val = 0.0;   // (above the diagonal: not read for a result)
+        else if (heldq[q] | heldq[c]) val = q == c ? 1.0 : 0.0;
+        else {
+          const int p0 = a.asm_ptr[e], p1 = a.asm_ptr[e + 1];
+          double acc = 0.0;
+          for (int p = p0; p < p1; ++p) {
+            const GnAsmTerm t = a.asm_terms[p];
+            const double vv = Vb[t.a] * Vb[t.b];
+            acc += (act[t.row] ? 1.0 : 0.0) * vv;
+          }
+          if (q == c) val = rho * acc + mu;
+          else val = p1 > p0 ? rho * acc : 0.0;   // (no shared row: +0.0 as it stands)
+        }
+        Lb[e] = val;
+      }
+    }
+    __syncthreads();
+
+    // factorisation and forward solve, block columns ascending
+    for (int J = 0; J < nt; ++J) {
+      const int bfJ = a.bfirst[J];
+      double* rowJ = Lb + 256 * a.tile_off[J];   // tile (J, K) at rowJ + 256 (K - bfJ)
+      const int cp0 = a.tcol_ptr[J], cnt = a.tcol_ptr[J + 1] - cp0;
+      if (wave == 0) {
+        double* T = rowJ + 256 * (J - bfJ);
+        gn_v4f64 acc;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = T[64 * i + lane];
+        double s = 0.0;   // this lane's share of sum_K L_JK y_K for row lane & 15: the k = 4 kk + (lane >> 4)
+        for (int K = bfJ; K < J; ++K) {
+          const double* A = rowJ + 256 * (K - bfJ);
+          double va[4];
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) va[kk] = A[64 * kk + lane];
+          acc = gn_tile_msub(acc, va, va);
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) s += va[kk] * y[kGnTile * K + 4 * kk + (lane >> 4)];
+        }
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        // row r = lane & 15 of the tile into registers: entry (r, c) is accumulator c >> 2 of lane r + 16 (c & 3)
+        const int r = lane & 15;
+        double row[kGnTile];
+#pragma unroll
+        for (int c = 0; c < kGnTile; ++c) row[c] = __shfl(acc[c >> 2], r + 16 * (c & 3), 64);
+        double t = y[kGnTile * J + r] - s;
+        int badk = -1;
+#pragma unroll
+        for (int k = 0; k < kGnTile; ++k) {
+          __builtin_amdgcn_sched_barrier(0);   // (one step's shuffles at a time: the rows stay in registers)
+          if (badk < 0) {   // (wave-uniform)
+            const double piv = __shfl(row[k], k, 64);
+            if (!(piv > 0.0)) badk = k;   // (a NaN too)
+            else {
+              if (!heldq[kGnTile * J + k]) {
+                if (piv < pmin) pmin = piv;
+                if (piv > pmax) pmax = piv;
+              }
+              const double l = __builtin_sqrt(piv);
+              row[k] = r == k ? l : row[k] / l;
+              const double yk = __shfl(t, k, 64) / l;
+              if (r == k) t = yk;
+              else if (r > k) t -= row[k] * yk;
+#pragma unroll
+              for (int c = k + 1; c < kGnTile; ++c) row[c] -= row[k] * __shfl(row[k], c, 64);
+            }
+          }
+        }
+        if (lane < kGnTile) {
+#pragma unroll
+          for (int c = 0; c < kGnTile; ++c) {
+            const double v = c <= r ? row[c] : 0.0;
+            sL[kGnTile * c + r] = v;
+            T[kGnTile * c + r] = v;
+          }
+          y[kGnTile * J + r] = t;
+        }
+        if (lane == 0) s_bad = badk;
+      } else {
+        for (int i = wave - 1; i < cnt; i += kGnWaves - 1) {
+          const int I = a.tcol_rows[cp0 + i];
+          const int bfI = a.bfirst[I];
+          double* rowI = Lb + 256 * a.tile_off[I];
+          double* T = rowI + 256 * (J - bfI);
+          gn_v4f64 acc;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[k] = T[64 * k + lane];
+          for (int K = bfI > bfJ ? bfI : bfJ; K < J; ++K) {
+            const double* A = rowJ + 256 * (K - bfJ);
+            const double* Bt = rowI + 256 * (K - bfI);
+            double va[4], vb[4];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) { va[kk] = A[64 * kk + lane]; vb[kk] = Bt[64 * kk + lane]; }
+            acc = gn_tile_msub(acc, va, vb);
+          }
+#pragma unroll
+          for (int k = 0; k < 4; ++k) T[64 * k + lane] = acc[k];
+        }
+      }
+      __syncthreads();
+      const int bad = s_bad;   // (block-uniform: written before the barrier, next after the one below)
+      if (bad >= 0) { code = 2; bcol = kGnTile * J + bad; break; }
+      // the panel: row p & 15 of tile p >> 4 of the block column, X L_JJ^T = A by columns ascending
+      for (int p = tid; p < kGnTile * cnt; p += kGnBlock) {
+        const int I = a.tcol_rows[cp0 + (p >> 4)];
+        double* T = Lb + 256 * (a.tile_off[I] + J - a.bfirst[I]) + (p & 15);
+        double x[kGnTile];
+#pragma unroll
+        for (int c = 0; c < kGnTile; ++c) x[c] = T[kGnTile * c];
+#pragma unroll
+        for (int c = 0; c < kGnTile; ++c) {
+          __builtin_amdgcn_sched_barrier(0);   // (one column's reads of L_JJ at a time)
+          double s = x[c];
+#pragma unroll
+          for (int k = 0; k < c; ++k) s -= x[k] * sL[kGnTile * k + c];
+          x[c] = s / sL[(kGnTile + 1) * c];
+        }
+#pragma unroll
+        for (int c = 0; c < kGnTile; ++c) T[kGnTile * c] = x[c];
+      }
+      __syncthreads();
+    }
+
+    // backward solve, block columns descending
+    if (code == 1) {
+      for (int J = nt - 1; J >= 0; --J) {
+        const int bfJ = a.bfirst[J];
+        const double* rowJ = Lb + 256 * a.tile_off[J];
+        if (wave == 0) {
+          const int c = lane & 15;
+          const double* T = rowJ + 256 * (J - bfJ) + kGnTile * c;   // column c of L_JJ
+          double col[kGnTile];
+#pragma unroll
+          for (int k = 0; k < kGnTile; ++k) col[k] = T[k];
+          double t = y[kGnTile * J + c] - bacc[kGnTile * J + c];
+#pragma unroll
+          for (int k = kGnTile - 1; k >= 0; --k) {
+            __builtin_amdgcn_sched_barrier(0);
+            const double dk = __shfl(t, k, 64) / __shfl(col[k], k, 64);
+            if (c == k) t = dk;
+            else if (c < k) t -= col[k] * dk;
+          }
+          if (lane < kGnTile) {
+            const int q = kGnTile * J + c;
+            y[q] = t;
+            if (q < n && !heldq[q]) Db[a.inv[q]] = t;
+          }
+        }
+        __syncthreads();
+        for (int p = tid; p < kGnTile * (J - bfJ); p += kGnBlock) {   // column p & 15 of tile (J, bfJ + (p >> 4))
+          const double* T = rowJ + kGnTile * p;
+          double s = 0.0;
+#pragma unroll
+          for (int r = kGnTile - 1; r >= 0; --r) s += T[r] * y[kGnTile * J + r];
+          bacc[kGnTile * bfJ + p] += s;
+        }
+        __syncthreads();
+      }
+    }
+  }
+
+  // D on the held columns (or everywhere unless solved) and the slope sum g D over all columns
+  double w[1] = {0.0};
+  for (int j = tid; j < n; j += kGnBlock) {
+    const double g = Gb[j];
+    double d = g;
+    if (code == 1 && heldq[a.pos[j]] == 0) d = Db[j];
+    else Db[j] = g;
+    w[0] += g * d;
+  }
+  gn_block_sums<1>(w, s_part, s_bc, tid);
+  if (tid == 0) {
+    double* Sb = a.SUM + b * a.lds;
+    Sb[0] = code == 1 ? 1.0 : 0.0;
+    Sb[1] = bb;
+    Sb[2] = pmin == __builtin_inf() ? 0.0 : pmin;
+    Sb[3] = w[0];
+    Sb[4] = nheld;
+    Sb[5] = (double)code;
+    Sb[6] = pmax;
+    Sb[7] = (double)bcol;
+  }
+}
+
 }  // namespace
+
+size_t gn_tiled_lds(int n, int m) {
+  const size_t np = (size_t)kGnTile * ((n + kGnTile - 1) / kGnTile);
+  return sizeof(double) * (2 * np + 256) + (size_t)((m + 15) & ~15) + np;
+}
+const void* gn_tiled_kernel() { return reinterpret_cast<const void*>(&towr_gn_tiled_kernel); }
 
 size_t gn_direct_lds(int n, int m, int width) {
   return sizeof(double) * (size_t)(4 * ((n + 1) & ~1) + 2 * ((width + 2) & ~1)) + (size_t)((m + 15) & ~15) + (size_t)((n + 15) & ~15);

@@ -512,6 +512,35 @@ struct GnDirectArgs {
 size_t gn_direct_lds(int n, int m, int width);   // dynamic LDS (bytes)
 const void* gn_direct_kernel();
 
+// The tiled direct Gauss-Newton direction (jprod.hip, towr_gpu_gn_direction_tiled_batch_device): the same system, held
+// rule, ordering and summary as the direct direction, factorised as a block Cholesky on kGnTile x kGnTile tiles inside
+// the tile envelope of towr_gpu_gn_tile_info. The workspace row holds the stored tiles block row by block row: tile
+// (I, K), bfirst[I] <= K <= I, at 256 (tile_off[I] + K - bfirst[I]), entry (r, c) of a tile at 16 c + r (column-major).
+// tcol_ptr / tcol_rows list per block column J the block rows I > J whose envelope reaches J, ascending. The assembly is
+// symbolic too: stored entry e (of permuted columns q >= c) sums the terms asm_ptr[e] .. asm_ptr[e + 1] - 1, one per row
+// of J that holds both columns, rows ascending (what the direct kernel's merge finds, found once per handle).
+struct GnAsmTerm { int32_t a, b, row; };   // the CSR entries of column inv[q] and of column inv[c] in that row
+struct GnTiledArgs {
+  const double* V; int64_t ldv;
+  const double* LAMP; int64_t ldlp;
+  const double* RHO; double rho;
+  const double* X; int64_t ldx;
+  const double* GR; int64_t ldgr;
+  const double *XL, *XU; int64_t ldb;
+  const int32_t* RUN; int64_t run_stride;
+  double* D; int64_t ldd;
+  double* SUM; int64_t lds;
+  double* W; int64_t ldw;
+  double mu;
+  const int32_t *pos, *inv;                                  // n each
+  const int32_t *bfirst, *tile_off, *tcol_ptr, *tcol_rows;   // nt, nt + 1, nt + 1, tiles - nt
+  const int32_t* asm_ptr; const GnAsmTerm* asm_terms;        // 256 tiles + 1, asm_ptr[256 tiles]
+  int32_t n, m, nt, tiles;
+};
+constexpr int kGnTile = 16;
+size_t gn_tiled_lds(int n, int m);   // dynamic LDS (bytes)
+const void* gn_tiled_kernel();
+
 // The resident GN loop's select (lbfgs.hip): per problem by the flags the line search wrote, D <- DC (bit 0), else
 // D <- GR (bit 2), else nothing; one block of kLbfgsBlock threads per problem.
 struct GnSelectArgs {

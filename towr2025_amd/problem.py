@@ -812,6 +812,50 @@ class TowrGpuProblem:
             self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
             wp, ldw, wr, gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
 
+    def gn_tile_info(self):
+        """The symbolic phase of the tiled direct Gauss-Newton direction (a layout-only handle answers too): dict(tile
+        (capi.GN_TILE), nt (block rows), bfirst (nt; the first stored tile of block row I under gn_factor_info's
+        ordering), tiles, ldw_min (workspace doubles per problem: 256 per stored tile))."""
+        nt = (self.n + capi.GN_TILE - 1) // capi.GN_TILE
+        bfirst = np.zeros(nt, dtype=np.int32)
+        t, k = C.c_int32(0), C.c_int32(0)
+        tiles, ldw = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.towr_gpu_gn_tile_info(self._h, C.byref(t), C.byref(k), capi.iptr(bfirst), C.byref(tiles),
+                                                    C.byref(ldw)))
+        return dict(tile=t.value, nt=k.value, bfirst=bfirst, tiles=tiles.value, ldw_min=ldw.value)
+
+    def gn_tiled_direction_batch_device(self, gn, V, LAMP, GR, D, SUM, W, wrows=None, rho=1.0, X=None, XL=None, XU=None,
+                                        RUN=None, run_stride=1, stream=None):
+        """gn_direct_direction_batch_device's system, arguments, codes and SUM with the factorisation done as a block
+        Cholesky on 16 x 16 tiles inside gn_tile_info's tile envelope; W rows hold >= its ldw_min doubles. The bits are
+        this entry's own (towr_gpu.h): a function of the problem's operands alone, not the envelope entry's."""
+        B = GR.shape[0]
+        ops = [(V, "V", self.nnz), (LAMP, "LAMP", self.m), (GR, "GR", self.n), (D, "D", self.n), (SUM, "SUM", 8)]
+        if X is not None:
+            ops.append((X, "X", self.n))
+        self._check_rows(B, *ops)
+        xl, xu, ldb = self._var_bounds_operands(B, XL, XU)
+        rp, r, run = self._gn_rho_run(B, rho, RUN, run_stride)
+        wp, ldw, wr = self._gn_workspace(W, wrows, B)
+        self._check(self._lib.towr_gpu_gn_direction_tiled_batch_device(
+            self._h, B, C.byref(gn), *_opt(V), *_opt(LAMP), rp, r, *_opt(X), *_opt(GR), xl, xu, ldb, run, int(run_stride),
+            *_opt(D), *_opt(SUM), wp, ldw, wr, self._stream(stream, GR)))
+
+    def alsolve_gn_tiled_iterate(self, params, st, gn, DC, GSUM, W, wrows=None, iters=1, GL=None, GU=None, XL=None, XU=None,
+                                 stream=None):
+        """alsolve_gn_direct_iterate with the direction of gn_tiled_direction_batch_device (W rows of gn_tile_info's
+        ldw_min; towr_gpu.h)."""
+        c = self._alsolve_state(st, params)
+        self._check_rows(st.B, (DC, "DC", self.n), (GSUM, "GSUM", 8))
+        if DC.stride(0) != st.X.stride(0):
+            raise TowrGpuError("X and DC: they share one leading dimension")
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        wp, ldw, wr = self._gn_workspace(W, wrows, st.B)
+        self._check(self._lib.towr_gpu_alsolve_gn_tiled_iterate_batch_device(
+            self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
+            wp, ldw, wr, gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
+
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
         self._check(self._lib.towr_gpu_set_products_chunk(self._h, int(k)))
