@@ -952,6 +952,117 @@ int towr_gpu_alsolve_gn_tiled_iterate_batch_device(towr_gpu_handle h, int32_t B,
                                                    const double* GL, const double* GU, int64_t ldgb,
                                                    const double* XL, const double* XU, int64_t ldxb, void* stream);
 
+/* ---- a solve to completion: the resident loop in rounds, frozen problems compacted out of the batch ----------------- */
+/* The partition plan of a batch by its phases. ISTATE is int32_t[4*B] as in towr_alsolve_state_t (only the phase word
+ * ISTATE[4 b] is read), HEAD is int32_t[8], PAIRS is int32_t[2*(B/2)]; all DEVICE pointers. Row b is ACTIVE iff its
+ * phase word is 0 (RESTART) or 1 (SEARCH); any other value, negative and out-of-range ones included, is FROZEN.
+ *   HEAD[0] = na, the number of active rows; HEAD[1] = np, the number of pairs; HEAD[2..6] = the number of rows with
+ *   phase 0, 1, 2, 3, 4; HEAD[7] = the number of rows with any other value.
+ *   Pair i is (PAIRS[2 i], PAIRS[2 i + 1]) = (f_i, a_i): f_i the i-th frozen row of [0, na), a_i the i-th active row of
+ *   [na, B), both ascending. There are equally many of both; np is that number (np <= B / 2).
+ * After the rows of every pair have been exchanged, rows [0, na) are all active, rows [na, B) all frozen, and a row that
+ * was on its side already has not moved. Nothing of PAIRS beyond 2 np ints is written. One block, integer counts in a
+ * fixed order: the outputs are a function of the phase words. B = 0 writes HEAD = 0. No handle scratch; the kept
+ * Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for a NULL pointer or B < 0.                          */
+int towr_gpu_alsolve_partition_batch_device(towr_gpu_handle h, int32_t B, const int32_t* ISTATE, int32_t* HEAD,
+                                            int32_t* PAIRS, void* stream);
+
+/* The rows of an array: row r is bytes [r*ld_bytes, r*ld_bytes + row_bytes) from base (DEVICE memory). */
+typedef struct { void* base; int64_t ld_bytes; int64_t row_bytes; } towr_rows_t;
+#define TOWR_SWAP_MAX_ARRAYS 32
+
+/* Exchanges rows in place: for every pair i < count and every array k < n_arrays, bytes [0, row_bytes) of rows
+ * PAIRS[2 i] and PAIRS[2 i + 1] of array k. Not one byte beyond row_bytes of any row is read or written: the padding up
+ * to ld_bytes stays exactly as it was. `arrays` is HOST memory, read at the call; PAIRS (and NP) are DEVICE pointers.
+ *   NP != NULL: count = min(NP[0], max_pairs), read on the device (NP is typically the partition's HEAD + 1, so no host
+ *   round trip lies between the two calls); the grid holds max_pairs pairs and the blocks beyond count exit; npairs is
+ *   not read. NP == NULL: count = npairs, a host value; max_pairs is not read.
+ * The pairs must be disjoint (no row in two of them) and index rows every array holds, as the partition's are; a pair
+ * with a negative index or two equal ones is skipped. A list of disjoint pairs is an involution: the same call again
+ * undoes it. row_bytes is a positive multiple of 4, base and ld_bytes are multiples of 4 and ld_bytes >= row_bytes; 8
+ * bytes move per lane where base, ld_bytes and row_bytes are all multiples of 8, else 4. Both rows are read before
+ * either is written. No handle scratch; the kept Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for:
+ * NULL PAIRS, NULL arrays with n_arrays > 0, npairs < 0 (NP NULL) or max_pairs < 0 (NP given), n_arrays outside
+ * 0..TOWR_SWAP_MAX_ARRAYS, a descriptor with a NULL or misaligned base, ld_bytes or row_bytes not a positive multiple of
+ * 4, ld_bytes < row_bytes, and two descriptors whose rows 0 share a byte (with equal ld_bytes that is every row of both:
+ * one array passed twice, or two views of the same columns; rows of different index cannot be told apart without a row
+ * count and are the caller's business).                                                                              */
+int towr_gpu_alsolve_swap_rows_batch_device(towr_gpu_handle h, const int32_t* NP, int32_t npairs, int32_t max_pairs,
+                                            const int32_t* PAIRS, int32_t n_arrays, const towr_rows_t* arrays,
+                                            void* stream);
+
+/* The solve driver's options (host memory, read at the call): the iterate entry that runs the iterations, the most
+ * iterations (>= 0), the iterations per round K (>= 1; the host looks at the batch once per round), and whether frozen
+ * problems are compacted out of the batch (0 or 1).                                                                  */
+#define TOWR_SOLVE_LBFGS 0      /* towr_gpu_alsolve_iterate_batch_device           */
+#define TOWR_SOLVE_GN 1         /* towr_gpu_alsolve_gn_iterate_batch_device        */
+#define TOWR_SOLVE_GN_PC 2      /* towr_gpu_alsolve_gn_pc_iterate_batch_device     */
+#define TOWR_SOLVE_GN_DIRECT 3  /* towr_gpu_alsolve_gn_direct_iterate_batch_device */
+#define TOWR_SOLVE_GN_TILED 4   /* towr_gpu_alsolve_gn_tiled_iterate_batch_device  */
+typedef struct { int32_t method, max_iters, check_every, compact; } towr_solve_opts_t;
+/* What the method's iterate entry takes beside `state` (host memory; the pointers in it are DEVICE pointers): gn,
+ * precond and PC (GN_PC), DC, GSUM, ldgs (every GN method), W, ldw, wrows (GN_DIRECT, GN_TILED). Fields the method does
+ * not read may be NULL or 0.                                                                                         */
+typedef struct {
+  const towr_gn_params_t* gn;
+  int32_t precond, wrows;
+  double *DC, *GSUM; int64_t ldgs;
+  double* PC;
+  double* W; int64_t ldw;
+} towr_solve_dir_t;
+/* Written at return (host memory): the rounds run, the iterations run (the same for every problem still in the batch),
+ * the sum over the rounds of (rows in the round's batch) x (iterations of the round), and HEAD[2..7] of a final
+ * partition over all B rows: the number of problems in phase 0, 1, 2, 3, 4 and with any other phase word.             */
+typedef struct { int32_t rounds, iters_run; int64_t problem_iters; int32_t n_phase[6]; int32_t reserved[2]; } towr_solve_report_t;
+
+/* Runs the resident loop until every problem is frozen or max_iters iterations have run. The caller has run
+ * towr_gpu_alsolve_init_batch_device (or holds a state that an iterate entry left); this entry does not. With Bcur = B,
+ * rounds run while iters_run < max_iters and Bcur > 0. One round, all on `stream`:
+ *   1. k = min(check_every, max_iters - iters_run) iterations of the method's iterate entry on rows [0, Bcur), its own
+ *      launches and checks;
+ *   2. towr_gpu_alsolve_partition_batch_device over rows [0, Bcur): HEAD = LOG[0..7], the pairs behind those of the
+ *      rounds before (LOG + 8 + 2 * the pairs so far);
+ *   3. with compact = 1, towr_gpu_alsolve_swap_rows_batch_device with NP = LOG + 1 on every per-problem array (below);
+ *   4. a copy of HEAD to page-locked host memory and ONE synchronisation of the stream;
+ *   5. the host reads na and np: it stops when na == 0, and with compact = 1 sets Bcur = na.
+ * With compact = 0, Bcur stays B and no swap is queued: the same rounds on the whole batch. When the loop has ended, the
+ * swaps of all rounds are run again in reverse order (host counts, NP = NULL), which puts every array back in the
+ * caller's order; then a final partition over all B rows fills `report`, and a last synchronisation. THE ENTRY BLOCKS
+ * THE HOST: one synchronisation per round and one before it returns; on return all its work on `stream` has finished.
+ * LOG is caller-owned DEVICE memory, int32_t[8 + 2 B]: a frozen row moves at most once (out of the front into the tail
+ * of its round, which no later round touches), so the pairs of all rounds number at most B. Its contents after the call
+ * are the final partition's HEAD and unspecified pairs.
+ *   Arrays exchanged (with the used widths stated for each): every per-problem row of `state` — X, GR, XC, GRC, D (n),
+ *   LAM, LAMP (m), HS, HY (a problem's `mem` pairs as one row: (mem - 1) ldh + n doubles at mem ldh, so the padding
+ *   between a problem's pairs travels with it), HMETA (2 ints), ALPHA, RHO, FC (1), SCAL (8), ISTATE (4 ints), RSUM
+ *   (4 + n_constraints), SSUM (5 + n_varsets), DSUM (5), USUM (6), LSUM (8); DC (n, at ldx) and GSUM (6; 8 for GN_PC,
+ *   GN_DIRECT and GN_TILED) for the GN methods; GL / GU (m) and XL / XU (n) when their leading dimension is > 0 — they
+ *   are per-problem rows then, are PERMUTED DURING THE CALL AND BACK IN THE CALLER'S ORDER AT RETURN, and are therefore
+ *   not const here; a leading dimension of 0 (one shared row) and NULL (the handle's bounds) are not touched. When batch
+ *   terrains are set (towr_gpu_set_batch_terrain; exactly B of them), the driver permutes a private device copy and
+ *   hands that to the launches: the handle's set is not modified. W and PC are not exchanged; their contents after the
+ *   call are unspecified.
+ *   Persistent arrays: X, GR, LAM, RHO, SCAL, ISTATE, HS, HY, HMETA, D, ALPHA — those the iterate entries never change
+ *   again once a problem is frozen — are at return, for every problem, bit for bit what the method's iterate entry
+ *   leaves after iters_run iterations on the whole batch; for compact = 0 and 1 alike, for any check_every that gives the
+ *   same iters_run, any products chunk, any wrows (problem b's outputs are a function of its own operands alone, so its
+ *   place in the batch does not matter).
+ *   Candidate-side and summary rows: XC, GRC, FC, LAMP, RSUM, SSUM, DSUM, USUM, LSUM, DC, GSUM are the iterate entry's
+ *   bits for the problems active to the end (and for every problem with compact = 0); for a problem frozen before the
+ *   last round they are those of the last iteration in which it was part of the batch.
+ *   Failure: if a launch or copy fails after the first swap, the recorded swaps are still run in reverse and the first
+ *   error is returned; if that fails too, the row order is unspecified and towr_gpu_last_error says so.
+ * Handle scratch, the cross-stream rule and the kept Jacobian as for the iterate entry. TOWR_ERR_INVALID before anything
+ * runs for: NULL opts, dir, LOG or report, a method outside 0..4, max_iters < 0, check_every < 1, compact outside
+ * {0, 1}, everything the method's iterate entry refuses for these arguments, an array above that fails the swap's
+ * checks, and batch terrains set for another number of problems than B. TOWR_ERR_UNSUPPORTED and TOWR_ERR_NO_DEVICE as
+ * for that iterate entry.                                                                                            */
+int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                        const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                        const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb,
+                                        double* XL, double* XU, int64_t ldxb, int32_t* LOG, towr_solve_report_t* report,
+                                        void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

@@ -1,0 +1,133 @@
+"""Solve-to-completion timings on the GPU box (tool, not product): towr_gpu_alsolve_solve_batch_device with and without
+compaction, beside the hand-written iterate-and-poll loop it replaces, on one box in one session.
+
+ANYmal trot (anymal_trot_2p4s, B default 1024) or the procedural monoped of the short-solve tests (B_MONOPED default
+4096, whose starts freeze after 9 .. 100+ iterations), from the starts x0 + 0.05 randn(SEED + b), TOWR_SOLVE_GN_TILED with
+wrows = B, SOLVE_PAR of the short-solve tests, damping MU (default 1e-6), at most MAX_ITERS iterations (default 120).
+Per check_every K in KS (default 4,16), alternated within every round:
+  (n) alsolve_solve(compact = 0);
+  (c) alsolve_solve(compact = 1);
+  (h) the hand loop: alsolve_gn_tiled_iterate(iters = K) through the C-ABI, the phase words copied to the host, repeated
+      until no problem is active or MAX_ITERS is reached — what a caller wrote before the driver existed;
+and on a batch of B copies of start 0, where every problem freezes in the same round and compaction has nothing to gain:
+  (n1), (c1) as (n), (c).
+A solve is timed by the host clock from a synchronised device to the return of the call (the driver synchronises before
+it returns; the hand loop ends in a copy to the host); the state is restored and alsolve_init run before every solve,
+outside the window. Printed: the median and the spread over ROUNDS per variant, iters_run, problem_iters, the phase counts,
+the ratio of times beside the ratio of problem_iters, and whether compact = 1 and compact = 0 left the same bits in X.
+usage: python tools/solve_timing.py [anymal|monoped|all]"""
+import ctypes as C
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from towr2025_amd import AlSolveState, TowrGpuProblem, _capi as capi, alsolve_params, gn_params  # noqa: E402
+from towr2025_amd import formulation as F  # noqa: E402
+
+ROUNDS = int(os.environ.get("ROUNDS", "3"))
+MAX_ITERS = int(os.environ.get("MAX_ITERS", "120"))
+KS = [int(k) for k in os.environ.get("KS", "4,16").split(",")]
+MU = float(os.environ.get("MU", "1e-6"))
+SEED = int(os.environ.get("SEED", "900"))
+SOLVE_PAR = dict(mem=8, shrink=0.1, rho0=10.0, curv_eps=1e-14, max_inner=200, alpha_min=1e-16)
+
+
+def run(title, p, B):
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    n, mem = p.n, SOLVE_PAR["mem"]
+    par, gn = alsolve_params(**SOLVE_PAR), gn_params(mu=MU)
+    x0 = p.initial_x()
+    starts = np.stack([x0 + 0.05 * np.random.default_rng(SEED + b).standard_normal(n) for b in range(B)])
+    X0 = {"spread": torch.from_numpy(starts).to(dev), "same": torch.from_numpy(np.repeat(starts[:1], B, axis=0)).to(dev)}
+    st = AlSolveState.allocate(p, B, mem)
+    DC, GS = torch.zeros_like(st.X), torch.zeros((B, 8), dtype=torch.float64, device=dev)
+    W = torch.empty((B, p.gn_tile_info()["ldw_min"]), dtype=torch.float64, device=dev)
+    LOG = torch.zeros(8 + 2 * B, dtype=torch.int32, device=dev)
+    sp = C.c_void_p(stream.cuda_stream)
+    c = p._alsolve_state(st, par)
+
+    def restart(which):
+        st.X.copy_(X0[which])
+        st.LAM.zero_()
+        p.alsolve_init(par, st, stream=stream)
+        torch.cuda.synchronize()
+
+    def driver(K, compact):
+        return p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=MAX_ITERS,
+                               check_every=K, compact=compact, LOG=LOG, stream=stream)
+
+    def hand(K):
+        phases = st.ISTATE.view(B, 4)[:, 0]
+        done, rounds = 0, 0
+        while done < MAX_ITERS:
+            k = min(K, MAX_ITERS - done)
+            p._check(p._lib.towr_gpu_alsolve_gn_tiled_iterate_batch_device(
+                p._h, B, k, C.byref(par), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), C.c_void_p(GS.data_ptr()), GS.stride(0),
+                C.c_void_p(W.data_ptr()), W.stride(0), B, None, None, 0, None, None, 0, sp))
+            done, rounds = done + k, rounds + 1
+            ph = phases.cpu()
+            if not ((ph == 0) | (ph == 1)).any():
+                break
+        counts = [int((ph == v).sum()) for v in range(5)]
+        return dict(rounds=rounds, iters_run=done, problem_iters=B * done, n_phase=counts + [B - sum(counts)])
+
+    variants = []
+    for K in KS:
+        variants += [(f"n  K={K:<2d} compact=0", "spread", lambda K=K: driver(K, False)),
+                     (f"c  K={K:<2d} compact=1", "spread", lambda K=K: driver(K, True)),
+                     (f"h  K={K:<2d} hand loop", "spread", lambda K=K: hand(K))]
+    variants += [(f"n1 K={KS[0]:<2d} compact=0, one start", "same", lambda: driver(KS[0], False)),
+                 (f"c1 K={KS[0]:<2d} compact=1, one start", "same", lambda: driver(KS[0], True))]
+    # warm-up: every variant once (the tables' upload, the scratch, the page-locked HEAD); the bits of X kept per variant
+    bits, reports = {}, {}
+    for name, which, fn in variants:
+        restart(which)
+        reports[name] = fn()
+        torch.cuda.synchronize()
+        bits[name] = st.X.clone()
+    times = {name: [] for name, _, _ in variants}
+    for _ in range(ROUNDS):
+        for name, which, fn in variants:
+            restart(which)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append(1e3 * (time.perf_counter() - t0))
+    codes = torch.bincount(GS[:, 5].to(torch.int64).clamp(0, 3), minlength=4).tolist()
+    print(f"{title}: B={B} n={p.n} m={p.m} nnz={p.nnz} mu={MU} max_iters={MAX_ITERS} rounds={ROUNDS}; direction codes 0..3 of "
+          f"the last solve {codes}", flush=True)
+    med = {}
+    for name, _, _ in variants:
+        t, r = times[name], reports[name]
+        med[name] = statistics.median(t)
+        print(f"  {name:32s} {med[name]:9.2f} ms  (min {min(t):.2f} max {max(t):.2f})  rounds {r['rounds']} iters_run {r['iters_run']} "
+              f"problem_iters {r['problem_iters']} phases 0..4,other {r['n_phase']}", flush=True)
+    for K in KS:
+        nn, cc, hh = (f"{v}  K={K:<2d} {w}" for v, w in (("n", "compact=0"), ("c", "compact=1"), ("h", "hand loop")))
+        print(f"  K={K}: time c / n {med[cc] / med[nn]:.3f} vs problem_iters c / n "
+              f"{reports[cc]['problem_iters'] / max(reports[nn]['problem_iters'], 1):.3f}; driver n / hand loop {med[nn] / med[hh]:.3f}; "
+              f"X bit-equal c vs n: {torch.equal(bits[cc].view(torch.int64), bits[nn].view(torch.int64))}, n vs hand: "
+              f"{torch.equal(bits[nn].view(torch.int64), bits[hh].view(torch.int64))}", flush=True)
+    n1, c1 = variants[-2][0], variants[-1][0]
+    print(f"  one start: time c1 / n1 {med[c1] / med[n1]:.3f}; X bit-equal: "
+          f"{torch.equal(bits[c1].view(torch.int64), bits[n1].view(torch.int64))}", flush=True)
+
+
+if __name__ == "__main__":
+    which = sys.argv[1] if len(sys.argv) > 1 else "anymal"
+    if which in ("anymal", "all"):
+        f = F.anymal_trot()
+        f.params_.enable_stance_tracking = False
+        run("anymal_trot", TowrGpuProblem(f.to_desc(), device=0, data=f.var_bounds_data()), int(os.environ.get("B", "1024")))
+    if which in ("monoped", "all"):
+        f, vs, cs, goal, T = F.procedural_monoped()
+        vb = f.var_bounds_data(varsets=vs, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)
+        run("monoped_procedural", TowrGpuProblem(F.procedural_desc(), device=0, data=vb), int(os.environ.get("B_MONOPED", "4096")))

@@ -105,6 +105,29 @@ class GnParams(C.Structure):   # towr_gn_params_t
     _fields_ = [("ncg", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double), ("tol", C.c_double)]
 
 
+SOLVE_LBFGS, SOLVE_GN, SOLVE_GN_PC, SOLVE_GN_DIRECT, SOLVE_GN_TILED = 0, 1, 2, 3, 4   # TOWR_SOLVE_*: the solve's method
+SWAP_MAX_ARRAYS = 32   # TOWR_SWAP_MAX_ARRAYS
+
+
+class Rows(C.Structure):   # towr_rows_t
+    _fields_ = [("base", C.c_void_p), ("ld_bytes", C.c_int64), ("row_bytes", C.c_int64)]
+
+
+class SolveOpts(C.Structure):   # towr_solve_opts_t
+    _fields_ = [("method", C.c_int32), ("max_iters", C.c_int32), ("check_every", C.c_int32), ("compact", C.c_int32)]
+
+
+class SolveDir(C.Structure):   # towr_solve_dir_t
+    _fields_ = [("gn", C.POINTER(GnParams)), ("precond", C.c_int32), ("wrows", C.c_int32),
+                ("DC", C.c_void_p), ("GSUM", C.c_void_p), ("ldgs", C.c_int64), ("PC", C.c_void_p),
+                ("W", C.c_void_p), ("ldw", C.c_int64)]
+
+
+class SolveReport(C.Structure):   # towr_solve_report_t
+    _fields_ = [("rounds", C.c_int32), ("iters_run", C.c_int32), ("problem_iters", C.c_int64),
+                ("n_phase", C.c_int32 * 6), ("reserved", C.c_int32 * 2)]
+
+
 class CostDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("ee", C.c_int32), ("weight", C.c_double), ("dt", C.c_double),
                 ("p", C.c_double * 4), ("ip", C.c_int32 * 4)]
@@ -268,6 +291,13 @@ SYMBOLS = {
                                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                                                   C.c_void_p, C.c_void_p, C.c_int64,
                                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_alsolve_partition_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "towr_gpu_alsolve_swap_rows_batch_device": (C.c_int, [_HANDLE, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                           C.POINTER(Rows), C.c_void_p]),
+    "towr_gpu_alsolve_solve_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(SolveOpts), C.POINTER(AlSolveParams),
+                                                       C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
+                                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                       C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

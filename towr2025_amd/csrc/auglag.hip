@@ -2,7 +2,8 @@
 // augmented-Lagrangian loop calls between evaluations: Jacobian products (J p, J^T lam), constraint residuals and
 // multiplier updates, the projected step, the L-BFGS history and direction, the Gauss-Newton direction (CG, or direct
 // with its ordering and envelope found here on the host), and the
-// fused sequences of these behind an evaluation. Host code only: the kernels live in jprod.hip, resid.hip, step.hip and lbfgs.hip, their argument
+// fused sequences of these behind an evaluation, and the solve driver that runs those sequences in rounds and compacts the
+// frozen problems out of the batch between them. Host code only: the kernels live in jprod.hip, resid.hip, step.hip and lbfgs.hip, their argument
 // structs in layout.h. The evaluator (towr_gpu.hip) is used through handle.h alone: launch, launch_cost,
 // batch_terrain, bind and the scratch helpers.
 //
@@ -29,6 +30,7 @@ void towr_gpu_handle_s::AugLag::release() {
   for (void* p : d_gt) if (p) (void)hipFree(p);
   void* rest[] = {d_pv, d_set_row0, d_blo, d_bup, d_rg, d_rl, d_set_col0, d_xlo, d_xup, d_sd, d_sf};
   for (void* p : rest) if (p) (void)hipFree(p);
+  if (h_head) (void)hipHostFree(h_head);
 }
 
 namespace {
@@ -696,10 +698,13 @@ struct Batch {
 // released on every path behind that (also after a failure: what was queued still orders the scratch); the first code
 // that is not TOWR_OK is the answer. A call that needs no table uses none of this file's scratch: its body runs as it is.
 using Ready = int (*)(towr_gpu_handle);
+// `ter` (the solve driver): the per-problem terrains of this call's rows in the handle's place.
 template <class Body>
-int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> ready, Body body) {
-  Batch b{reinterpret_cast<hipStream_t>(stream), nullptr, 0};
-  if (int rc = batch_terrain(h, B, false, &b.ter, &b.per)) return rc;
+int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> ready, Body body,
+          const towr_terrain_t* ter = nullptr) {
+  Batch b{reinterpret_cast<hipStream_t>(stream), ter, ter ? 1 : 0};
+  if (!ter)
+    if (int rc = batch_terrain(h, B, false, &b.ter, &b.per)) return rc;
   if (B == 0) return TOWR_OK;
   if (ready.size() == 0) return body(b);
   for (Ready r : ready)
@@ -1081,9 +1086,11 @@ int towr_gpu_alsolve_init_batch_device(towr_gpu_handle h, int32_t B, const towr_
 // Per iteration what the six public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag
 // chunks with the per-problem RHO accumulated onto GRC (g in handle scratch), the line search, the outer update, the
 // direction of the problems whose flag bit 1 is set (RUN = the flags) and the step.
-int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
-                                          const towr_alsolve_state_t* state, const double* GL, const double* GU, int64_t ldgb,
-                                          const double* XL, const double* XU, int64_t ldxb, void* stream) {
+// (ter: fused()'s, the solve driver's permuted terrains)
+static int alsolve_lbfgs_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                 const towr_alsolve_state_t* state, const double* GL, const double* GU, int64_t ldgb,
+                                 const double* XL, const double* XU, int64_t ldxb, void* stream,
+                                 const towr_terrain_t* ter = nullptr) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   const towr_alsolve_state_t& st = *state;
@@ -1110,7 +1117,13 @@ int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t 
       if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
     }
     return rc;
-  });
+  }, ter);
+}
+
+int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
+                                          const towr_alsolve_state_t* state, const double* GL, const double* GU, int64_t ldgb,
+                                          const double* XL, const double* XU, int64_t ldxb, void* stream) {
+  return alsolve_lbfgs_iterate(h, B, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream);
 }
 
 // ---- the Gauss-Newton direction (jprod.hip) and the resident loop that uses it ------------------------------------------
@@ -1172,7 +1185,8 @@ int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const to
 static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                               const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC, double* GSUM,
                               int64_t ldgs, bool pc, int32_t precond, double* PC, const double* GL, const double* GU, int64_t ldgb,
-                              const double* XL, const double* XU, int64_t ldxb, void* stream, const GnWorkspace* ws = nullptr) {
+                              const double* XL, const double* XU, int64_t ldxb, void* stream, const GnWorkspace* ws = nullptr,
+                              const towr_terrain_t* ter = nullptr) {   // (ter: fused()'s)
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   if (int rc = ws ? gn_direct_params(h, gn, DC, GSUM, ldgs, *ws) : gn_params(h, gn, DC, GSUM, ldgs)) return rc;
@@ -1231,7 +1245,7 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
       if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
     }
     return rc;
-  });
+  }, ter);
 }
 
 int towr_gpu_alsolve_gn_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
@@ -1350,6 +1364,182 @@ int towr_gpu_alsolve_gn_tiled_iterate_batch_device(towr_gpu_handle h, int32_t B,
   const GnWorkspace ws{W, ldw, wrows, true};
   return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, false, TOWR_GN_PC_NONE, nullptr, GL, GU, ldgb, XL, XU,
                             ldxb, stream, &ws);
+}
+
+// ---- a solve to completion: rounds of the resident loop, frozen problems compacted out (lbfgs.hip) ---------------------
+// what the swap refuses of its descriptors
+static int swap_rows_args(towr_gpu_handle h, int32_t n_arrays, const towr_rows_t* arrays) {
+  if (n_arrays < 0 || n_arrays > TOWR_SWAP_MAX_ARRAYS) return fail(h, TOWR_ERR_INVALID, "swap: n_arrays outside 0..TOWR_SWAP_MAX_ARRAYS");
+  if (n_arrays > 0 && !arrays) return fail(h, TOWR_ERR_INVALID, "swap: null arrays");
+  for (int k = 0; k < n_arrays; ++k) {
+    const towr_rows_t& r = arrays[k];
+    if (!r.base || (reinterpret_cast<uintptr_t>(r.base) & 3)) return fail(h, TOWR_ERR_INVALID, "swap: array " + std::to_string(k) + ": base is NULL or not a multiple of 4");
+    if (r.row_bytes <= 0 || (r.row_bytes & 3)) return fail(h, TOWR_ERR_INVALID, "swap: array " + std::to_string(k) + ": row_bytes is not a positive multiple of 4");
+    if (r.ld_bytes <= 0 || (r.ld_bytes & 3)) return fail(h, TOWR_ERR_INVALID, "swap: array " + std::to_string(k) + ": ld_bytes is not a positive multiple of 4");
+    if (r.ld_bytes < r.row_bytes) return fail(h, TOWR_ERR_INVALID, "swap: array " + std::to_string(k) + ": ld_bytes smaller than row_bytes");
+    for (int j = 0; j < k; ++j) {
+      const char *p = static_cast<const char*>(arrays[j].base), *q = static_cast<const char*>(r.base);
+      if (p < q + r.row_bytes && q < p + arrays[j].row_bytes)
+        return fail(h, TOWR_ERR_INVALID, "swap: arrays " + std::to_string(j) + " and " + std::to_string(k) + " overlap");
+    }
+  }
+  return TOWR_OK;
+}
+
+static int launch_partition(towr_gpu_handle h, int B, const int32_t* ISTATE, int32_t* HEAD, int32_t* PAIRS, hipStream_t s) {
+  PartitionArgs a{ISTATE, HEAD, PAIRS, B, 0};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_partition_kernel(), dim3(1), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+// (NP NULL: `pairs` is the count; else the grid's pairs. After swap_rows_args.)
+static int launch_swap_rows(towr_gpu_handle h, const int32_t* NP, int pairs, const int32_t* PAIRS, int n_arrays,
+                            const towr_rows_t* arrays, hipStream_t s) {
+  if (pairs == 0 || n_arrays == 0) return TOWR_OK;
+  SwapRowsArgs a{};
+  a.NP = NP; a.PAIRS = PAIRS; a.npairs = pairs; a.n_arrays = n_arrays;
+  for (int k = 0; k < n_arrays; ++k) a.rows[k] = SwapRows{static_cast<char*>(arrays[k].base), arrays[k].ld_bytes, arrays[k].row_bytes};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_swap_rows_kernel(), dim3((unsigned)pairs, (unsigned)n_arrays), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+int towr_gpu_alsolve_partition_batch_device(towr_gpu_handle h, int32_t B, const int32_t* ISTATE, int32_t* HEAD, int32_t* PAIRS,
+                                            void* stream) {
+  if (!h || B < 0 || !ISTATE || !HEAD || !PAIRS) return fail(h, TOWR_ERR_INVALID, "bad argument (null ISTATE, HEAD or PAIRS, or B < 0)");
+  if (int rc = bind(h)) return rc;
+  return launch_partition(h, B, ISTATE, HEAD, PAIRS, reinterpret_cast<hipStream_t>(stream));   // (B = 0: HEAD = 0)
+}
+
+int towr_gpu_alsolve_swap_rows_batch_device(towr_gpu_handle h, const int32_t* NP, int32_t npairs, int32_t max_pairs,
+                                            const int32_t* PAIRS, int32_t n_arrays, const towr_rows_t* arrays, void* stream) {
+  if (!h || !PAIRS) return fail(h, TOWR_ERR_INVALID, "bad argument (null PAIRS)");
+  if (NP ? max_pairs < 0 : npairs < 0) return fail(h, TOWR_ERR_INVALID, "swap: negative pair count (npairs without NP, max_pairs with it)");
+  if (int rc = swap_rows_args(h, n_arrays, arrays)) return rc;
+  if (int rc = bind(h)) return rc;
+  return launch_swap_rows(h, NP, NP ? max_pairs : npairs, PAIRS, n_arrays, arrays, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                        const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                        const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb, double* XL, double* XU,
+                                        int64_t ldxb, int32_t* LOG, towr_solve_report_t* report, void* stream) {
+  if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
+  if (!opts || !dir || !LOG || !report) return fail(h, TOWR_ERR_INVALID, "solve: null opts, dir, LOG or report");
+  if (opts->method < TOWR_SOLVE_LBFGS || opts->method > TOWR_SOLVE_GN_TILED) return fail(h, TOWR_ERR_INVALID, "solve: method outside 0..4");
+  if (opts->max_iters < 0) return fail(h, TOWR_ERR_INVALID, "solve: max_iters is negative");
+  if (opts->check_every < 1) return fail(h, TOWR_ERR_INVALID, "solve: check_every must be >= 1");
+  if (opts->compact != 0 && opts->compact != 1) return fail(h, TOWR_ERR_INVALID, "solve: compact outside {0, 1}");
+  const int method = opts->method;
+  const bool gn = method != TOWR_SOLVE_LBFGS, compact = opts->compact == 1;
+  const GnWorkspace ws{dir->W, dir->ldw, dir->wrows, method == TOWR_SOLVE_GN_TILED};
+  // `iters` iterations of the method's iterate entry on rows [0, Bc): its own checks and launches (iters = 0: the checks)
+  auto iterate = [&](int Bc, int iters, const towr_terrain_t* ter) -> int {
+    if (!gn) return alsolve_lbfgs_iterate(h, Bc, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream, ter);
+    const bool pc = method == TOWR_SOLVE_GN_PC;
+    return alsolve_gn_iterate(h, Bc, iters, params, state, dir->gn, dir->DC, dir->GSUM, dir->ldgs, pc,
+                              pc ? dir->precond : (int32_t)TOWR_GN_PC_NONE, pc ? dir->PC : nullptr, GL, GU, ldgb, XL, XU, ldxb, stream,
+                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter);
+  };
+  // the iterate entry's refusals, TOWR_ERR_NO_DEVICE and TOWR_ERR_UNSUPPORTED (it binds the handle); nothing is queued.
+  // Its argument checks come first: with another code they have passed, and this entry's own follow before that code
+  const int pre = iterate(B, 0, nullptr);
+  if (pre == TOWR_ERR_INVALID) return pre;
+  if (h->d_bterrain && h->bterrain_n != B)
+    return fail(h, TOWR_ERR_INVALID, "batch terrains are set for " + std::to_string(h->bterrain_n) + " problems, the call has " +
+                                         std::to_string(B));
+  // the per-problem arrays (towr_gpu.h): what a round's swap exchanges
+  const Layout& L = h->L;
+  const towr_alsolve_state_t& st = *state;
+  towr_rows_t rows[TOWR_SWAP_MAX_ARRAYS];
+  int nr = 0;
+  auto add = [&](void* base, int64_t ld_bytes, int64_t row_bytes) {   // (n or m = 0: nothing to exchange)
+    if (row_bytes > 0) rows[nr++] = towr_rows_t{base, ld_bytes, row_bytes};
+  };
+  for (double* p : {st.X, st.GR, st.XC, st.GRC, st.D}) add(p, 8 * st.ldx, 8 * (int64_t)L.n);
+  for (double* p : {st.LAM, st.LAMP}) add(p, 8 * st.ldl, 8 * (int64_t)L.m);
+  for (double* p : {st.HS, st.HY}) add(p, 8 * params->mem * st.ldh, 8 * ((params->mem - 1) * st.ldh + L.n));
+  add(st.HMETA, 8, 8);
+  for (double* p : {st.ALPHA, st.RHO, st.FC}) add(p, 8, 8);
+  add(st.SCAL, 8 * st.ldsc, 64);
+  add(st.ISTATE, 16, 16);
+  add(st.RSUM, 8 * st.ldrs, 8 * (4 + (int64_t)L.cons.size()));
+  add(st.SSUM, 8 * st.ldss, 8 * (5 + (int64_t)L.varsets.size()));
+  add(st.DSUM, 8 * st.ldds, 40);
+  add(st.USUM, 8 * st.ldus, 48);
+  add(st.LSUM, 8 * st.ldls, 64);
+  if (gn) {
+    add(dir->DC, 8 * st.ldx, 8 * (int64_t)L.n);
+    add(dir->GSUM, 8 * dir->ldgs, method == TOWR_SOLVE_GN ? 48 : 64);
+  }
+  if (GL && ldgb > 0) for (double* p : {GL, GU}) add(p, 8 * ldgb, 8 * (int64_t)L.m);
+  if (XL && ldxb > 0) for (double* p : {XL, XU}) add(p, 8 * ldxb, 8 * (int64_t)L.n);
+  if (int rc = swap_rows_args(h, nr, rows)) return rc;
+  if (pre != TOWR_OK) return pre;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (!al.h_head) HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&al.h_head), 8 * sizeof(int32_t), hipHostMallocDefault));
+  towr_terrain_t* ter = nullptr;   // the private copy of the batch terrains, exchanged with the rest
+  if (h->d_bterrain && B > 0 && opts->max_iters > 0) {
+    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&ter), sizeof(towr_terrain_t) * (size_t)B));
+    if (hipMemcpyAsync(ter, h->d_bterrain, sizeof(towr_terrain_t) * (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      (void)hipFree(ter);
+      return fail(h, TOWR_ERR_HIP, "solve: copying the batch terrains failed");
+    }
+    static_assert(sizeof(towr_terrain_t) % 8 == 0, "a terrain is exchanged as 8-byte words");
+    add(ter, sizeof(towr_terrain_t), sizeof(towr_terrain_t));
+  }
+  // HEAD to the host behind everything queued so far
+  auto head_sync = [&]() -> int {
+    HIPCHK(h, hipMemcpyAsync(al.h_head, LOG, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return TOWR_OK;
+  };
+
+  int32_t* pairs = LOG + 8;
+  std::vector<std::pair<int64_t, int>> swaps;   // per round that moved rows: (its first pair in the log, its pairs)
+  int64_t used = 0, problem_iters = 0;
+  int rounds = 0, iters_run = 0, Bcur = B, rc = TOWR_OK;
+  bool lost = false;   // a swap was queued whose pair count never reached the host
+  while (rc == TOWR_OK && iters_run < opts->max_iters && Bcur > 0) {
+    const int k = std::min(opts->check_every, opts->max_iters - iters_run);
+    rc = iterate(Bcur, k, ter);
+    if (rc == TOWR_OK) rc = launch_partition(h, Bcur, st.ISTATE, LOG, pairs + 2 * used, s);
+    if (rc == TOWR_OK && compact) rc = launch_swap_rows(h, LOG + 1, Bcur / 2, pairs + 2 * used, nr, rows, s);
+    if (rc == TOWR_OK && (rc = head_sync()) != TOWR_OK) lost = compact;
+    if (rc != TOWR_OK) break;
+    ++rounds;
+    iters_run += k;
+    problem_iters += (int64_t)Bcur * k;
+    const int na = al.h_head[0], np = al.h_head[1];
+    if (compact) {
+      if (np > 0) swaps.emplace_back(used, np);
+      used += np;
+      Bcur = na;
+    }
+    if (na == 0) break;
+  }
+  // back to the caller's order: the rounds' swaps again, the last first
+  int rb = TOWR_OK;
+  for (auto it = swaps.rbegin(); it != swaps.rend() && rb == TOWR_OK; ++it)
+    rb = launch_swap_rows(h, nullptr, it->second, pairs + 2 * it->first, nr, rows, s);
+  if (rb == TOWR_OK) rb = launch_partition(h, B, st.ISTATE, LOG, pairs, s);
+  if (rb == TOWR_OK) rb = head_sync();
+  else (void)hipStreamSynchronize(s);
+  if (ter) (void)hipFree(ter);
+  if (rc != TOWR_OK) {
+    if (rb != TOWR_OK || lost) return fail(h, rc, "solve: a round failed and so did putting the rows back: the row order is unspecified");
+    return rc;
+  }
+  if (rb != TOWR_OK) return fail(h, rb, "solve: putting the rows back failed: the row order is unspecified");
+  report->rounds = rounds;
+  report->iters_run = iters_run;
+  report->problem_iters = problem_iters;
+  for (int k = 0; k < 6; ++k) report->n_phase[k] = al.h_head[2 + k];
+  report->reserved[0] = report->reserved[1] = 0;
+  return TOWR_OK;
 }
 
 }  // extern "C"

@@ -180,6 +180,9 @@ struct towr_gpu_handle_s {
     double *d_xlo = nullptr, *d_xup = nullptr;
     double *d_sd = nullptr, *d_sf = nullptr;
     int64_t sd_cap = 0, sf_cap = 0;
+    // The solve driver (towr_gpu_alsolve_solve_batch_device): page-locked host memory for the partition's HEAD (8 ints),
+    // made by the first solve
+    int32_t* h_head = nullptr;
     void release();   // frees every device allocation above (towr_gpu_destroy, device handles only)
   } al;
 };

@@ -321,6 +321,27 @@ const void* linesearch_kernel();
 const void* alsolve_outer_kernel();
 const void* alsolve_init_kernel();
 
+// The compacting solve's kernels (towr_gpu_alsolve_solve_batch_device; lbfgs.hip). The partition: one block of
+// kLbfgsBlock threads over the B phase words. The swap: a grid of (pairs, arrays) blocks of kLbfgsBlock threads; npairs
+// is the number of pairs the grid holds, and the count itself when NP is NULL (else min(NP[0], npairs)). The array
+// descriptors travel in the argument struct.
+struct PartitionArgs {
+  const int32_t* ISTATE;
+  int32_t* HEAD;
+  int32_t* PAIRS;
+  int32_t B, reserved;
+};
+constexpr int kSwapMaxArrays = TOWR_SWAP_MAX_ARRAYS;
+struct SwapRows { char* base; int64_t ld_bytes, row_bytes; };
+struct SwapRowsArgs {
+  const int32_t* NP;
+  const int32_t* PAIRS;
+  int32_t npairs, n_arrays;
+  SwapRows rows[kSwapMaxArrays];
+};
+const void* alsolve_partition_kernel();
+const void* alsolve_swap_rows_kernel();
+
 struct Layout {
   int n = 0, m = 0;
   int64_t nnz = 0;

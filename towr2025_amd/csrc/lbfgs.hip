@@ -1,6 +1,7 @@
 // lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
 // and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device); and the kernels of the
-// resident AL loop built on them (the line search, the outer update, the state's initialisation; at the end).
+// resident AL loop built on them (the line search, the outer update, the state's initialisation; at the end), with the
+// two kernels of the compacting solve behind those (the partition plan and the row swap).
 //
 // The shape of resid.hip and step.hip. One block of kLbfgsBlock threads per problem. Lane l takes columns l,
 // l + kLbfgsBlock, ... in ascending order in every pass, so a column belongs to one lane for the whole kernel: the
@@ -490,8 +491,118 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_gn_select_kernel(GnSelectArg
   for (int j = tid; j < a.n; j += kLbfgsBlock) Db[j] = Sb[j];
 }
 
+// The partition plan of the compacting solve (towr_gpu_alsolve_partition_batch_device). One block. A row is active iff
+// its phase word is 0 or 1. The first pass counts the six classes of phase words (a ballot per class and stride, the
+// waves' counts added through LDS): na = the active rows. The second pass walks the rows again in strides of the block
+// and ranks the frozen rows in [0, na) and the active rows in [na, B), each in ascending row order: a lane's rank is the
+// running count of the strides before, the counts of the waves before it in this stride and the set bits below it in its
+// wave's ballot. Integer counts only: the result is a function of the phase words. Rank r < np <= B / 2 writes
+// PAIRS[2 r] (frozen) or PAIRS[2 r + 1] (active); nothing else of PAIRS is written.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_partition_kernel(PartitionArgs a) {
+  __shared__ int32_t s_cnt[kLbfgsWaves][6];
+  __shared__ int32_t s_tot[2][kLbfgsWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int B = a.B;
+  int32_t cnt[6] = {0, 0, 0, 0, 0, 0};
+  for (int base = 0; base < B; base += kLbfgsBlock) {   // (a uniform trip count: every lane takes every ballot)
+    const int i = base + tid;
+    int cls = -1;
+    if (i < B) {
+      const int32_t p = a.ISTATE[4 * (int64_t)i];
+      cls = (p >= 0 && p <= 4) ? p : 5;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cnt[k] += __popcll(__ballot(cls == k));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_cnt[wave][k] = cnt[k];
+  }
+  __syncthreads();
+  int32_t tot[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    tot[k] = 0;
+    for (int w = 0; w < kLbfgsWaves; ++w) tot[k] += s_cnt[w][k];
+  }
+  const int na = tot[0] + tot[1];
+  int32_t run_f = 0, run_a = 0;   // frozen rows ranked so far in [0, na), active rows in [na, B): the same in every lane
+  for (int base = 0; base < B; base += kLbfgsBlock) {
+    const int i = base + tid;
+    bool act = false;
+    if (i < B) {
+      const int32_t p = a.ISTATE[4 * (int64_t)i];
+      act = p == kAlRestart || p == kAlSearch;
+    }
+    const bool f = i < na && !act;           // (na <= B)
+    const bool g = i >= na && i < B && act;
+    const unsigned long long mf = __ballot(f), mg = __ballot(g);
+    if (lane == 0) {
+      s_tot[0][wave] = __popcll(mf);
+      s_tot[1][wave] = __popcll(mg);
+    }
+    __syncthreads();
+    int32_t off_f = run_f, off_a = run_a;
+    for (int w = 0; w < kLbfgsWaves; ++w) {
+      const int32_t tf = s_tot[0][w], ta = s_tot[1][w];
+      if (w < wave) { off_f += tf; off_a += ta; }
+      run_f += tf;
+      run_a += ta;
+    }
+    if (f) a.PAIRS[2 * (int64_t)(off_f + __popcll(mf & below))] = i;
+    if (g) a.PAIRS[2 * (int64_t)(off_a + __popcll(mg & below)) + 1] = i;
+    __syncthreads();   // s_tot is rewritten by the next stride
+  }
+  if (tid == 0) {
+    a.HEAD[0] = na;
+    a.HEAD[1] = run_f;   // (== run_a: [0, na) lacks as many active rows as [na, B) holds)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a.HEAD[2 + k] = tot[k];
+  }
+}
+
+// The row swap of the compacting solve (towr_gpu_alsolve_swap_rows_batch_device): block (i, k) exchanges bytes
+// [0, row_bytes) of rows PAIRS[2 i] and PAIRS[2 i + 1] of array k; blocks beyond the pair count (read from NP[0] when
+// given) exit. A lane reads its word of both rows into registers, then writes both; a word belongs to one lane and the
+// pairs are disjoint, so no two lanes of the grid touch the same byte. 8 bytes per lane where the array's base, leading
+// dimension and row length allow, else 4; coalesced.
+template <class T>
+__device__ inline void swap_words(char* p, char* q, int64_t bytes, int tid) {
+  T* u = reinterpret_cast<T*>(p);
+  T* v = reinterpret_cast<T*>(q);
+  const int64_t nw = bytes / (int64_t)sizeof(T);
+#pragma unroll 4
+  for (int64_t j = tid; j < nw; j += kLbfgsBlock) {
+    const T x = u[j], y = v[j];
+    u[j] = y;
+    v[j] = x;
+  }
+}
+
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_swap_rows_kernel(SwapRowsArgs a) {
+  const int i = blockIdx.x;
+  int count = a.npairs;
+  if (a.NP) {
+    count = a.NP[0];
+    if (count > a.npairs) count = a.npairs;   // (npairs: the grid's pairs, max_pairs)
+  }
+  if (i >= count) return;
+  const int32_t f = a.PAIRS[2 * (int64_t)i], g = a.PAIRS[2 * (int64_t)i + 1];
+  if (f < 0 || g < 0 || f == g) return;   // (never from the partition)
+  const SwapRows& r = a.rows[blockIdx.y];
+  char* p = r.base + (int64_t)f * r.ld_bytes;
+  char* q = r.base + (int64_t)g * r.ld_bytes;
+  if (((reinterpret_cast<uintptr_t>(r.base) | (uintptr_t)r.ld_bytes | (uintptr_t)r.row_bytes) & 7) == 0)
+    swap_words<unsigned long long>(p, q, r.row_bytes, threadIdx.x);
+  else
+    swap_words<uint32_t>(p, q, r.row_bytes, threadIdx.x);
+}
+
 }  // namespace
 
+const void* alsolve_partition_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_partition_kernel); }
+const void* alsolve_swap_rows_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_swap_rows_kernel); }
 const void* gn_select_kernel() { return reinterpret_cast<const void*>(&towr_gn_select_kernel); }
 const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }

@@ -856,6 +856,98 @@ class TowrGpuProblem:
             self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
             wp, ldw, wr, gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
 
+    # -------------------------------------------------------------------- solve to completion -
+    def _int_operand(self, t, what, count):
+        import torch
+        if t.dtype != torch.int32 or t.device.type != "cuda" or t.device.index != self.device or not t.is_contiguous() \
+                or t.numel() < count:
+            raise TowrGpuError(f"{what}: expected a contiguous int32 tensor of >= {count} entries on the handle's device")
+        return C.c_void_p(t.data_ptr())
+
+    def alsolve_partition(self, ISTATE, HEAD, PAIRS, B=None, stream=None):
+        """The partition plan of a batch by its phases (towr_gpu.h): ISTATE int32 (>= 4 B), HEAD int32 (>= 8) takes
+        na, np and the six phase counts, PAIRS int32 (>= 2 (B // 2)) the (frozen row, active row) pairs whose exchange
+        puts the active rows in front. B None: ISTATE.numel() // 4."""
+        B = ISTATE.numel() // 4 if B is None else int(B)
+        self._check(self._lib.towr_gpu_alsolve_partition_batch_device(
+            self._h, B, self._int_operand(ISTATE, "ISTATE", 4 * B), self._int_operand(HEAD, "HEAD", 8),
+            self._int_operand(PAIRS, "PAIRS", 2 * (B // 2)), self._stream(stream, ISTATE)))
+
+    def alsolve_swap_rows(self, PAIRS, arrays, NP=None, npairs=0, max_pairs=None, stream=None):
+        """Exchange rows PAIRS[2 i] and PAIRS[2 i + 1], i < count, of every array in place (towr_gpu.h). `arrays`: torch
+        HIP tensors (1-D: rows of one element; 2-D: row-major rows, any padding behind the columns of a view is not
+        touched) or (tensor, columns) to exchange only the first `columns` of each row. The count is NP[0] (an int32
+        device tensor, e.g. HEAD[1:]; the grid holds max_pairs pairs, default PAIRS.numel() // 2) or, with NP None, the
+        host value npairs."""
+        desc = (capi.Rows * max(len(arrays), 1))()
+        if len(arrays) > capi.SWAP_MAX_ARRAYS:
+            raise TowrGpuError(f"alsolve_swap_rows: {len(arrays)} arrays, at most {capi.SWAP_MAX_ARRAYS}")
+        for k, a in enumerate(arrays):
+            t, cols = a if isinstance(a, tuple) else (a, None)
+            if t.device.type != "cuda" or t.device.index != self.device or t.dim() not in (1, 2) or \
+                    (t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1):
+                raise TowrGpuError(f"alsolve_swap_rows: array {k}: expected a 1-D or row-major 2-D tensor on the handle's device")
+            es = t.element_size()
+            width = 1 if t.dim() == 1 else t.shape[1]
+            cols = width if cols is None else int(cols)
+            if cols > width:
+                raise TowrGpuError(f"alsolve_swap_rows: array {k}: {cols} columns of {width}")
+            ld = t.stride(0) if t.shape[0] > 1 else max(width, 1)
+            desc[k].base, desc[k].ld_bytes, desc[k].row_bytes = t.data_ptr(), ld * es, cols * es
+        if NP is None:
+            np_, n, mx = C.c_void_p(None), int(npairs), 0
+            need = 2 * n
+        else:
+            mx = PAIRS.numel() // 2 if max_pairs is None else int(max_pairs)
+            np_, n = self._int_operand(NP, "NP", 1), 0
+            need = 2 * mx
+        self._check(self._lib.towr_gpu_alsolve_swap_rows_batch_device(
+            self._h, np_, n, mx, self._int_operand(PAIRS, "PAIRS", max(need, 0)), len(arrays), desc, self._stream(stream, PAIRS)))
+
+    def alsolve_solve(self, params, st, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
+                      precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, compact=True,
+                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None):
+        """Run the resident loop to completion (towr_gpu.h, towr_gpu_alsolve_solve_batch_device): rounds of check_every
+        iterations of the method's iterate entry (capi.SOLVE_*; gn, DC, GSUM, PC / precond, W / wrows as that entry
+        takes them), the host looking at the phases once per round, until every problem is frozen or max_iters
+        iterations have run. compact: the frozen problems are moved out of the batch between rounds; every array is
+        back in the caller's order at return, and the persistent arrays hold the bits of the plain iterate loop. Per-problem
+        GL / GU / XL / XU rows are permuted during the call. The call blocks the host. LOG: int32 (>= 8 + 2 B), allocated
+        when None. Returns dict(rounds, iters_run, problem_iters, n_phase (6 counts: phases 0..4, other))."""
+        import torch
+        c = self._alsolve_state(st, params)
+        B = st.B
+        d = capi.SolveDir()
+        if method != capi.SOLVE_LBFGS:
+            if gn is None or DC is None or GSUM is None:
+                raise TowrGpuError("alsolve_solve: a GN method needs gn, DC and GSUM")
+            self._check_rows(B, (DC, "DC", self.n), (GSUM, "GSUM", 6 if method == capi.SOLVE_GN else 8))
+            if DC.stride(0) != st.X.stride(0):
+                raise TowrGpuError("X and DC: they share one leading dimension")
+            d.gn, d.DC, d.GSUM, d.ldgs = C.pointer(gn), DC.data_ptr(), GSUM.data_ptr(), GSUM.stride(0)
+        if method == capi.SOLVE_GN_PC:
+            d.precond = int(precond)
+            if PC is not None:
+                self._check_rows(B, (PC, "PC", self.n))
+                if PC.stride(0) != st.X.stride(0):
+                    raise TowrGpuError("X and PC: they share one leading dimension")
+                d.PC = PC.data_ptr()
+        if method in (capi.SOLVE_GN_DIRECT, capi.SOLVE_GN_TILED):
+            if W is None:
+                raise TowrGpuError("alsolve_solve: the direct methods need the workspace W")
+            wp, d.ldw, d.wrows = self._gn_workspace(W, wrows, B)
+            d.W = wp.value
+        gl, gu, ldgb = self._bounds_operands(B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(B, XL, XU)
+        if LOG is None:
+            LOG = torch.zeros(8 + 2 * B, dtype=torch.int32, device=st.X.device)
+        opts = capi.SolveOpts(method=int(method), max_iters=int(max_iters), check_every=int(check_every), compact=int(bool(compact)))
+        rep = capi.SolveReport()
+        self._check(self._lib.towr_gpu_alsolve_solve_batch_device(
+            self._h, B, C.byref(opts), C.byref(params), C.byref(c), C.byref(d), gl, gu, ldgb, xl, xu, ldxb,
+            self._int_operand(LOG, "LOG", 8 + 2 * B), C.byref(rep), self._stream(stream, st.X)))
+        return dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase))
+
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
         self._check(self._lib.towr_gpu_set_products_chunk(self._h, int(k)))
