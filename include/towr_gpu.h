@@ -1063,6 +1063,61 @@ int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr
                                         double* XL, double* XU, int64_t ldxb, int32_t* LOG, towr_solve_report_t* report,
                                         void* stream);
 
+/* ---- two more stops for the resident loop: an acceptable point, and an infeasible stationary point ----------------- */
+/* Two more frozen phases. Every kernel above treats a phase word outside {0, 1} as frozen, so a problem in one of them
+ * is skipped by the line search, the directions' RUN masks and the partition like a CONVERGED one.
+ *   ACCEPTABLE: the base stayed within (acc_eta, acc_omega) for acc_iters consecutive iterations while the loop could
+ *     not reach (eta_star, omega_star): the counterpart of IPOPT's acceptable termination (acceptable_tol,
+ *     acceptable_iter).
+ *   INFEASIBLE: the penalty is about to grow again although it is already >= infeas_rho and the violation has not
+ *     fallen below infeas_keep x its value at the previous growth: a stationary point of the infeasibility.          */
+#define TOWR_AL_ACCEPTABLE 5
+#define TOWR_AL_INFEASIBLE 6
+
+/* The rule's parameters (host memory, read at the call). acc_iters = 0 switches the acceptable rule off;
+ * infeas_rho = +inf switches the infeasible rule off. TOWR_ERR_INVALID before anything runs for: acc_eta, acc_omega or
+ * infeas_rho negative or NaN, acc_iters < 0, infeas_keep outside (0, 1] or NaN.                                     */
+typedef struct {
+  double acc_eta, acc_omega;
+  int32_t acc_iters, reserved;
+  double infeas_keep, infeas_rho;
+} towr_alsolve_stop_t;
+
+/* The stop rule alone, between towr_gpu_linesearch_batch_device and towr_gpu_auglag_outer_batch_device. One thread per
+ * problem. It acts on problem b only if phase == SEARCH; of any other problem (RESTART, frozen, any other word) not one
+ * byte changes. It keeps its memory in the two spare slots of SCAL, which towr_gpu_alsolve_init_batch_device zeroes:
+ * SCAL[6], a run length (a small exact integer held in a double), and SCAL[7], the violation at the previous penalty
+ * growth. With viol = SCAL[4], pg = SCAL[1], omega = SCAL[3], eta = SCAL[2], flags and inner as the line search left
+ * them, and with acc_iters > 0:
+ *   run = (viol <= acc_eta and pg <= acc_omega) ? SCAL[6] + 1 : 0; SCAL[6] = run;
+ *   run >= acc_iters: phase = ACCEPTABLE, ALPHA[b] = 0, flags = 0; nothing else.
+ * (acc_iters = 0: SCAL[6] is not written and the rule never fires.) Otherwise, with
+ *   grow = (flags & 1) and (pg <= omega or inner >= max_inner) and not (viol <= eta),
+ * which is exactly the outer update's condition for its RHO branch (a NaN viol included):
+ *   grow and SCAL[7] > 0 and viol >= infeas_keep * SCAL[7] (one rounded product) and RHO[b] >= infeas_rho:
+ *     phase = INFEASIBLE, ALPHA[b] = 0, flags = 0 (the outer update then does not act on the problem);
+ *   grow otherwise: SCAL[7] = viol (the outer update grows RHO behind this call).
+ * A NaN operand falls on the NON-STOPPING side of every comparison: a NaN viol or pg resets the run length; a NaN
+ * viol, SCAL[7] or RHO[b] never gives INFEASIBLE (a NaN viol is then recorded in SCAL[7], and fails the next test
+ * too). Only IEEE comparisons and the one product: problem b's outputs are a function of its own operands. Of `params`
+ * only max_inner is used, but the whole struct is checked as in the outer update. Fields used: ALPHA, RHO, SCAL,
+ * ISTATE. No handle scratch; the kept Jacobian is not dropped. TOWR_ERR_INVALID before anything runs for: NULL params,
+ * state or stop, an invalid params or stop field, NULL ISTATE, SCAL, HMETA, ALPHA or RHO, ldsc < 8, B < 0.           */
+int towr_gpu_alsolve_stop_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                       const towr_alsolve_stop_t* stop, const towr_alsolve_state_t* state, void* stream);
+
+/* towr_gpu_alsolve_solve_batch_device with the stop rule in every iteration: the method's iterate entry with
+ * towr_gpu_alsolve_stop_batch_device between its line search and its outer update (bit-identical to those calls in
+ * sequence). Compaction needs nothing more: SCAL rows travel with their problem. report->reserved[0] and [1] hold the
+ * number of problems in phase ACCEPTABLE and INFEASIBLE after the final partition (both are also part of n_phase[5],
+ * "any other word"). stop == NULL: towr_gpu_alsolve_solve_batch_device itself, its launches and its report
+ * (reserved = 0). TOWR_ERR_INVALID before anything runs for what that entry refuses and for an invalid stop field.   */
+int towr_gpu_alsolve_solve_ex_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                           const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                           const towr_alsolve_state_t* state, const towr_solve_dir_t* dir, double* GL,
+                                           double* GU, int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
+                                           towr_solve_report_t* report, void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

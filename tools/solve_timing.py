@@ -15,7 +15,13 @@ A solve is timed by the host clock from a synchronised device to the return of t
 it returns; the hand loop ends in a copy to the host); the state is restored and alsolve_init run before every solve,
 outside the window. Printed: the median and the spread over ROUNDS per variant, iters_run, problem_iters, the phase counts,
 the ratio of times beside the ratio of problem_iters, and whether compact = 1 and compact = 0 left the same bits in X.
-usage: python tools/solve_timing.py [anymal|monoped|all]"""
+Environment: FEASIBLE=1 gives the ANYmal goal the standing height -nominal_stance[0][2] (the default goal z = 0 has no
+feasible point); STOP=1 runs the driver through towr_gpu_alsolve_solve_ex_batch_device with the stop rule's
+example parameters (ACC_ETA 1e-6, ACC_OMEGA 1e-4, ACC_ITERS 15, INFEAS_KEEP 0.99, INFEAS_RHO 1e4) and leaves out the hand
+loop, whose iterate entry has no rule; MAX_INNER overrides SOLVE_PAR's 200.
+`stopcost`: the rule's own cost — one round of STOPCOST_ITERS (default 20) iterations on all B ANYmal problems (default
+4096), compact = 0, with and without the rule, alternated, per iteration.
+usage: python tools/solve_timing.py [anymal|monoped|all|stopcost]"""
 import ctypes as C
 import os
 import statistics
@@ -27,7 +33,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from towr2025_amd import AlSolveState, TowrGpuProblem, _capi as capi, alsolve_params, gn_params  # noqa: E402
+from towr2025_amd import AlSolveState, TowrGpuProblem, _capi as capi, alsolve_params, alsolve_stop_params, gn_params  # noqa: E402
 from towr2025_amd import formulation as F  # noqa: E402
 
 ROUNDS = int(os.environ.get("ROUNDS", "3"))
@@ -35,7 +41,23 @@ MAX_ITERS = int(os.environ.get("MAX_ITERS", "120"))
 KS = [int(k) for k in os.environ.get("KS", "4,16").split(",")]
 MU = float(os.environ.get("MU", "1e-6"))
 SEED = int(os.environ.get("SEED", "900"))
-SOLVE_PAR = dict(mem=8, shrink=0.1, rho0=10.0, curv_eps=1e-14, max_inner=200, alpha_min=1e-16)
+SOLVE_PAR = dict(mem=8, shrink=0.1, rho0=10.0, curv_eps=1e-14, max_inner=int(os.environ.get("MAX_INNER", "200")), alpha_min=1e-16)
+FEASIBLE = os.environ.get("FEASIBLE", "0") == "1"
+STOP = os.environ.get("STOP", "0") == "1"
+
+
+def stop_params():
+    e = os.environ.get
+    return alsolve_stop_params(acc_eta=float(e("ACC_ETA", "1e-6")), acc_omega=float(e("ACC_OMEGA", "1e-4")),
+                               acc_iters=int(e("ACC_ITERS", "15")), infeas_keep=float(e("INFEAS_KEEP", "0.99")),
+                               infeas_rho=float(e("INFEAS_RHO", "1e4")))
+
+
+def anymal():
+    f = F.anymal_trot(goal=(2.1, 0.0, -F.RobotModel(F.RobotModel.Anymal).kinematic_model.nominal_stance[0][2])) if FEASIBLE \
+        else F.anymal_trot()
+    f.params_.enable_stance_tracking = False
+    return TowrGpuProblem(f.to_desc(), device=0, data=f.var_bounds_data())
 
 
 def run(title, p, B):
@@ -60,9 +82,11 @@ def run(title, p, B):
         p.alsolve_init(par, st, stream=stream)
         torch.cuda.synchronize()
 
+    stop = stop_params() if STOP else None
+
     def driver(K, compact):
         return p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=MAX_ITERS,
-                               check_every=K, compact=compact, LOG=LOG, stream=stream)
+                               check_every=K, compact=compact, LOG=LOG, stream=stream, stop=stop)
 
     def hand(K):
         phases = st.ISTATE.view(B, 4)[:, 0]
@@ -82,8 +106,9 @@ def run(title, p, B):
     variants = []
     for K in KS:
         variants += [(f"n  K={K:<2d} compact=0", "spread", lambda K=K: driver(K, False)),
-                     (f"c  K={K:<2d} compact=1", "spread", lambda K=K: driver(K, True)),
-                     (f"h  K={K:<2d} hand loop", "spread", lambda K=K: hand(K))]
+                     (f"c  K={K:<2d} compact=1", "spread", lambda K=K: driver(K, True))]
+        if not STOP:
+            variants += [(f"h  K={K:<2d} hand loop", "spread", lambda K=K: hand(K))]
     variants += [(f"n1 K={KS[0]:<2d} compact=0, one start", "same", lambda: driver(KS[0], False)),
                  (f"c1 K={KS[0]:<2d} compact=1, one start", "same", lambda: driver(KS[0], True))]
     # warm-up: every variant once (the tables' upload, the scratch, the page-locked HEAD); the bits of X kept per variant
@@ -102,16 +127,23 @@ def run(title, p, B):
             torch.cuda.synchronize()
             times[name].append(1e3 * (time.perf_counter() - t0))
     codes = torch.bincount(GS[:, 5].to(torch.int64).clamp(0, 3), minlength=4).tolist()
-    print(f"{title}: B={B} n={p.n} m={p.m} nnz={p.nnz} mu={MU} max_iters={MAX_ITERS} rounds={ROUNDS}; direction codes 0..3 of "
+    print(f"{title}: B={B} n={p.n} m={p.m} nnz={p.nnz} mu={MU} max_iters={MAX_ITERS} max_inner={SOLVE_PAR['max_inner']} "
+          f"rounds={ROUNDS} stop={'on' if STOP else 'off'}; direction codes 0..3 of "
           f"the last solve {codes}", flush=True)
     med = {}
     for name, _, _ in variants:
         t, r = times[name], reports[name]
         med[name] = statistics.median(t)
         print(f"  {name:32s} {med[name]:9.2f} ms  (min {min(t):.2f} max {max(t):.2f})  rounds {r['rounds']} iters_run {r['iters_run']} "
-              f"problem_iters {r['problem_iters']} phases 0..4,other {r['n_phase']}", flush=True)
+              f"problem_iters {r['problem_iters']} phases 0..4,other {r['n_phase']}"
+              + (f" acceptable {r['n_acceptable']} infeasible {r['n_infeasible']}" if STOP else ""), flush=True)
     for K in KS:
         nn, cc, hh = (f"{v}  K={K:<2d} {w}" for v, w in (("n", "compact=0"), ("c", "compact=1"), ("h", "hand loop")))
+        if STOP:
+            print(f"  K={K}: time c / n {med[cc] / med[nn]:.3f} vs problem_iters c / n "
+                  f"{reports[cc]['problem_iters'] / max(reports[nn]['problem_iters'], 1):.3f}; X bit-equal c vs n: "
+                  f"{torch.equal(bits[cc].view(torch.int64), bits[nn].view(torch.int64))}", flush=True)
+            continue
         print(f"  K={K}: time c / n {med[cc] / med[nn]:.3f} vs problem_iters c / n "
               f"{reports[cc]['problem_iters'] / max(reports[nn]['problem_iters'], 1):.3f}; driver n / hand loop {med[nn] / med[hh]:.3f}; "
               f"X bit-equal c vs n: {torch.equal(bits[cc].view(torch.int64), bits[nn].view(torch.int64))}, n vs hand: "
@@ -121,12 +153,44 @@ def run(title, p, B):
           f"{torch.equal(bits[c1].view(torch.int64), bits[n1].view(torch.int64))}", flush=True)
 
 
+def stop_cost(p, B):
+    """One round of `iters` iterations on the whole batch with and without the rule, alternated."""
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    n, mem, iters = p.n, SOLVE_PAR["mem"], int(os.environ.get("STOPCOST_ITERS", "20"))
+    par, gn, stop = alsolve_params(**SOLVE_PAR), gn_params(mu=MU), stop_params()
+    x0 = p.initial_x()
+    X0 = torch.from_numpy(np.stack([x0 + 0.05 * np.random.default_rng(SEED + b).standard_normal(n) for b in range(B)])).to(dev)
+    st = AlSolveState.allocate(p, B, mem)
+    DC, GS = torch.zeros_like(st.X), torch.zeros((B, 8), dtype=torch.float64, device=dev)
+    W = torch.empty((B, p.gn_tile_info()["ldw_min"]), dtype=torch.float64, device=dev)
+    LOG = torch.zeros(8 + 2 * B, dtype=torch.int32, device=dev)
+    times = {"without": [], "with": []}
+    for r in range(ROUNDS + 1):               # (round 0: warm-up)
+        for name, s in (("without", None), ("with", stop)):
+            st.X.copy_(X0)
+            st.LAM.zero_()
+            p.alsolve_init(par, st, stream=stream)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=iters,
+                            check_every=iters, compact=False, LOG=LOG, stream=stream, stop=s)
+            torch.cuda.synchronize()
+            if r:
+                times[name].append(1e3 * (time.perf_counter() - t0) / iters)
+    a, b = statistics.median(times["without"]), statistics.median(times["with"])
+    print(f"stop rule's cost: anymal B={B}, one round of {iters} iterations, ms per iteration: without {a:.4f} "
+          f"(min {min(times['without']):.4f} max {max(times['without']):.4f}), with {b:.4f} (min {min(times['with']):.4f} max "
+          f"{max(times['with']):.4f}), difference {1e3 * (b - a):.1f} us", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "anymal"
+    if which == "stopcost":
+        stop_cost(anymal(), int(os.environ.get("B", "4096")))
     if which in ("anymal", "all"):
-        f = F.anymal_trot()
-        f.params_.enable_stance_tracking = False
-        run("anymal_trot", TowrGpuProblem(f.to_desc(), device=0, data=f.var_bounds_data()), int(os.environ.get("B", "1024")))
+        run("anymal_trot_feasible" if FEASIBLE else "anymal_trot", anymal(), int(os.environ.get("B", "1024")))
     if which in ("monoped", "all"):
         f, vs, cs, goal, T = F.procedural_monoped()
         vb = f.var_bounds_data(varsets=vs, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)

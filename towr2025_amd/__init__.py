@@ -6,6 +6,7 @@
   towr2025_amd._capi         ctypes mirror of include/towr_gpu.h, loader of lib/libtowr_gpu.so
 """
 from . import _capi, formulation  # noqa: F401
-from .problem import AlSolveState, TowrGpuError, TowrGpuProblem, alsolve_params, gn_params  # noqa: F401
+from .problem import (AlSolveState, TowrGpuError, TowrGpuProblem, alsolve_params, alsolve_stop_params,  # noqa: F401
+                      gn_params)
 
-__all__ = ["TowrGpuProblem", "TowrGpuError", "AlSolveState", "alsolve_params", "gn_params", "formulation"]
+__all__ = ["TowrGpuProblem", "TowrGpuError", "AlSolveState", "alsolve_params", "alsolve_stop_params", "gn_params", "formulation"]

@@ -80,6 +80,7 @@ GN_TILE = 16                      # TOWR_GN_TILE: the tile edge towr_gpu_gn_tile
 
 
 AL_RESTART, AL_SEARCH, AL_CONVERGED, AL_STALLED, AL_MAXED = range(5)   # TOWR_AL_*: the phases of the resident loop
+AL_ACCEPTABLE, AL_INFEASIBLE = 5, 6                                     # the stop rule's two frozen phases
 
 
 class AlSolveParams(C.Structure):   # towr_alsolve_params_t
@@ -99,6 +100,11 @@ class AlSolveStateC(C.Structure):   # towr_alsolve_state_t
                 ("RSUM", C.c_void_p), ("ldrs", C.c_int64), ("SSUM", C.c_void_p), ("ldss", C.c_int64),
                 ("DSUM", C.c_void_p), ("ldds", C.c_int64), ("USUM", C.c_void_p), ("ldus", C.c_int64),
                 ("LSUM", C.c_void_p), ("ldls", C.c_int64)]
+
+
+class AlSolveStop(C.Structure):   # towr_alsolve_stop_t
+    _fields_ = [("acc_eta", C.c_double), ("acc_omega", C.c_double), ("acc_iters", C.c_int32), ("reserved", C.c_int32),
+                ("infeas_keep", C.c_double), ("infeas_rho", C.c_double)]
 
 
 class GnParams(C.Structure):   # towr_gn_params_t
@@ -298,6 +304,12 @@ SYMBOLS = {
                                                        C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
                                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                        C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
+    "towr_gpu_alsolve_stop_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(AlSolveParams), C.POINTER(AlSolveStop),
+                                                      C.POINTER(AlSolveStateC), C.c_void_p]),
+    "towr_gpu_alsolve_solve_ex_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(SolveOpts), C.POINTER(AlSolveParams),
+                                                          C.POINTER(AlSolveStop), C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
+                                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

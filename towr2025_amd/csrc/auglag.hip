@@ -520,9 +520,19 @@ int alsolve_params(towr_gpu_handle h, const towr_alsolve_params_t* p) {
   return TOWR_OK;
 }
 
+// the stop rule's parameters (towr_alsolve_stop_t)
+int alsolve_stop_params(towr_gpu_handle h, const towr_alsolve_stop_t* sp) {
+  if (!sp) return fail(h, TOWR_ERR_INVALID, "null stop");
+  if (!(sp->acc_eta >= 0) || !(sp->acc_omega >= 0) || !(sp->infeas_rho >= 0))   // (a NaN fails every test)
+    return fail(h, TOWR_ERR_INVALID, "stop: acc_eta, acc_omega or infeas_rho is negative or NaN");
+  if (sp->acc_iters < 0) return fail(h, TOWR_ERR_INVALID, "stop: acc_iters is negative");
+  if (!(sp->infeas_keep > 0 && sp->infeas_keep <= 1)) return fail(h, TOWR_ERR_INVALID, "stop: infeas_keep outside (0, 1]");
+  return TOWR_OK;
+}
+
 // the state fields an entry uses: kAlLs the line search's, kAlOuter the outer update's, kAlInit the initialisation's;
-// the iteration uses every field
-enum : unsigned { kAlLs = 1, kAlOuter = 2, kAlInit = 4, kAlAll = 8 };
+// kAlStop the stop rule's; the iteration uses every field
+enum : unsigned { kAlLs = 1, kAlOuter = 2, kAlInit = 4, kAlAll = 8, kAlStop = 16 };
 int alsolve_state(towr_gpu_handle h, const towr_alsolve_state_t* s, unsigned use) {
   if (!s) return fail(h, TOWR_ERR_INVALID, "null state");
   const Layout& L = h->L;
@@ -533,7 +543,7 @@ int alsolve_state(towr_gpu_handle h, const towr_alsolve_state_t* s, unsigned use
   if (ls && (!s->GR || !s->GRC)) return fail(h, TOWR_ERR_INVALID, "state: null GR or GRC");
   if ((in || all) && !s->D) return fail(h, TOWR_ERR_INVALID, "state: null D");
   if ((ls || in) && s->ldx < L.n) return fail(h, TOWR_ERR_INVALID, "state: ldx smaller than n");
-  if ((ou || in) && !s->RHO) return fail(h, TOWR_ERR_INVALID, "state: null RHO");
+  if ((ou || in || (use & kAlStop)) && !s->RHO) return fail(h, TOWR_ERR_INVALID, "state: null RHO");
   if (ou && (!s->LAM || !s->LAMP)) return fail(h, TOWR_ERR_INVALID, "state: null LAM or LAMP");
   if (ou && s->ldl < L.m) return fail(h, TOWR_ERR_INVALID, "state: ldl smaller than m");
   if (ls) {
@@ -681,6 +691,15 @@ int launch_outer(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const
   OuterArgs a{st, p, h->L.m};
   void* args[] = {&a};
   HIPCHK(h, launch_kernel(alsolve_outer_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+// the stop rule: one thread per problem
+int launch_stop(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const towr_alsolve_stop_t& sp,
+                const towr_alsolve_state_t& st, hipStream_t s) {
+  StopArgs a{st.ISTATE, st.SCAL, st.ldsc, st.ALPHA, st.RHO, sp, p.max_inner, B};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_stop_kernel(), dim3((unsigned)((B + kLbfgsBlock - 1) / kLbfgsBlock)), dim3(kLbfgsBlock), args, 0, s));
   return TOWR_OK;
 }
 
@@ -1056,6 +1075,17 @@ int towr_gpu_auglag_outer_batch_device(towr_gpu_handle h, int32_t B, const towr_
   return launch_outer(h, B, *params, *state, reinterpret_cast<hipStream_t>(stream));
 }
 
+int towr_gpu_alsolve_stop_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                       const towr_alsolve_stop_t* stop, const towr_alsolve_state_t* state, void* stream) {
+  if (!h || B < 0) return fail(h, TOWR_ERR_INVALID, "bad argument (B < 0)");
+  if (int rc = alsolve_params(h, params)) return rc;
+  if (int rc = alsolve_stop_params(h, stop)) return rc;
+  if (int rc = alsolve_state(h, state, kAlStop)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  return launch_stop(h, B, *params, *stop, *state, reinterpret_cast<hipStream_t>(stream));
+}
+
 // what the iteration refuses (the initialisation answers the same arguments, so a loop fails at its first call)
 static int alsolve_args(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
                         const double* GL, const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb) {
@@ -1086,12 +1116,14 @@ int towr_gpu_alsolve_init_batch_device(towr_gpu_handle h, int32_t B, const towr_
 // Per iteration what the six public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag
 // chunks with the per-problem RHO accumulated onto GRC (g in handle scratch), the line search, the outer update, the
 // direction of the problems whose flag bit 1 is set (RUN = the flags) and the step.
-// (ter: fused()'s, the solve driver's permuted terrains)
+// (ter: fused()'s, the solve driver's permuted terrains; stop: the stop rule between the line search and the outer update)
 static int alsolve_lbfgs_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                                  const towr_alsolve_state_t* state, const double* GL, const double* GU, int64_t ldgb,
                                  const double* XL, const double* XU, int64_t ldxb, void* stream,
-                                 const towr_terrain_t* ter = nullptr) {
+                                 const towr_terrain_t* ter = nullptr, const towr_alsolve_stop_t* stop = nullptr) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
+  if (stop)
+    if (int rc = alsolve_stop_params(h, stop)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   const towr_alsolve_state_t& st = *state;
   ResArgs r{nullptr, 0, GL, GU, ldgb, st.LAM, st.ldl, st.LAMP, st.ldl, st.RSUM, st.ldrs};
@@ -1112,6 +1144,7 @@ static int alsolve_lbfgs_iterate(towr_gpu_handle h, int32_t B, int32_t iters, co
       if (rc == TOWR_OK)
         rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b);
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
+      if (rc == TOWR_OK && stop) rc = launch_stop(h, B, *params, *stop, st, b.s);
       if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
       if (rc == TOWR_OK) rc = launch_lbfgs_direction(h, B, dir, b.s);
       if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
@@ -1181,13 +1214,16 @@ int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const to
 // Per iteration what the public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag chunks
 // with the per-problem RHO accumulated onto GRC and, per chunk, the GN direction at (XC, GRC) into DC on the values still
 // in handle scratch (RUN = the phases: frozen problems are skipped), the line search, the outer update, the select
-// (D <- DC or GR by the flags) and the step.
+// (D <- DC or GR by the flags) and the step. (stop: as above)
 static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                               const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC, double* GSUM,
                               int64_t ldgs, bool pc, int32_t precond, double* PC, const double* GL, const double* GU, int64_t ldgb,
                               const double* XL, const double* XU, int64_t ldxb, void* stream, const GnWorkspace* ws = nullptr,
-                              const towr_terrain_t* ter = nullptr) {   // (ter: fused()'s)
+                              const towr_terrain_t* ter = nullptr,   // (ter: fused()'s)
+                              const towr_alsolve_stop_t* stop = nullptr) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
+  if (stop)
+    if (int rc = alsolve_stop_params(h, stop)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   if (int rc = ws ? gn_direct_params(h, gn, DC, GSUM, ldgs, *ws) : gn_params(h, gn, DC, GSUM, ldgs)) return rc;
   const towr_alsolve_state_t& st = *state;
@@ -1240,6 +1276,7 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
         rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b,
                            ws ? nullptr : &g, ws && !tiled ? &gd : nullptr, ws ? ws->wrows : 0, tiled ? &gt : nullptr);
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
+      if (rc == TOWR_OK && stop) rc = launch_stop(h, B, *params, *stop, st, b.s);
       if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
       if (rc == TOWR_OK) rc = launch_gn_select(h, B, st, DC, b.s);
       if (rc == TOWR_OK) rc = launch_step(h, B, step, b.s);
@@ -1421,10 +1458,13 @@ int towr_gpu_alsolve_swap_rows_batch_device(towr_gpu_handle h, const int32_t* NP
   return launch_swap_rows(h, NP, NP ? max_pairs : npairs, PAIRS, n_arrays, arrays, reinterpret_cast<hipStream_t>(stream));
 }
 
-int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
-                                        const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
-                                        const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb, double* XL, double* XU,
-                                        int64_t ldxb, int32_t* LOG, towr_solve_report_t* report, void* stream) {
+}  // extern "C"
+
+// both solve entries; stop NULL: the plain loop and the plain report
+static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts, const towr_alsolve_params_t* params,
+                         const towr_alsolve_stop_t* stop, const towr_alsolve_state_t* state, const towr_solve_dir_t* dir,
+                         double* GL, double* GU, int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
+                         towr_solve_report_t* report, void* stream) {
   if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
   if (!opts || !dir || !LOG || !report) return fail(h, TOWR_ERR_INVALID, "solve: null opts, dir, LOG or report");
   if (opts->method < TOWR_SOLVE_LBFGS || opts->method > TOWR_SOLVE_GN_TILED) return fail(h, TOWR_ERR_INVALID, "solve: method outside 0..4");
@@ -1436,11 +1476,11 @@ int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr
   const GnWorkspace ws{dir->W, dir->ldw, dir->wrows, method == TOWR_SOLVE_GN_TILED};
   // `iters` iterations of the method's iterate entry on rows [0, Bc): its own checks and launches (iters = 0: the checks)
   auto iterate = [&](int Bc, int iters, const towr_terrain_t* ter) -> int {
-    if (!gn) return alsolve_lbfgs_iterate(h, Bc, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream, ter);
+    if (!gn) return alsolve_lbfgs_iterate(h, Bc, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream, ter, stop);
     const bool pc = method == TOWR_SOLVE_GN_PC;
     return alsolve_gn_iterate(h, Bc, iters, params, state, dir->gn, dir->DC, dir->GSUM, dir->ldgs, pc,
                               pc ? dir->precond : (int32_t)TOWR_GN_PC_NONE, pc ? dir->PC : nullptr, GL, GU, ldgb, XL, XU, ldxb, stream,
-                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter);
+                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter, stop);
   };
   // the iterate entry's refusals, TOWR_ERR_NO_DEVICE and TOWR_ERR_UNSUPPORTED (it binds the handle); nothing is queued.
   // Its argument checks come first: with another code they have passed, and this entry's own follow before that code
@@ -1539,7 +1579,33 @@ int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr
   report->problem_iters = problem_iters;
   for (int k = 0; k < 6; ++k) report->n_phase[k] = al.h_head[2 + k];
   report->reserved[0] = report->reserved[1] = 0;
+  if (stop && B > 0) {   // the two new words among "any other word": counted on the host from the phase words
+    std::vector<int32_t> is(4 * (size_t)B);
+    HIPCHK(h, hipMemcpyAsync(is.data(), st.ISTATE, sizeof(int32_t) * is.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) {
+      if (is[4 * (size_t)b] == kAlAcceptable) ++report->reserved[0];
+      if (is[4 * (size_t)b] == kAlInfeasible) ++report->reserved[1];
+    }
+  }
   return TOWR_OK;
+}
+
+extern "C" {
+
+int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                        const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                        const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb, double* XL, double* XU,
+                                        int64_t ldxb, int32_t* LOG, towr_solve_report_t* report, void* stream) {
+  return alsolve_solve(h, B, opts, params, nullptr, state, dir, GL, GU, ldgb, XL, XU, ldxb, LOG, report, stream);
+}
+
+int towr_gpu_alsolve_solve_ex_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                           const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                           const towr_alsolve_state_t* state, const towr_solve_dir_t* dir, double* GL, double* GU,
+                                           int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
+                                           towr_solve_report_t* report, void* stream) {
+  return alsolve_solve(h, B, opts, params, stop, state, dir, GL, GU, ldgb, XL, XU, ldxb, LOG, report, stream);
 }
 
 }  // extern "C"

@@ -299,7 +299,9 @@ const void* lbfgs_direction_kernel();
 // The resident AL loop's kernels (towr_gpu.h, towr_alsolve_state_t; all in lbfgs.hip): the line search (it offers the
 // accepted pair with the update kernel's own device code and needs its lbfgs_update_lds(n) bytes), the outer update and
 // the state initialisation; one block of kLbfgsBlock threads per problem. XL / XU / ldb as in StepArgs.
-enum AlPhase : int32_t { kAlRestart = 0, kAlSearch = 1, kAlConverged = 2, kAlStalled = 3, kAlMaxed = 4 };
+enum AlPhase : int32_t {
+  kAlRestart = 0, kAlSearch = 1, kAlConverged = 2, kAlStalled = 3, kAlMaxed = 4, kAlAcceptable = 5, kAlInfeasible = 6
+};
 struct LineSearchArgs {
   towr_alsolve_state_t st;
   const double *XL, *XU; int64_t ldb;
@@ -311,6 +313,15 @@ struct OuterArgs {
   towr_alsolve_params_t pr;
   int32_t m;
 };
+// the stop rule (towr_gpu_alsolve_stop_batch_device): one thread per problem, blocks of kLbfgsBlock over B
+struct StopArgs {
+  int32_t* ISTATE;
+  double* SCAL; int64_t ldsc;
+  double* ALPHA;
+  const double* RHO;
+  towr_alsolve_stop_t sp;
+  int32_t max_inner, B;
+};
 struct AlInitArgs {
   towr_alsolve_state_t st;
   const double *XL, *XU; int64_t ldb;
@@ -319,6 +330,7 @@ struct AlInitArgs {
 };
 const void* linesearch_kernel();
 const void* alsolve_outer_kernel();
+const void* alsolve_stop_kernel();
 const void* alsolve_init_kernel();
 
 // The compacting solve's kernels (towr_gpu_alsolve_solve_batch_device; lbfgs.hip). The partition: one block of

@@ -1,7 +1,7 @@
 // lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
 // and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device); and the kernels of the
-// resident AL loop built on them (the line search, the outer update, the state's initialisation; at the end), with the
-// two kernels of the compacting solve behind those (the partition plan and the row swap).
+// resident AL loop built on them (the line search, the outer update, the stop rule, the state's initialisation; at the
+// end), with the two kernels of the compacting solve behind those (the partition plan and the row swap).
 //
 // The shape of resid.hip and step.hip. One block of kLbfgsBlock threads per problem. Lane l takes columns l,
 // l + kLbfgsBlock, ... in ascending order in every pass, so a column belongs to one lane for the whole kernel: the
@@ -442,6 +442,46 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_outer_kernel(OuterAr
   IS[0] = outer + 1 >= pr.max_outer ? kAlMaxed : kAlRestart;
 }
 
+// The stop rule of the resident AL loop (towr_gpu.h, towr_gpu_alsolve_stop_batch_device), between the line search and
+// the outer update. One thread per problem: it reads the problem's four state words, five scalars and RHO and takes
+// every decision on them; a problem that is not in SEARCH returns before anything is written. IEEE comparisons and one
+// rounded product; every test is written so that a NaN operand makes it false on the stopping side (`within` false
+// resets the run, `!(viol <= eta)` is the outer update's own "not feasible", the three tests of `stuck` are false).
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_stop_kernel(StopArgs a) {
+#pragma clang fp contract(off)
+  const int64_t b = (int64_t)blockIdx.x * kLbfgsBlock + threadIdx.x;
+  if (b >= a.B) return;
+  int32_t* IS = a.ISTATE + 4 * b;
+  if (IS[0] != kAlSearch) return;
+  double* Sc = a.SCAL + b * a.ldsc;
+  const int flags = IS[1], inner = IS[2];
+  const double pg = Sc[1], eta = Sc[2], omega = Sc[3], viol = Sc[4];
+  const towr_alsolve_stop_t& sp = a.sp;
+  if (sp.acc_iters > 0) {
+    const bool within = viol <= sp.acc_eta && pg <= sp.acc_omega;
+    const double run = within ? Sc[6] + 1.0 : 0.0;
+    Sc[6] = run;
+    if (run >= (double)sp.acc_iters) {
+      IS[0] = kAlAcceptable;
+      IS[1] = 0;
+      a.ALPHA[b] = 0.0;
+      return;
+    }
+  }
+  const bool grow = (flags & 1) && (pg <= omega || inner >= a.max_inner) && !(viol <= eta);
+  if (!grow) return;
+  const double last = Sc[7];
+  const double keep = sp.infeas_keep * last;
+  const bool stuck = last > 0.0 && viol >= keep && a.RHO[b] >= sp.infeas_rho;
+  if (stuck) {
+    IS[0] = kAlInfeasible;
+    IS[1] = 0;
+    a.ALPHA[b] = 0.0;
+  } else {
+    Sc[7] = viol;
+  }
+}
+
 __global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_init_kernel(AlInitArgs a) {
 #pragma clang fp contract(off)
   const towr_alsolve_state_t& st = a.st;
@@ -608,6 +648,7 @@ const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_l
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }
 const void* linesearch_kernel() { return reinterpret_cast<const void*>(&towr_linesearch_kernel); }
 const void* alsolve_outer_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_outer_kernel); }
+const void* alsolve_stop_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_stop_kernel); }
 const void* alsolve_init_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_init_kernel); }
 
 }  // namespace tg

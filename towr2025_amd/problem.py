@@ -76,6 +76,13 @@ def alsolve_params(**kw) -> capi.AlSolveParams:
     return capi.AlSolveParams(**{**AL_PARAM_DEFAULTS, **kw})
 
 
+def alsolve_stop_params(acc_eta=0.0, acc_omega=0.0, acc_iters=0, infeas_keep=1.0, infeas_rho=float("inf")) -> capi.AlSolveStop:
+    """towr_alsolve_stop_t: the acceptable rule (acc_iters = 0: off) and the infeasible rule (infeas_rho = inf: off); the
+    defaults switch both off. The C-ABI checks the ranges."""
+    return capi.AlSolveStop(acc_eta=float(acc_eta), acc_omega=float(acc_omega), acc_iters=int(acc_iters), reserved=0,
+                            infeas_keep=float(infeas_keep), infeas_rho=float(infeas_rho))
+
+
 def gn_params(ncg=8, mu=0.0, tol=0.0) -> capi.GnParams:
     """towr_gn_params_t: at most ncg CG steps, the damping mu, the relative residual tolerance tol; the C-ABI checks
     the ranges."""
@@ -653,6 +660,14 @@ class TowrGpuProblem:
         self._check(self._lib.towr_gpu_auglag_outer_batch_device(self._h, st.B, C.byref(params), C.byref(c),
                                                                  self._stream(stream, st.X)))
 
+    def alsolve_stop(self, params, stop, st, stream=None):
+        """The stop rule alone, between the line search and the outer update: a SEARCH problem whose base stayed
+        acceptable for stop.acc_iters iterations becomes ACCEPTABLE, one whose penalty is about to grow again without
+        progress becomes INFEASIBLE (towr_gpu.h; SCAL[6..7] are the rule's memory)."""
+        c = self._alsolve_state(st, params)
+        self._check(self._lib.towr_gpu_alsolve_stop_batch_device(self._h, st.B, C.byref(params), C.byref(stop), C.byref(c),
+                                                                 self._stream(stream, st.X)))
+
     def alsolve_init(self, params, st, XL=None, XU=None, stream=None):
         """Start a solve from st.X (clamped into st.XC) and st.LAM: phases, counters, RHO, ALPHA, tolerances."""
         c = self._alsolve_state(st, params)
@@ -906,14 +921,17 @@ class TowrGpuProblem:
 
     def alsolve_solve(self, params, st, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
                       precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, compact=True,
-                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None):
+                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None):
         """Run the resident loop to completion (towr_gpu.h, towr_gpu_alsolve_solve_batch_device): rounds of check_every
         iterations of the method's iterate entry (capi.SOLVE_*; gn, DC, GSUM, PC / precond, W / wrows as that entry
         takes them), the host looking at the phases once per round, until every problem is frozen or max_iters
         iterations have run. compact: the frozen problems are moved out of the batch between rounds; every array is
         back in the caller's order at return, and the persistent arrays hold the bits of the plain iterate loop. Per-problem
         GL / GU / XL / XU rows are permuted during the call. The call blocks the host. LOG: int32 (>= 8 + 2 B), allocated
-        when None. Returns dict(rounds, iters_run, problem_iters, n_phase (6 counts: phases 0..4, other))."""
+        when None. Returns dict(rounds, iters_run, problem_iters, n_phase (6 counts: phases 0..4, other)). stop (an
+        alsolve_stop_params()): the stop rule runs in every iteration (towr_gpu_alsolve_solve_ex_batch_device) and the
+        dict also holds n_acceptable and n_infeasible, which n_phase[5] includes. ex: whether the call goes through the
+        _ex entry (default: when stop is given); ex=True with stop None passes stop == NULL to it."""
         import torch
         c = self._alsolve_state(st, params)
         B = st.B
@@ -943,10 +961,22 @@ class TowrGpuProblem:
             LOG = torch.zeros(8 + 2 * B, dtype=torch.int32, device=st.X.device)
         opts = capi.SolveOpts(method=int(method), max_iters=int(max_iters), check_every=int(check_every), compact=int(bool(compact)))
         rep = capi.SolveReport()
-        self._check(self._lib.towr_gpu_alsolve_solve_batch_device(
-            self._h, B, C.byref(opts), C.byref(params), C.byref(c), C.byref(d), gl, gu, ldgb, xl, xu, ldxb,
-            self._int_operand(LOG, "LOG", 8 + 2 * B), C.byref(rep), self._stream(stream, st.X)))
-        return dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase))
+        log = self._int_operand(LOG, "LOG", 8 + 2 * B)
+        if not (stop is not None if ex is None else ex):
+            if stop is not None:
+                raise TowrGpuError("alsolve_solve: stop needs the _ex entry (ex=False was given)")
+            self._check(self._lib.towr_gpu_alsolve_solve_batch_device(
+                self._h, B, C.byref(opts), C.byref(params), C.byref(c), C.byref(d), gl, gu, ldgb, xl, xu, ldxb,
+                log, C.byref(rep), self._stream(stream, st.X)))
+            return dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase))
+        self._check(self._lib.towr_gpu_alsolve_solve_ex_batch_device(
+            self._h, B, C.byref(opts), C.byref(params), None if stop is None else C.byref(stop), C.byref(c), C.byref(d),
+            gl, gu, ldgb, xl, xu, ldxb,
+            log, C.byref(rep), self._stream(stream, st.X)))
+        out = dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase))
+        if stop is not None:
+            out.update(n_acceptable=rep.reserved[0], n_infeasible=rep.reserved[1])
+        return out
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
