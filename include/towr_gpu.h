@@ -1118,6 +1118,107 @@ int towr_gpu_alsolve_solve_ex_batch_device(towr_gpu_handle h, int32_t B, const t
                                            double* GU, int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
                                            towr_solve_report_t* report, void* stream);
 
+/* ---- a queue of problems through the resident solve's slots: each leaves when it is done, the next takes its row ---- */
+/* The retire key of a batch: which rows leave their slots. ISTATE as in towr_alsolve_state_t (only the phase word
+ * ISTATE[4 b] is read; NOT WRITTEN), AGE is int32_t[B] (the iterations a row's problem has run), KEY is int32_t[4*B]
+ * (ISTATE's stride; only KEY[4 b] is written); all DEVICE pointers. One thread per row:
+ *   add > 0: AGE[b] += add first (add = 0: AGE is only read);
+ *   KEY[4 b] = (ISTATE[4 b] is 0 or 1) and AGE[b] >= max_age ? 7 : ISTATE[4 b].
+ * towr_gpu_alsolve_partition_batch_device runs on KEY as it does on ISTATE: it treats every word outside {0, 1} as
+ * frozen, and 7 is counted in HEAD[7]. A key and not a phase word, so that a problem that ran out of budget keeps its
+ * RESTART / SEARCH word. Integer compares only. No handle scratch; the kept Jacobian is not dropped. TOWR_ERR_INVALID
+ * before anything runs for a NULL pointer, B < 0 or add < 0.                                                           */
+int towr_gpu_alsolve_retire_key_batch_device(towr_gpu_handle h, int32_t B, const int32_t* ISTATE, int32_t* AGE, int32_t add,
+                                             int32_t max_age, int32_t* KEY, void* stream);
+
+/* Moves rows between slots and arrays indexed by problem: for every i < count and every pair k < n_arrays, bytes
+ * [0, row_bytes) of row r0 + i of slot[k] are copied to row ID[r0 + i] of out[k]; with reverse = 1 from that row of
+ * out[k] into the slot row (out[k] is then only read). ID is a DEVICE pointer (int32_t, rows r0 .. r0 + count - 1 are
+ * read); a negative ID skips its row. `slot` and `out` are HOST memory, read at the call; slot[k] and out[k] state the
+ * same row_bytes. Not one byte beyond row_bytes of any row is read or written. The IDs of a call must be distinct and
+ * index rows every out[k] holds, and slot[k] and out[k] must not share a byte; that is the caller's business. Per side
+ * the swap's rules: row_bytes a positive multiple of 4, base and ld_bytes multiples of 4, ld_bytes >= row_bytes; 8 bytes
+ * move per lane where both bases, both ld_bytes and row_bytes are multiples of 8, else 4. count is a host value; count =
+ * 0 or n_arrays = 0 launches nothing. No handle scratch; the kept Jacobian is not dropped. TOWR_ERR_INVALID before
+ * anything runs for: NULL ID, r0 or count < 0, reverse outside {0, 1}, n_arrays outside 0..TOWR_MOVE_MAX_ARRAYS, NULL slot
+ * or out with n_arrays > 0, two row_bytes that differ, and a descriptor that breaks the rules above.                  */
+#define TOWR_MOVE_MAX_ARRAYS 16
+int towr_gpu_alsolve_move_rows_batch_device(towr_gpu_handle h, const int32_t* ID, int32_t r0, int32_t count,
+                                            int32_t n_arrays, const towr_rows_t* slot, const towr_rows_t* out,
+                                            int32_t reverse, void* stream);
+
+/* A queue of N problems for B slots (host memory, read at the call; the pointers in it are DEVICE pointers).
+ *   Inputs, indexed by problem and only read: X0 (N rows of n at ldx0 >= n), the starting points; LAM0 (N rows of m at
+ *   ldl0 >= m), the starting multipliers, or NULL for zeros; the bounds GL / GU (ldgb) and XL / XU (ldxb): NULL (the
+ *   handle's), a leading dimension of 0 (one row shared by all problems) or > 0 (N per-problem rows). Per-problem bounds
+ *   need slot-side work rows, B of each: GLW / GUW at ldgw >= m, XLW / XUW at ldxw >= n; they are not read otherwise.
+ *   Slot bookkeeping: ID (int32_t[B], the problem in each slot), AGE (int32_t[B], its iterations so far), KEY
+ *   (int32_t[4 B], the retire keys).
+ *   Outputs, indexed by problem: X_OUT (n at ldxo >= n), LAM_OUT (m at ldlo >= m), RHO_OUT[N], SCAL_OUT[8 N],
+ *   ISTATE_OUT[4 N], ITERS_OUT[N] (int32_t).                                                                          */
+typedef struct {
+  int32_t N, reserved;
+  const double* X0; int64_t ldx0;
+  const double* LAM0; int64_t ldl0;
+  const double *GL, *GU; int64_t ldgb;
+  const double *XL, *XU; int64_t ldxb;
+  double *GLW, *GUW; int64_t ldgw;
+  double *XLW, *XUW; int64_t ldxw;
+  int32_t *ID, *AGE, *KEY;
+  double* X_OUT; int64_t ldxo;
+  double* LAM_OUT; int64_t ldlo;
+  double *RHO_OUT, *SCAL_OUT;
+  int32_t *ISTATE_OUT, *ITERS_OUT;
+} towr_solve_queue_t;
+
+/* Solves the N problems of `queue` through B resident slots: a problem leaves its slot when it is frozen or has run
+ * max_iters iterations, and the next problem of the queue takes the freed row. `state`, dir's DC / GSUM / PC / W and the
+ * work rows are sized for B as in the solve entries; their contents at entry do not matter. With K = check_every,
+ * M = max_iters, `next` the queue's cursor and Bcur the live rows (both start at 0), one round, all on `stream`:
+ *   1. admit: c = min(B - Bcur, N - next) problems next .. next + c - 1 into rows [Bcur, Bcur + c): X, LAM (zeros when
+ *      LAM0 is NULL), the per-problem bound rows and the batch terrain are copied in by towr_gpu_alsolve_move_rows_batch_
+ *      device, ID = the problem, AGE = 0; then towr_gpu_alsolve_init_batch_device's launch on exactly those rows;
+ *   2. K iterations of the method's iterate entry on rows [0, Bcur), with the stop rule when `stop` is given, as
+ *      towr_gpu_alsolve_solve_ex_batch_device runs them;
+ *   3. towr_gpu_alsolve_retire_key_batch_device (add = K, max_age = M), towr_gpu_alsolve_partition_batch_device on KEY
+ *      (HEAD = LOG[0..7], the pairs behind it) and towr_gpu_alsolve_swap_rows_batch_device with NP = LOG + 1 on that
+ *      entry's arrays plus ID, AGE, the work rows and the private terrain copy;
+ *   4. a copy of HEAD to page-locked host memory and ONE synchronisation: the round's only host look;
+ *   5. retire: rows [na, Bcur) move out, X, LAM, RHO, SCAL (8) and ISTATE (4) to row ID of the outputs and AGE to
+ *      ITERS_OUT; Bcur = na;
+ *   6. the loop ends when Bcur == 0 and the queue is empty.
+ * THE ENTRY BLOCKS THE HOST: once per round and once before it returns, when all its work on `stream` has finished.
+ *   The contract: for every problem and every B >= 1, X_OUT, LAM_OUT, RHO_OUT, SCAL_OUT and ISTATE_OUT are bit for bit
+ *   the X, LAM, RHO, SCAL and ISTATE that towr_gpu_alsolve_solve_ex_batch_device leaves for that problem with the same
+ *   opts, params, stop and dir, behind towr_gpu_alsolve_init_batch_device, the N problems solved as one batch: problem
+ *   b's outputs are a function of its own operands alone, so neither its slot nor its neighbours nor what an earlier
+ *   tenant left in the slot can change a bit. A problem that ran out of budget keeps its RESTART / SEARCH word.
+ *   ITERS_OUT = K ceil(t / K), t the iteration at which the problem froze, or M. max_iters must be a positive multiple
+ *   of check_every: no problem's last round is cut short, as the solve entry's min(K, M - iters_run) schedule would.
+ *   opts->compact is not read (0 or 1). No padding byte of an output is written; nothing of the inputs is written; rows
+ *   beyond min(N, B) of the slot arrays are not touched. The slot state, DC, GSUM, W, PC, ID, AGE, KEY, LOG and the work
+ *   rows are unspecified at return: nothing is put back in any order. When batch terrains are set
+ *   (towr_gpu_set_batch_terrain) they must number exactly N; the driver keeps a private B-entry copy that travels with
+ *   the rows, and the handle's set is not modified. LOG is int32_t[8 + 2 (B / 2)], DEVICE memory.
+ *   `report`: rounds; iters_run = K rounds; problem_iters = the sum over the rounds of Bcur K (= the sum of ITERS_OUT;
+ *   rounds >= ceil(problem_iters / (B K))); n_phase[0..5] and reserved[0..1] counted over the N rows of ISTATE_OUT as
+ *   the ex entry defines them (reserved = 0 when stop is NULL). N = 0: nothing runs and the report is zero.
+ *   Failure: every argument check passes before anything is queued; if a launch or copy fails, the first error is
+ *   returned and the outputs of the problems not yet retired are unspecified.
+ * Handle scratch, the cross-stream rule and the kept Jacobian as for the iterate entry. TOWR_ERR_INVALID before anything
+ * runs for: NULL opts, dir, queue, LOG or report, a method outside 0..4, check_every < 1, max_iters not a positive
+ * multiple of check_every, compact outside {0, 1}, N < 0, B < 1 with N > 0, with N > 0 (an empty queue names no array)
+ * a NULL X0, ID, AGE, KEY or output, ldx0 or ldxo < n, ldl0 (LAM0 given) or ldlo < m, only one of GL / GU or of XL / XU, a leading dimension of the bounds that is
+ * negative or in (0, m) / (0, n), per-problem bounds without their work rows or with ldgw < m / ldxw < n, everything the
+ * method's iterate entry refuses for B rows, more per-problem arrays than TOWR_SWAP_MAX_ARRAYS, an array that fails the
+ * swap's or the move's checks, and batch terrains set for another number of problems than N. TOWR_ERR_UNSUPPORTED and
+ * TOWR_ERR_NO_DEVICE as for that iterate entry, behind all of these.                                                  */
+int towr_gpu_alsolve_solve_queue_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                              const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                              const towr_alsolve_state_t* state, const towr_solve_dir_t* dir,
+                                              const towr_solve_queue_t* queue, int32_t* LOG, towr_solve_report_t* report,
+                                              void* stream);
+
 /* Launch classes and launches, for roofline accounting. Kernel indices 0..4 are the launch
  * classes: Dynamic, RangeOfMotion, ForceConstraintDiscretized, TorqueConstraintDiscretized and the
  * small kinds (node-value constraints, SplineAcc, BaseMotion, TotalDuration, ...), one kernel each.

@@ -21,6 +21,9 @@ example parameters (ACC_ETA 1e-6, ACC_OMEGA 1e-4, ACC_ITERS 15, INFEAS_KEEP 0.99
 loop, whose iterate entry has no rule; MAX_INNER overrides SOLVE_PAR's 200.
 `stopcost`: the rule's own cost — one round of STOPCOST_ITERS (default 20) iterations on all B ANYmal problems (default
 4096), compact = 0, with and without the rule, alternated, per iteration.
+QUEUE=1: towr_gpu_alsolve_solve_queue_batch_device (queue_run below): N starts (N_MONOPED default 16384, N default 2048
+for ANYmal) through B slots (B_MONOPED 4096, B 512) with K = the first of KS, beside N / B successive compact = 1 solves of B
+and one compact = 1 solve of all N (ALL_AT_ONCE=0 leaves it out); STOP, FEASIBLE and MAX_ITERS as above.
 usage: python tools/solve_timing.py [anymal|monoped|all|stopcost]"""
 import ctypes as C
 import os
@@ -185,8 +188,122 @@ def stop_cost(p, B):
           f"{max(times['with']):.4f}), difference {1e3 * (b - a):.1f} us", flush=True)
 
 
+def queue_run(title, p, N, B, K):
+    """QUEUE=1: N starts through B slots (q) beside what the solve entry can do in the same memory, N / B successive
+    compact = 1 solves of B starts each (s), and beside one compact = 1 solve of all N where its state fits (a); and (q0, s0)
+    a run of 2 K iterations on B starts, where nothing freezes, for the queue's overhead per round. Every window holds the
+    whole job from the starts on the device to the results on the device: the copies in, alsolve_init, the solve, the copies
+    out."""
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    n, m, mem = p.n, p.m, SOLVE_PAR["mem"]
+    par, gn = alsolve_params(**SOLVE_PAR), gn_params(mu=MU)
+    stop = stop_params() if STOP else None
+    x0 = p.initial_x()
+    X0 = torch.from_numpy(np.stack([x0 + 0.05 * np.random.default_rng(SEED + b).standard_normal(n) for b in range(N)])).to(dev)
+    ldw = p.gn_tile_info()["ldw_min"]
+
+    def slots(rows):
+        st = AlSolveState.allocate(p, rows, mem)
+        return dict(st=st, DC=torch.zeros_like(st.X), GS=torch.zeros((rows, 8), dtype=torch.float64, device=dev),
+                    W=torch.empty((rows, ldw), dtype=torch.float64, device=dev),
+                    LOG=torch.zeros(8 + 2 * rows, dtype=torch.int32, device=dev))
+
+    def outputs():
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+        i = lambda k: torch.zeros(k, dtype=torch.int32, device=dev)
+        return dict(X_OUT=z(N, n), LAM_OUT=z(N, m), RHO_OUT=z(N), SCAL_OUT=z(N, 8), ISTATE_OUT=i(4 * N), ITERS_OUT=i(N))
+
+    sB = slots(B)
+    out_q, out_s, out_a = outputs(), outputs(), outputs()
+    book = dict(ID=torch.zeros(B, dtype=torch.int32, device=dev), AGE=torch.zeros(B, dtype=torch.int32, device=dev),
+                KEY=torch.zeros(4 * B, dtype=torch.int32, device=dev))
+
+    def queue(count=N, M=MAX_ITERS):
+        r = p.alsolve_solve_queue(par, sB["st"], X0[:count], method=capi.SOLVE_GN_TILED, gn=gn, DC=sB["DC"], GSUM=sB["GS"], W=sB["W"],
+                                  wrows=B, max_iters=M, check_every=K, LOG=sB["LOG"], stream=stream, stop=stop,
+                                  out={k: t[:count * (4 if k == "ISTATE_OUT" else 1)] for k, t in out_q.items()}, **book)
+        return {k: r[k] for k in ("rounds", "iters_run", "problem_iters", "n_phase")}
+
+    def solve(s, lo, hi, out, M=MAX_ITERS):
+        st = s["st"]
+        st.X[:hi - lo].copy_(X0[lo:hi])
+        st.LAM.zero_()
+        p.alsolve_init(par, st, stream=stream)
+        r = p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=s["DC"], GSUM=s["GS"], W=s["W"], wrows=st.B, max_iters=M,
+                            check_every=K, compact=True, LOG=s["LOG"], stream=stream, stop=stop, ex=True)
+        out["X_OUT"][lo:hi].copy_(st.X)
+        out["LAM_OUT"][lo:hi].copy_(st.LAM)
+        out["RHO_OUT"][lo:hi].copy_(st.RHO)
+        out["SCAL_OUT"][lo:hi].copy_(st.SCAL)
+        out["ISTATE_OUT"][4 * lo:4 * hi].copy_(st.ISTATE)
+        return r
+
+    def successive():
+        tot = dict(rounds=0, iters_run=0, problem_iters=0, n_phase=[0] * 6)
+        for lo in range(0, N, B):
+            r = solve(sB, lo, lo + B, out_s)
+            tot = dict(rounds=tot["rounds"] + r["rounds"], iters_run=tot["iters_run"] + r["iters_run"],
+                       problem_iters=tot["problem_iters"] + r["problem_iters"],
+                       n_phase=[a + b for a, b in zip(tot["n_phase"], r["n_phase"])])
+        return tot
+
+    assert N % B == 0, "N must be a multiple of B"
+    variants = [(f"q  queue N={N} through B={B}", queue), (f"s  {N // B} solves of B={B}", successive)]
+    if os.environ.get("ALL_AT_ONCE", "1") == "1":
+        try:
+            sN = slots(N)
+            variants.append((f"a  one solve of N={N}", lambda: solve(sN, 0, N, out_a)))
+        except RuntimeError as e:           # (the state of all N does not fit)
+            print(f"  one solve of N={N}: not run ({str(e).splitlines()[0]})", flush=True)
+    variants += [(f"q0 queue N=B={B}, {2 * K} iterations", lambda: queue(B, 2 * K)),
+                 (f"s0 solve B={B}, {2 * K} iterations", lambda: solve(sB, 0, B, out_s, 2 * K))]
+    reports, times = {}, {name: [] for name, _ in variants}
+    same = None
+    for name, fn in variants:               # warm-up: every variant once
+        reports[name] = fn()
+        torch.cuda.synchronize()
+        if name == variants[1][0]:          # (before q0 / s0 write their rows of the outputs)
+            same = all(torch.equal(out_q[k], out_s[k]) if out_q[k].dtype == torch.int32 else
+                       torch.equal(out_q[k].view(torch.int64), out_s[k].view(torch.int64)) for k in out_s if k != "ITERS_OUT")
+    for _ in range(ROUNDS):
+        for name, fn in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append(1e3 * (time.perf_counter() - t0))
+    print(f"{title} QUEUE: N={N} B={B} K={K} n={n} m={m} mu={MU} max_iters={MAX_ITERS} max_inner={SOLVE_PAR['max_inner']} "
+          f"rounds={ROUNDS} stop={'on' if STOP else 'off'}", flush=True)
+    med = {}
+    for name, _ in variants:
+        t, r = times[name], reports[name]
+        med[name] = statistics.median(t)
+        rows = B if name[0] in "qs" else N
+        print(f"  {name:40s} {med[name]:9.2f} ms  (min {min(t):.2f} max {max(t):.2f})  rounds {r['rounds']} problem_iters "
+              f"{r['problem_iters']} occupancy {r['problem_iters'] / max(r['rounds'] * K * rows, 1):.3f} phases 0..4,other {r['n_phase']}",
+              flush=True)
+    q, s = variants[0][0], variants[1][0]
+    q0, s0 = variants[-2][0], variants[-1][0]
+    print(f"  time q / s {med[q] / med[s]:.3f}" + (f", q / a {med[q] / med[variants[2][0]]:.3f}" if len(variants) == 5 else "")
+          + f"; outputs bit-equal q vs s: {same}; nothing freezes: q0 - s0 = {1e3 * (med[q0] - med[s0]):.0f} us over "
+          f"{reports[q0]['rounds']} rounds = {1e3 * (med[q0] - med[s0]) / max(reports[q0]['rounds'], 1):.0f} us per round", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "anymal"
+    if os.environ.get("QUEUE", "0") == "1":
+        K = KS[0]
+        if which in ("monoped", "all"):
+            f, vs, cs, goal, T = F.procedural_monoped()
+            vb = f.var_bounds_data(varsets=vs, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)
+            queue_run("monoped_procedural", TowrGpuProblem(F.procedural_desc(), device=0, data=vb),
+                      int(os.environ.get("N_MONOPED", "16384")), int(os.environ.get("B_MONOPED", "4096")), K)
+        if which in ("anymal", "all"):
+            queue_run("anymal_trot_feasible" if FEASIBLE else "anymal_trot", anymal(), int(os.environ.get("N", "2048")),
+                      int(os.environ.get("B", "512")), K)
+        sys.exit(0)
     if which == "stopcost":
         stop_cost(anymal(), int(os.environ.get("B", "4096")))
     if which in ("anymal", "all"):

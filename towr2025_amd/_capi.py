@@ -134,6 +134,20 @@ class SolveReport(C.Structure):   # towr_solve_report_t
                 ("n_phase", C.c_int32 * 6), ("reserved", C.c_int32 * 2)]
 
 
+MOVE_MAX_ARRAYS = 16   # TOWR_MOVE_MAX_ARRAYS
+
+
+class SolveQueue(C.Structure):   # towr_solve_queue_t
+    _fields_ = [("N", C.c_int32), ("reserved", C.c_int32), ("X0", C.c_void_p), ("ldx0", C.c_int64),
+                ("LAM0", C.c_void_p), ("ldl0", C.c_int64), ("GL", C.c_void_p), ("GU", C.c_void_p), ("ldgb", C.c_int64),
+                ("XL", C.c_void_p), ("XU", C.c_void_p), ("ldxb", C.c_int64),
+                ("GLW", C.c_void_p), ("GUW", C.c_void_p), ("ldgw", C.c_int64),
+                ("XLW", C.c_void_p), ("XUW", C.c_void_p), ("ldxw", C.c_int64),
+                ("ID", C.c_void_p), ("AGE", C.c_void_p), ("KEY", C.c_void_p),
+                ("X_OUT", C.c_void_p), ("ldxo", C.c_int64), ("LAM_OUT", C.c_void_p), ("ldlo", C.c_int64),
+                ("RHO_OUT", C.c_void_p), ("SCAL_OUT", C.c_void_p), ("ISTATE_OUT", C.c_void_p), ("ITERS_OUT", C.c_void_p)]
+
+
 class CostDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("ee", C.c_int32), ("weight", C.c_double), ("dt", C.c_double),
                 ("p", C.c_double * 4), ("ip", C.c_int32 * 4)]
@@ -310,6 +324,13 @@ SYMBOLS = {
                                                           C.POINTER(AlSolveStop), C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
                                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                           C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
+    "towr_gpu_alsolve_retire_key_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                            C.c_void_p, C.c_void_p]),
+    "towr_gpu_alsolve_move_rows_batch_device": (C.c_int, [_HANDLE, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.POINTER(Rows), C.POINTER(Rows), C.c_int32, C.c_void_p]),
+    "towr_gpu_alsolve_solve_queue_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(SolveOpts), C.POINTER(AlSolveParams),
+                                                             C.POINTER(AlSolveStop), C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
+                                                             C.POINTER(SolveQueue), C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
     "towr_gpu_kernel_info": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(C.c_char_p), _IP, _LP]),
     "towr_gpu_eval_batch_device_kernel": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

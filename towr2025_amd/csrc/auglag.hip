@@ -1097,20 +1097,26 @@ static int alsolve_args(towr_gpu_handle h, int32_t B, const towr_alsolve_params_
   return box_args(h, XL, XU, ldxb, h->L.n, "XL / XU", "n");
 }
 
+// the initialisation's launch on the B rows of `st` (behind its checks and bind; the queued solve runs it per admission)
+static int launch_alsolve_init(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const towr_alsolve_state_t& st,
+                               const double* XL, const double* XU, int64_t ldxb, hipStream_t s) {
+  if (B == 0) return TOWR_OK;
+  if (!XL)
+    if (int rc = step_ready(h)) return rc;
+  AlInitArgs a{st, XL, XU, ldxb, p.rho0, p.eta0, p.omega0, h->L.n};
+  if (!a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_init_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
 int towr_gpu_alsolve_init_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
                                        const towr_alsolve_state_t* state, const double* XL, const double* XU, int64_t ldxb,
                                        void* stream) {
   if (int rc = alsolve_args(h, B, params, state, nullptr, nullptr, 0, XL, XU, ldxb)) return rc;
   if (int rc = bind(h)) return rc;
   if (int rc = lbfgs_fits(h)) return rc;
-  if (B == 0) return TOWR_OK;
-  if (!XL)
-    if (int rc = step_ready(h)) return rc;
-  AlInitArgs a{*state, XL, XU, ldxb, params->rho0, params->eta0, params->omega0, h->L.n};
-  if (!a.XL) { a.XL = h->al.d_xlo; a.XU = h->al.d_xup; a.ldb = 0; }
-  void* args[] = {&a};
-  HIPCHK(h, launch_kernel(alsolve_init_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, reinterpret_cast<hipStream_t>(stream)));
-  return TOWR_OK;
+  return launch_alsolve_init(h, B, *params, *state, XL, XU, ldxb, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Per iteration what the six public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag
@@ -1442,6 +1448,65 @@ static int launch_swap_rows(towr_gpu_handle h, const int32_t* NP, int pairs, con
   return TOWR_OK;
 }
 
+// what the move refuses of its descriptor pairs (the swap's rules for either side; a pair shares one row length)
+static int move_rows_args(towr_gpu_handle h, int32_t n_arrays, const towr_rows_t* slot, const towr_rows_t* out) {
+  if (n_arrays < 0 || n_arrays > TOWR_MOVE_MAX_ARRAYS) return fail(h, TOWR_ERR_INVALID, "move: n_arrays outside 0..TOWR_MOVE_MAX_ARRAYS");
+  if (n_arrays > 0 && (!slot || !out)) return fail(h, TOWR_ERR_INVALID, "move: null slot or out descriptors");
+  for (int k = 0; k < n_arrays; ++k) {
+    const std::string pair = "move: pair " + std::to_string(k) + ": ";
+    if (slot[k].row_bytes != out[k].row_bytes) return fail(h, TOWR_ERR_INVALID, pair + "the two row_bytes differ");
+    if (slot[k].row_bytes <= 0 || (slot[k].row_bytes & 3)) return fail(h, TOWR_ERR_INVALID, pair + "row_bytes is not a positive multiple of 4");
+    for (const towr_rows_t* r : {&slot[k], &out[k]}) {
+      if (!r->base || (reinterpret_cast<uintptr_t>(r->base) & 3)) return fail(h, TOWR_ERR_INVALID, pair + "base is NULL or not a multiple of 4");
+      if (r->ld_bytes <= 0 || (r->ld_bytes & 3)) return fail(h, TOWR_ERR_INVALID, pair + "ld_bytes is not a positive multiple of 4");
+      if (r->ld_bytes < r->row_bytes) return fail(h, TOWR_ERR_INVALID, pair + "ld_bytes smaller than row_bytes");
+    }
+  }
+  return TOWR_OK;
+}
+
+// (add: AGE += add before the compare; after the entry's checks)
+static int launch_retire_key(towr_gpu_handle h, int B, const int32_t* ISTATE, int32_t* AGE, int32_t* KEY, int add, int max_age,
+                             hipStream_t s) {
+  if (B == 0) return TOWR_OK;
+  RetireKeyArgs a{ISTATE, AGE, KEY, B, add, max_age, 0};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_retire_key_kernel(), dim3((unsigned)((B + kLbfgsBlock - 1) / kLbfgsBlock)), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+// (after move_rows_args)
+static int launch_move_rows(towr_gpu_handle h, const int32_t* ID, int r0, int count, int n_arrays, const towr_rows_t* slot,
+                            const towr_rows_t* out, bool reverse, hipStream_t s) {
+  if (count == 0 || n_arrays == 0) return TOWR_OK;
+  MoveRowsArgs a{};
+  a.ID = ID; a.r0 = r0; a.count = count; a.n_arrays = n_arrays; a.reverse = reverse ? 1 : 0;
+  for (int k = 0; k < n_arrays; ++k)
+    a.rows[k] = MoveRows{static_cast<char*>(slot[k].base), slot[k].ld_bytes, static_cast<char*>(out[k].base), out[k].ld_bytes,
+                         slot[k].row_bytes};
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_move_rows_kernel(), dim3((unsigned)count, (unsigned)n_arrays), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
+int towr_gpu_alsolve_retire_key_batch_device(towr_gpu_handle h, int32_t B, const int32_t* ISTATE, int32_t* AGE, int32_t add,
+                                             int32_t max_age, int32_t* KEY, void* stream) {
+  if (!h || B < 0 || !ISTATE || !AGE || !KEY) return fail(h, TOWR_ERR_INVALID, "bad argument (null ISTATE, AGE or KEY, or B < 0)");
+  if (add < 0) return fail(h, TOWR_ERR_INVALID, "retire key: add is negative");
+  if (int rc = bind(h)) return rc;
+  return launch_retire_key(h, B, ISTATE, AGE, KEY, add, max_age, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_alsolve_move_rows_batch_device(towr_gpu_handle h, const int32_t* ID, int32_t r0, int32_t count, int32_t n_arrays,
+                                            const towr_rows_t* slot, const towr_rows_t* out, int32_t reverse, void* stream) {
+  if (!h || !ID) return fail(h, TOWR_ERR_INVALID, "bad argument (null ID)");
+  if (r0 < 0 || count < 0) return fail(h, TOWR_ERR_INVALID, "move: negative r0 or count");
+  if (reverse != 0 && reverse != 1) return fail(h, TOWR_ERR_INVALID, "move: reverse outside {0, 1}");
+  if (int rc = move_rows_args(h, n_arrays, slot, out)) return rc;
+  if (int rc = bind(h)) return rc;
+  return launch_move_rows(h, ID, r0, count, n_arrays, slot, out, reverse == 1, reinterpret_cast<hipStream_t>(stream));
+}
+
 int towr_gpu_alsolve_partition_batch_device(towr_gpu_handle h, int32_t B, const int32_t* ISTATE, int32_t* HEAD, int32_t* PAIRS,
                                             void* stream) {
   if (!h || B < 0 || !ISTATE || !HEAD || !PAIRS) return fail(h, TOWR_ERR_INVALID, "bad argument (null ISTATE, HEAD or PAIRS, or B < 0)");
@@ -1459,6 +1524,29 @@ int towr_gpu_alsolve_swap_rows_batch_device(towr_gpu_handle h, const int32_t* NP
 }
 
 }  // extern "C"
+
+// The per-problem rows of the state and of the method's direction (towr_gpu.h lists them with their used widths), in the
+// order both solve drivers exchange them: add(base, ld_bytes, row_bytes).
+template <class Add>
+static void solve_state_rows(const Layout& L, const towr_alsolve_params_t& par, const towr_alsolve_state_t& st,
+                             const towr_solve_dir_t& dir, int method, Add add) {
+  for (double* p : {st.X, st.GR, st.XC, st.GRC, st.D}) add(p, 8 * st.ldx, 8 * (int64_t)L.n);
+  for (double* p : {st.LAM, st.LAMP}) add(p, 8 * st.ldl, 8 * (int64_t)L.m);
+  for (double* p : {st.HS, st.HY}) add(p, 8 * par.mem * st.ldh, 8 * ((par.mem - 1) * st.ldh + L.n));
+  add(st.HMETA, 8, 8);
+  for (double* p : {st.ALPHA, st.RHO, st.FC}) add(p, 8, 8);
+  add(st.SCAL, 8 * st.ldsc, 64);
+  add(st.ISTATE, 16, 16);
+  add(st.RSUM, 8 * st.ldrs, 8 * (4 + (int64_t)L.cons.size()));
+  add(st.SSUM, 8 * st.ldss, 8 * (5 + (int64_t)L.varsets.size()));
+  add(st.DSUM, 8 * st.ldds, 40);
+  add(st.USUM, 8 * st.ldus, 48);
+  add(st.LSUM, 8 * st.ldls, 64);
+  if (method != TOWR_SOLVE_LBFGS) {
+    add(dir.DC, 8 * st.ldx, 8 * (int64_t)L.n);
+    add(dir.GSUM, 8 * dir.ldgs, method == TOWR_SOLVE_GN ? 48 : 64);
+  }
+}
 
 // both solve entries; stop NULL: the plain loop and the plain report
 static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts, const towr_alsolve_params_t* params,
@@ -1497,22 +1585,7 @@ static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* 
   auto add = [&](void* base, int64_t ld_bytes, int64_t row_bytes) {   // (n or m = 0: nothing to exchange)
     if (row_bytes > 0) rows[nr++] = towr_rows_t{base, ld_bytes, row_bytes};
   };
-  for (double* p : {st.X, st.GR, st.XC, st.GRC, st.D}) add(p, 8 * st.ldx, 8 * (int64_t)L.n);
-  for (double* p : {st.LAM, st.LAMP}) add(p, 8 * st.ldl, 8 * (int64_t)L.m);
-  for (double* p : {st.HS, st.HY}) add(p, 8 * params->mem * st.ldh, 8 * ((params->mem - 1) * st.ldh + L.n));
-  add(st.HMETA, 8, 8);
-  for (double* p : {st.ALPHA, st.RHO, st.FC}) add(p, 8, 8);
-  add(st.SCAL, 8 * st.ldsc, 64);
-  add(st.ISTATE, 16, 16);
-  add(st.RSUM, 8 * st.ldrs, 8 * (4 + (int64_t)L.cons.size()));
-  add(st.SSUM, 8 * st.ldss, 8 * (5 + (int64_t)L.varsets.size()));
-  add(st.DSUM, 8 * st.ldds, 40);
-  add(st.USUM, 8 * st.ldus, 48);
-  add(st.LSUM, 8 * st.ldls, 64);
-  if (gn) {
-    add(dir->DC, 8 * st.ldx, 8 * (int64_t)L.n);
-    add(dir->GSUM, 8 * dir->ldgs, method == TOWR_SOLVE_GN ? 48 : 64);
-  }
+  solve_state_rows(L, *params, st, *dir, method, add);
   if (GL && ldgb > 0) for (double* p : {GL, GU}) add(p, 8 * ldgb, 8 * (int64_t)L.m);
   if (XL && ldxb > 0) for (double* p : {XL, XU}) add(p, 8 * ldxb, 8 * (int64_t)L.n);
   if (int rc = swap_rows_args(h, nr, rows)) return rc;
@@ -1591,7 +1664,197 @@ static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* 
   return TOWR_OK;
 }
 
+// ---- a queue of problems through the resident solve's slots ----------------------------------------------------------------
+// the state's rows from row r on
+static towr_alsolve_state_t state_from_row(const towr_alsolve_state_t& s, int r, int mem) {
+  towr_alsolve_state_t o = s;
+  const int64_t b = r;
+  for (double** p : {&o.X, &o.GR, &o.XC, &o.GRC, &o.D}) *p += b * s.ldx;
+  for (double** p : {&o.LAM, &o.LAMP}) *p += b * s.ldl;
+  for (double** p : {&o.HS, &o.HY}) *p += b * mem * s.ldh;
+  o.HMETA += 2 * b;
+  for (double** p : {&o.ALPHA, &o.RHO, &o.FC}) *p += b;
+  o.SCAL += b * s.ldsc;
+  o.ISTATE += 4 * b;
+  o.RSUM += b * s.ldrs;
+  o.SSUM += b * s.ldss;
+  o.DSUM += b * s.ldds;
+  o.USUM += b * s.ldus;
+  o.LSUM += b * s.ldls;
+  return o;
+}
+
+// Rounds of admit / iterate / key, partition and swap / one host look / retire (towr_gpu.h). The frozen and the expired
+// rows are swapped behind the live ones in every round and moved out from there; the variant that retires in place and
+// admits into the holes was not built.
+static int alsolve_solve_queue(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts, const towr_alsolve_params_t* params,
+                               const towr_alsolve_stop_t* stop, const towr_alsolve_state_t* state, const towr_solve_dir_t* dir,
+                               const towr_solve_queue_t* queue, int32_t* LOG, towr_solve_report_t* report, void* stream) {
+  if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
+  if (!opts || !dir || !queue || !LOG || !report) return fail(h, TOWR_ERR_INVALID, "queue: null opts, dir, queue, LOG or report");
+  if (opts->method < TOWR_SOLVE_LBFGS || opts->method > TOWR_SOLVE_GN_TILED) return fail(h, TOWR_ERR_INVALID, "queue: method outside 0..4");
+  if (opts->check_every < 1) return fail(h, TOWR_ERR_INVALID, "queue: check_every must be >= 1");
+  if (opts->max_iters < 1 || opts->max_iters % opts->check_every != 0)
+    return fail(h, TOWR_ERR_INVALID, "queue: max_iters must be a positive multiple of check_every");
+  if (opts->compact != 0 && opts->compact != 1) return fail(h, TOWR_ERR_INVALID, "queue: compact outside {0, 1} (it is not read)");
+  const towr_solve_queue_t& q = *queue;
+  const int N = q.N, K = opts->check_every, M = opts->max_iters, method = opts->method;
+  if (N < 0) return fail(h, TOWR_ERR_INVALID, "queue: N is negative");
+  if (N > 0 && B < 1) return fail(h, TOWR_ERR_INVALID, "queue: N problems need B >= 1 slots");
+  const int64_t n = h->L.n, m = h->L.m;
+  if (N > 0 && (!q.X0 || !q.ID || !q.AGE || !q.KEY || !q.X_OUT || (!q.LAM_OUT && m > 0) || !q.RHO_OUT || !q.SCAL_OUT || !q.ISTATE_OUT || !q.ITERS_OUT))
+    return fail(h, TOWR_ERR_INVALID, "queue: null X0, ID, AGE, KEY, X_OUT, LAM_OUT, RHO_OUT, SCAL_OUT, ISTATE_OUT or ITERS_OUT");
+  if (N > 0 && (q.ldx0 < n || q.ldxo < n)) return fail(h, TOWR_ERR_INVALID, "queue: ldx0 or ldxo below n");
+  if (N > 0 && ((q.LAM0 && q.ldl0 < m) || q.ldlo < m)) return fail(h, TOWR_ERR_INVALID, "queue: ldl0 or ldlo below m");
+  if (int rc = box_args(h, q.GL, q.GU, q.ldgb, m, "queue: GL / GU", "m")) return rc;
+  if (int rc = box_args(h, q.XL, q.XU, q.ldxb, n, "queue: XL / XU", "n")) return rc;
+  const bool per_g = q.GL && q.ldgb > 0, per_x = q.XL && q.ldxb > 0;
+  if (per_g && (!q.GLW || !q.GUW || q.ldgw < m)) return fail(h, TOWR_ERR_INVALID, "queue: per-problem GL / GU need the work rows GLW, GUW (ldgw >= m)");
+  if (per_x && (!q.XLW || !q.XUW || q.ldxw < n)) return fail(h, TOWR_ERR_INVALID, "queue: per-problem XL / XU need the work rows XLW, XUW (ldxw >= n)");
+  // the bounds the launches see: the slot-side work rows, or the shared row / the handle's as they are
+  double* GL = per_g ? q.GLW : const_cast<double*>(q.GL);
+  double* GU = per_g ? q.GUW : const_cast<double*>(q.GU);
+  double* XL = per_x ? q.XLW : const_cast<double*>(q.XL);
+  double* XU = per_x ? q.XUW : const_cast<double*>(q.XU);
+  const int64_t ldgb = per_g ? q.ldgw : 0, ldxb = per_x ? q.ldxw : 0;
+  const bool gn = method != TOWR_SOLVE_LBFGS;
+  const GnWorkspace ws{dir->W, dir->ldw, dir->wrows, method == TOWR_SOLVE_GN_TILED};
+  auto iterate = [&](int Bc, int iters, const towr_terrain_t* ter) -> int {   // (alsolve_solve's)
+    if (!gn) return alsolve_lbfgs_iterate(h, Bc, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream, ter, stop);
+    const bool pc = method == TOWR_SOLVE_GN_PC;
+    return alsolve_gn_iterate(h, Bc, iters, params, state, dir->gn, dir->DC, dir->GSUM, dir->ldgs, pc,
+                              pc ? dir->precond : (int32_t)TOWR_GN_PC_NONE, pc ? dir->PC : nullptr, GL, GU, ldgb, XL, XU, ldxb, stream,
+                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter, stop);
+  };
+  // the iterate entry's refusals for B slots (iters = 0 queues nothing and does not look at the batch terrains' count)
+  const int pre = iterate(B, 0, nullptr);
+  if (pre == TOWR_ERR_INVALID) return pre;
+  if (h->d_bterrain && h->bterrain_n != N)
+    return fail(h, TOWR_ERR_INVALID, "batch terrains are set for " + std::to_string(h->bterrain_n) + " problems, the queue holds " +
+                                         std::to_string(N));
+  if (N == 0) {   // (an empty queue names no arrays)
+    if (pre != TOWR_OK) return pre;
+    *report = towr_solve_report_t{};
+    return TOWR_OK;
+  }
+  const Layout& L = h->L;
+  const towr_alsolve_state_t& st = *state;
+  towr_rows_t rows[TOWR_SWAP_MAX_ARRAYS + 8];
+  int nr = 0;
+  auto add = [&](void* base, int64_t ld_bytes, int64_t row_bytes) {
+    if (row_bytes > 0 && nr < TOWR_SWAP_MAX_ARRAYS + 8) rows[nr++] = towr_rows_t{base, ld_bytes, row_bytes};
+  };
+  solve_state_rows(L, *params, st, *dir, method, add);
+  add(q.ID, 4, 4);
+  add(q.AGE, 4, 4);
+  if (per_g) for (double* p : {GL, GU}) add(p, 8 * ldgb, 8 * m);
+  if (per_x) for (double* p : {XL, XU}) add(p, 8 * ldxb, 8 * n);
+  const int ter_rows = h->d_bterrain ? 1 : 0;
+  if (nr + ter_rows > TOWR_SWAP_MAX_ARRAYS) return fail(h, TOWR_ERR_INVALID, "queue: more per-problem arrays than TOWR_SWAP_MAX_ARRAYS");
+  if (int rc = swap_rows_args(h, nr, rows)) return rc;
+  // the moves: what admission gathers by ID (the queue's side is only read) and what retirement scatters
+  towr_rows_t in_slot[TOWR_MOVE_MAX_ARRAYS], in_src[TOWR_MOVE_MAX_ARRAYS], out_slot[TOWR_MOVE_MAX_ARRAYS], out_dst[TOWR_MOVE_MAX_ARRAYS];
+  int n_in = 0, n_out = 0;
+  auto admit = [&](void* slot, int64_t slot_ld, const void* src, int64_t src_ld, int64_t row_bytes) {
+    if (row_bytes <= 0) return;
+    in_slot[n_in] = towr_rows_t{slot, slot_ld, row_bytes};
+    in_src[n_in++] = towr_rows_t{const_cast<void*>(src), src_ld, row_bytes};
+  };
+  auto retire = [&](void* slot, int64_t slot_ld, void* dst, int64_t dst_ld, int64_t row_bytes) {
+    if (row_bytes <= 0) return;
+    out_slot[n_out] = towr_rows_t{slot, slot_ld, row_bytes};
+    out_dst[n_out++] = towr_rows_t{dst, dst_ld, row_bytes};
+  };
+  admit(st.X, 8 * st.ldx, q.X0, 8 * q.ldx0, 8 * n);
+  if (q.LAM0) admit(st.LAM, 8 * st.ldl, q.LAM0, 8 * q.ldl0, 8 * m);
+  if (per_g) { admit(GL, 8 * ldgb, q.GL, 8 * q.ldgb, 8 * m); admit(GU, 8 * ldgb, q.GU, 8 * q.ldgb, 8 * m); }
+  if (per_x) { admit(XL, 8 * ldxb, q.XL, 8 * q.ldxb, 8 * n); admit(XU, 8 * ldxb, q.XU, 8 * q.ldxb, 8 * n); }
+  retire(st.X, 8 * st.ldx, q.X_OUT, 8 * q.ldxo, 8 * n);
+  retire(st.LAM, 8 * st.ldl, q.LAM_OUT, 8 * q.ldlo, 8 * m);
+  retire(st.RHO, 8, q.RHO_OUT, 8, 8);
+  retire(st.SCAL, 8 * st.ldsc, q.SCAL_OUT, 64, 64);
+  retire(st.ISTATE, 16, q.ISTATE_OUT, 16, 16);
+  retire(q.AGE, 4, q.ITERS_OUT, 4, 4);
+  if (int rc = move_rows_args(h, n_in, in_slot, in_src)) return rc;
+  if (int rc = move_rows_args(h, n_out, out_slot, out_dst)) return rc;
+  if (pre != TOWR_OK) return pre;
+
+  *report = towr_solve_report_t{};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  towr_gpu_handle_s::AugLag& al = h->al;
+  if (!al.h_head) HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&al.h_head), 8 * sizeof(int32_t), hipHostMallocDefault));
+  towr_terrain_t* ter = nullptr;   // the slots' terrains: gathered at admission, exchanged with the rows
+  if (h->d_bterrain) {
+    HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&ter), sizeof(towr_terrain_t) * (size_t)B));
+    static_assert(sizeof(towr_terrain_t) % 8 == 0, "a terrain is moved as 8-byte words");
+    add(ter, sizeof(towr_terrain_t), sizeof(towr_terrain_t));
+    admit(ter, sizeof(towr_terrain_t), h->d_bterrain, sizeof(towr_terrain_t), sizeof(towr_terrain_t));
+  }
+  std::vector<int32_t> ids((size_t)N);   // (pageable: the copies below are staged before they return)
+  for (int i = 0; i < N; ++i) ids[(size_t)i] = i;
+  auto hip = [&](hipError_t e, const char* what) -> int {
+    return e == hipSuccess ? TOWR_OK : fail(h, TOWR_ERR_HIP, std::string("queue: ") + what + " failed: " + hipGetErrorString(e));
+  };
+
+  int32_t* pairs = LOG + 8;
+  int64_t problem_iters = 0;
+  int rounds = 0, Bcur = 0, next = 0, rc = TOWR_OK;
+  while (rc == TOWR_OK) {
+    const int c = std::min(B - Bcur, N - next);
+    if (c > 0) {   // admit problems next .. next + c - 1 into rows [Bcur, Bcur + c)
+      rc = hip(hipMemcpyAsync(q.ID + Bcur, ids.data() + next, sizeof(int32_t) * (size_t)c, hipMemcpyHostToDevice, s), "writing ID");
+      if (rc == TOWR_OK) rc = hip(hipMemsetAsync(q.AGE + Bcur, 0, sizeof(int32_t) * (size_t)c, s), "clearing AGE");
+      if (rc == TOWR_OK && !q.LAM0 && m > 0)
+        rc = hip(hipMemset2DAsync(st.LAM + (int64_t)Bcur * st.ldl, 8 * (size_t)st.ldl, 0, 8 * (size_t)m, (size_t)c, s), "clearing LAM");
+      if (rc == TOWR_OK) rc = launch_move_rows(h, q.ID, Bcur, c, n_in, in_slot, in_src, true, s);
+      if (rc == TOWR_OK)
+        rc = launch_alsolve_init(h, c, *params, state_from_row(st, Bcur, params->mem), row_at(XL, Bcur, ldxb), row_at(XU, Bcur, ldxb),
+                                 ldxb, s);
+      if (rc != TOWR_OK) break;
+      Bcur += c;
+      next += c;
+    }
+    if (Bcur == 0) break;   // (next == N)
+    rc = iterate(Bcur, K, ter);
+    if (rc == TOWR_OK) rc = launch_retire_key(h, Bcur, st.ISTATE, q.AGE, q.KEY, K, M, s);
+    if (rc == TOWR_OK) rc = launch_partition(h, Bcur, q.KEY, LOG, pairs, s);
+    if (rc == TOWR_OK) rc = launch_swap_rows(h, LOG + 1, Bcur / 2, pairs, nr, rows, s);
+    if (rc == TOWR_OK) rc = hip(hipMemcpyAsync(al.h_head, LOG, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s), "copying HEAD");
+    if (rc == TOWR_OK) rc = hip(hipStreamSynchronize(s), "the round's synchronisation");
+    if (rc != TOWR_OK) break;
+    ++rounds;
+    problem_iters += (int64_t)Bcur * K;
+    const int na = al.h_head[0];
+    rc = launch_move_rows(h, q.ID, na, Bcur - na, n_out, out_slot, out_dst, false, s);   // rows [na, Bcur) leave
+    Bcur = na;
+  }
+  std::vector<int32_t> is(4 * (size_t)N);
+  if (rc == TOWR_OK) rc = hip(hipMemcpyAsync(is.data(), q.ISTATE_OUT, sizeof(int32_t) * is.size(), hipMemcpyDeviceToHost, s), "copying ISTATE_OUT");
+  const hipError_t es = hipStreamSynchronize(s);   // (on every path: nothing of this call is in flight at return)
+  if (ter) (void)hipFree(ter);
+  if (rc != TOWR_OK) return rc;
+  if (int r2 = hip(es, "the last synchronisation")) return r2;
+  report->rounds = rounds;
+  report->iters_run = K * rounds;
+  report->problem_iters = problem_iters;
+  for (int i = 0; i < N; ++i) {
+    const int32_t p = is[4 * (size_t)i];
+    ++report->n_phase[p >= 0 && p <= 4 ? p : 5];
+    if (stop && p == kAlAcceptable) ++report->reserved[0];
+    if (stop && p == kAlInfeasible) ++report->reserved[1];
+  }
+  return TOWR_OK;
+}
+
 extern "C" {
+
+int towr_gpu_alsolve_solve_queue_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                              const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                              const towr_alsolve_state_t* state, const towr_solve_dir_t* dir,
+                                              const towr_solve_queue_t* queue, int32_t* LOG, towr_solve_report_t* report,
+                                              void* stream) {
+  return alsolve_solve_queue(h, B, opts, params, stop, state, dir, queue, LOG, report, stream);
+}
 
 int towr_gpu_alsolve_solve_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
                                         const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,

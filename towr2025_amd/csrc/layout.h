@@ -354,6 +354,26 @@ struct SwapRowsArgs {
 const void* alsolve_partition_kernel();
 const void* alsolve_swap_rows_kernel();
 
+// The queued solve's kernels (towr_gpu_alsolve_solve_queue_batch_device; lbfgs.hip). The retire key: one thread per row,
+// blocks of kLbfgsBlock over B; AGE[b] += add first (add = 0: AGE is only read). The move: a grid of (rows, arrays) blocks
+// of kLbfgsBlock threads; block (i, k) copies row r0 + i of slot[k] to row ID[r0 + i] of out[k] (reverse: the other way).
+// The descriptors travel in the argument struct, as the swap's.
+struct RetireKeyArgs {
+  const int32_t* ISTATE;
+  int32_t* AGE;
+  int32_t* KEY;
+  int32_t B, add, max_age, reserved;
+};
+constexpr int kMoveMaxArrays = TOWR_MOVE_MAX_ARRAYS;
+struct MoveRows { char* slot; int64_t slot_ld; char* out; int64_t out_ld; int64_t row_bytes; };
+struct MoveRowsArgs {
+  const int32_t* ID;
+  int32_t r0, count, n_arrays, reverse;
+  MoveRows rows[kMoveMaxArrays];
+};
+const void* alsolve_retire_key_kernel();
+const void* alsolve_move_rows_kernel();
+
 struct Layout {
   int n = 0, m = 0;
   int64_t nnz = 0;

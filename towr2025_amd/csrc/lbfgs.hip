@@ -1,7 +1,8 @@
 // lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
 // and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device); and the kernels of the
 // resident AL loop built on them (the line search, the outer update, the stop rule, the state's initialisation; at the
-// end), with the two kernels of the compacting solve behind those (the partition plan and the row swap).
+// end), with the two kernels of the compacting solve behind those (the partition plan and the row swap) and the two of
+// the queued solve (the retire key and the row move by index).
 //
 // The shape of resid.hip and step.hip. One block of kLbfgsBlock threads per problem. Lane l takes columns l,
 // l + kLbfgsBlock, ... in ascending order in every pass, so a column belongs to one lane for the whole kernel: the
@@ -639,10 +640,62 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_swap_rows_kernel(Swa
     swap_words<uint32_t>(p, q, r.row_bytes, threadIdx.x);
 }
 
+// The retire key of the queued solve (towr_gpu_alsolve_retire_key_batch_device): one thread per row. A row leaves its
+// slot when it is frozen (the partition's rule on its phase word) or when it has run out of budget: the key of an active
+// row whose age has reached max_age is 7, a word the partition counts as frozen; every other row's key is its phase
+// word. ISTATE is not written, so an expired problem keeps its RESTART / SEARCH word. add > 0: AGE[b] += add first (the
+// round's iterations). Integer compares only. Of a KEY row only word 0 is written.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_retire_key_kernel(RetireKeyArgs a) {
+  const int64_t b = (int64_t)blockIdx.x * kLbfgsBlock + threadIdx.x;
+  if (b >= a.B) return;
+  int32_t age = a.AGE[b];
+  if (a.add != 0) {
+    age += a.add;
+    a.AGE[b] = age;
+  }
+  const int32_t p = a.ISTATE[4 * b];
+  const bool act = p == kAlRestart || p == kAlSearch;
+  a.KEY[4 * b] = (act && age >= a.max_age) ? 7 : p;
+}
+
+// The row move of the queued solve (towr_gpu_alsolve_move_rows_batch_device): block (i, k), i < count, copies bytes
+// [0, row_bytes) of row r0 + i of slot[k] to row ID[r0 + i] of out[k], or with `reverse` from there into the slot row. A
+// negative ID skips its row. A word belongs to one lane; the IDs of one call are distinct, so no two blocks write the same
+// byte. 8 bytes per lane where both bases, both leading dimensions and the row length allow, else 4; coalesced.
+template <class T>
+__device__ inline void copy_words(const char* src, char* dst, int64_t bytes, int tid) {
+  const T* u = reinterpret_cast<const T*>(src);
+  T* v = reinterpret_cast<T*>(dst);
+  const int64_t nw = bytes / (int64_t)sizeof(T);
+#pragma unroll 4
+  for (int64_t j = tid; j < nw; j += kLbfgsBlock) v[j] = u[j];
+}
+
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_move_rows_kernel(MoveRowsArgs a) {
+  const int i = blockIdx.x;
+  if (i >= a.count) return;
+  const int64_t row = (int64_t)a.r0 + i;
+  const int32_t id = a.ID[row];
+  if (id < 0) return;
+  const MoveRows& r = a.rows[blockIdx.y];
+  char* p = r.slot + row * r.slot_ld;
+  char* q = r.out + (int64_t)id * r.out_ld;
+  const char* src = a.reverse ? q : p;
+  char* dst = a.reverse ? p : q;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(r.slot) | reinterpret_cast<uintptr_t>(r.out) | (uintptr_t)r.slot_ld |
+                         (uintptr_t)r.out_ld | (uintptr_t)r.row_bytes;
+  if ((bits & 7) == 0)
+    copy_words<unsigned long long>(src, dst, r.row_bytes, threadIdx.x);
+  else
+    copy_words<uint32_t>(src, dst, r.row_bytes, threadIdx.x);
+}
+
 }  // namespace
 
 const void* alsolve_partition_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_partition_kernel); }
 const void* alsolve_swap_rows_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_swap_rows_kernel); }
+const void* alsolve_retire_key_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_retire_key_kernel); }
+const void* alsolve_move_rows_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_move_rows_kernel); }
 const void* gn_select_kernel() { return reinterpret_cast<const void*>(&towr_gn_select_kernel); }
 const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }

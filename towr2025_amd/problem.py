@@ -888,27 +888,33 @@ class TowrGpuProblem:
             self._h, B, self._int_operand(ISTATE, "ISTATE", 4 * B), self._int_operand(HEAD, "HEAD", 8),
             self._int_operand(PAIRS, "PAIRS", 2 * (B // 2)), self._stream(stream, ISTATE)))
 
+    def _row_descs(self, arrays, what, limit):
+        """towr_rows_t descriptors of torch HIP tensors (1-D: rows of one element; 2-D: row-major rows) or of
+        (tensor, columns) for only the first `columns` of each row."""
+        if len(arrays) > limit:
+            raise TowrGpuError(f"{what}: {len(arrays)} arrays, at most {limit}")
+        desc = (capi.Rows * max(len(arrays), 1))()
+        for k, a in enumerate(arrays):
+            t, cols = a if isinstance(a, tuple) else (a, None)
+            if t.device.type != "cuda" or t.device.index != self.device or t.dim() not in (1, 2) or \
+                    (t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1):
+                raise TowrGpuError(f"{what}: array {k}: expected a 1-D or row-major 2-D tensor on the handle's device")
+            es = t.element_size()
+            width = 1 if t.dim() == 1 else t.shape[1]
+            cols = width if cols is None else int(cols)
+            if cols > width:
+                raise TowrGpuError(f"{what}: array {k}: {cols} columns of {width}")
+            ld = t.stride(0) if t.shape[0] > 1 else max(width, 1)
+            desc[k].base, desc[k].ld_bytes, desc[k].row_bytes = t.data_ptr(), ld * es, cols * es
+        return desc
+
     def alsolve_swap_rows(self, PAIRS, arrays, NP=None, npairs=0, max_pairs=None, stream=None):
         """Exchange rows PAIRS[2 i] and PAIRS[2 i + 1], i < count, of every array in place (towr_gpu.h). `arrays`: torch
         HIP tensors (1-D: rows of one element; 2-D: row-major rows, any padding behind the columns of a view is not
         touched) or (tensor, columns) to exchange only the first `columns` of each row. The count is NP[0] (an int32
         device tensor, e.g. HEAD[1:]; the grid holds max_pairs pairs, default PAIRS.numel() // 2) or, with NP None, the
         host value npairs."""
-        desc = (capi.Rows * max(len(arrays), 1))()
-        if len(arrays) > capi.SWAP_MAX_ARRAYS:
-            raise TowrGpuError(f"alsolve_swap_rows: {len(arrays)} arrays, at most {capi.SWAP_MAX_ARRAYS}")
-        for k, a in enumerate(arrays):
-            t, cols = a if isinstance(a, tuple) else (a, None)
-            if t.device.type != "cuda" or t.device.index != self.device or t.dim() not in (1, 2) or \
-                    (t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1):
-                raise TowrGpuError(f"alsolve_swap_rows: array {k}: expected a 1-D or row-major 2-D tensor on the handle's device")
-            es = t.element_size()
-            width = 1 if t.dim() == 1 else t.shape[1]
-            cols = width if cols is None else int(cols)
-            if cols > width:
-                raise TowrGpuError(f"alsolve_swap_rows: array {k}: {cols} columns of {width}")
-            ld = t.stride(0) if t.shape[0] > 1 else max(width, 1)
-            desc[k].base, desc[k].ld_bytes, desc[k].row_bytes = t.data_ptr(), ld * es, cols * es
+        desc = self._row_descs(arrays, "alsolve_swap_rows", capi.SWAP_MAX_ARRAYS)
         if NP is None:
             np_, n, mx = C.c_void_p(None), int(npairs), 0
             need = 2 * n
@@ -919,21 +925,8 @@ class TowrGpuProblem:
         self._check(self._lib.towr_gpu_alsolve_swap_rows_batch_device(
             self._h, np_, n, mx, self._int_operand(PAIRS, "PAIRS", max(need, 0)), len(arrays), desc, self._stream(stream, PAIRS)))
 
-    def alsolve_solve(self, params, st, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
-                      precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, compact=True,
-                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None):
-        """Run the resident loop to completion (towr_gpu.h, towr_gpu_alsolve_solve_batch_device): rounds of check_every
-        iterations of the method's iterate entry (capi.SOLVE_*; gn, DC, GSUM, PC / precond, W / wrows as that entry
-        takes them), the host looking at the phases once per round, until every problem is frozen or max_iters
-        iterations have run. compact: the frozen problems are moved out of the batch between rounds; every array is
-        back in the caller's order at return, and the persistent arrays hold the bits of the plain iterate loop. Per-problem
-        GL / GU / XL / XU rows are permuted during the call. The call blocks the host. LOG: int32 (>= 8 + 2 B), allocated
-        when None. Returns dict(rounds, iters_run, problem_iters, n_phase (6 counts: phases 0..4, other)). stop (an
-        alsolve_stop_params()): the stop rule runs in every iteration (towr_gpu_alsolve_solve_ex_batch_device) and the
-        dict also holds n_acceptable and n_infeasible, which n_phase[5] includes. ex: whether the call goes through the
-        _ex entry (default: when stop is given); ex=True with stop None passes stop == NULL to it."""
-        import torch
-        c = self._alsolve_state(st, params)
+    def _solve_dir(self, st, method, gn, DC, GSUM, PC, precond, W, wrows):
+        """towr_solve_dir_t of a solve on st's rows: what the method's iterate entry takes beside the state."""
         B = st.B
         d = capi.SolveDir()
         if method != capi.SOLVE_LBFGS:
@@ -955,6 +948,25 @@ class TowrGpuProblem:
                 raise TowrGpuError("alsolve_solve: the direct methods need the workspace W")
             wp, d.ldw, d.wrows = self._gn_workspace(W, wrows, B)
             d.W = wp.value
+        return d
+
+    def alsolve_solve(self, params, st, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
+                      precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, compact=True,
+                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None):
+        """Run the resident loop to completion (towr_gpu.h, towr_gpu_alsolve_solve_batch_device): rounds of check_every
+        iterations of the method's iterate entry (capi.SOLVE_*; gn, DC, GSUM, PC / precond, W / wrows as that entry
+        takes them), the host looking at the phases once per round, until every problem is frozen or max_iters
+        iterations have run. compact: the frozen problems are moved out of the batch between rounds; every array is
+        back in the caller's order at return, and the persistent arrays hold the bits of the plain iterate loop. Per-problem
+        GL / GU / XL / XU rows are permuted during the call. The call blocks the host. LOG: int32 (>= 8 + 2 B), allocated
+        when None. Returns dict(rounds, iters_run, problem_iters, n_phase (6 counts: phases 0..4, other)). stop (an
+        alsolve_stop_params()): the stop rule runs in every iteration (towr_gpu_alsolve_solve_ex_batch_device) and the
+        dict also holds n_acceptable and n_infeasible, which n_phase[5] includes. ex: whether the call goes through the
+        _ex entry (default: when stop is given); ex=True with stop None passes stop == NULL to it."""
+        import torch
+        c = self._alsolve_state(st, params)
+        B = st.B
+        d = self._solve_dir(st, method, gn, DC, GSUM, PC, precond, W, wrows)
         gl, gu, ldgb = self._bounds_operands(B, GL, GU)
         xl, xu, ldxb = self._var_bounds_operands(B, XL, XU)
         if LOG is None:
@@ -977,6 +989,105 @@ class TowrGpuProblem:
         if stop is not None:
             out.update(n_acceptable=rep.reserved[0], n_infeasible=rep.reserved[1])
         return out
+
+    # -------------------------------------------------------------------- a queue through the slots
+    def alsolve_retire_key(self, ISTATE, AGE, KEY, max_age, add=0, B=None, stream=None):
+        """The retire key of a batch (towr_gpu.h): KEY[4 b] = 7 for an active row (phase word 0 or 1) whose AGE[b] has
+        reached max_age, else the phase word; add > 0 is added to AGE first. ISTATE int32 (>= 4 B, not written), AGE int32
+        (>= B), KEY int32 (>= 4 B). B None: ISTATE.numel() // 4."""
+        B = ISTATE.numel() // 4 if B is None else int(B)
+        self._check(self._lib.towr_gpu_alsolve_retire_key_batch_device(
+            self._h, B, self._int_operand(ISTATE, "ISTATE", 4 * B), self._int_operand(AGE, "AGE", B), int(add), int(max_age),
+            self._int_operand(KEY, "KEY", 4 * B), self._stream(stream, ISTATE)))
+
+    def alsolve_move_rows(self, ID, slot, out, count, r0=0, reverse=False, stream=None):
+        """Copy row r0 + i of every slot array to row ID[r0 + i] of its out array, i < count (reverse: from there into the
+        slot row); a negative ID skips its row (towr_gpu.h). `slot`, `out`: equally many arrays as alsolve_swap_rows takes
+        them, pairwise with the same row bytes. ID: int32 (>= r0 + count)."""
+        if len(slot) != len(out):
+            raise TowrGpuError(f"alsolve_move_rows: {len(slot)} slot arrays, {len(out)} out arrays")
+        ds = self._row_descs(slot, "alsolve_move_rows", capi.MOVE_MAX_ARRAYS)
+        do = self._row_descs(out, "alsolve_move_rows", capi.MOVE_MAX_ARRAYS)
+        self._check(self._lib.towr_gpu_alsolve_move_rows_batch_device(
+            self._h, self._int_operand(ID, "ID", max(int(r0) + int(count), 0)), int(r0), int(count), len(slot), ds, do,
+            int(bool(reverse)), self._stream(stream, ID)))
+
+    def _queue_bounds(self, N, B, lo, up, cols, names, work):
+        """(lower, upper, ld, work lower, work upper, work ld, kept tensors) of a queue's bounds: None, 1-D (shared) or
+        (N, >= cols) per-problem rows, which need B slot-side work rows (`work`: a pair of tensors, or None to allocate)."""
+        import torch
+        lp, up_, ld = self._box_operands(N, lo, up, cols, names)
+        if ld == 0:
+            return lp, up_, 0, None, None, 0, ()
+        if work is None:
+            work = tuple(torch.empty((B, cols), dtype=torch.float64, device=lo.device) for _ in range(2))
+        wl, wu, ldw = self._box_operands(B, work[0], work[1], cols, (names[0] + "W", names[1] + "W", names[2]))
+        return lp, up_, ld, wl.value, wu.value, ldw, work
+
+    def alsolve_solve_queue(self, params, st, X0, LAM0=None, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
+                            precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, GL=None, GU=None,
+                            XL=None, XU=None, work=None, ID=None, AGE=None, KEY=None, out=None, LOG=None, stream=None,
+                            stop=None):
+        """Solve the N = X0.shape[0] problems of a queue through the B = st.B slots of `st` (towr_gpu.h,
+        towr_gpu_alsolve_solve_queue_batch_device): a problem leaves its slot when it is frozen or has run max_iters
+        iterations (a positive multiple of check_every), and the next one takes the freed row. X0 (N, >= n), LAM0
+        (N, >= m) or None (zeros); GL / GU / XL / XU: None, 1-D (shared) or N per-problem rows (only read). st, DC, GSUM, PC
+        and W are sized for B; what they hold before and after the call does not matter. work: dict(GLW, GUW, XLW, XUW) of
+        B-row tensors for per-problem bounds; ID / AGE (int32, >= B), KEY (int32, >= 4 B), LOG (int32, >= 8 + 2 B) and
+        `out` (dict of X_OUT (N, >= n), LAM_OUT (N, >= m), RHO_OUT (N), SCAL_OUT (N, 8), ISTATE_OUT (int32, 4 N),
+        ITERS_OUT (int32, N)) are allocated when not given. stop: an alsolve_stop_params(). The call blocks the host.
+        Returns dict(rounds, iters_run, problem_iters, n_phase, n_acceptable, n_infeasible) plus the output tensors under
+        their names: per problem bit for bit what alsolve_solve leaves for it in one batch of N."""
+        import torch
+        c = self._alsolve_state(st, params)
+        B, N, n, m = st.B, int(X0.shape[0]), self.n, self.m
+        dev = st.X.device
+        d = self._solve_dir(st, method, gn, DC, GSUM, PC, precond, W, wrows)
+        self._check_rows(N, (X0, "X0", n))
+        if LAM0 is not None:
+            self._check_rows(N, (LAM0, "LAM0", m))
+        work = dict(work or {})
+        q = capi.SolveQueue(N=N)
+        q.X0, q.ldx0 = X0.data_ptr(), X0.stride(0)
+        if LAM0 is not None:
+            q.LAM0, q.ldl0 = LAM0.data_ptr(), LAM0.stride(0)
+        gpair = (work["GLW"], work["GUW"]) if "GLW" in work else None
+        xpair = (work["XLW"], work["XUW"]) if "XLW" in work else None
+        gl, gu, q.ldgb, q.GLW, q.GUW, q.ldgw, keep_g = self._queue_bounds(N, B, GL, GU, m, ("GL", "GU", "m"), gpair)
+        xl, xu, q.ldxb, q.XLW, q.XUW, q.ldxw, keep_x = self._queue_bounds(N, B, XL, XU, n, ("XL", "XU", "n"), xpair)
+        q.GL, q.GU, q.XL, q.XU = gl.value, gu.value, xl.value, xu.value
+        ints = lambda k: torch.zeros(k, dtype=torch.int32, device=dev)
+        ID = ints(B) if ID is None else ID
+        AGE = ints(B) if AGE is None else AGE
+        KEY = ints(4 * B) if KEY is None else KEY
+        LOG = ints(8 + 2 * B) if LOG is None else LOG
+        q.ID, q.AGE, q.KEY = (self._int_operand(ID, "ID", B).value, self._int_operand(AGE, "AGE", B).value,
+                              self._int_operand(KEY, "KEY", 4 * B).value)
+        out = dict(out or {})
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        for k, make in (("X_OUT", lambda: z(N, n)), ("LAM_OUT", lambda: z(N, m)), ("RHO_OUT", lambda: z(N)),
+                        ("SCAL_OUT", lambda: z(N, 8)), ("ISTATE_OUT", lambda: ints(4 * N)), ("ITERS_OUT", lambda: ints(N))):
+            if k not in out:
+                out[k] = make()
+        self._check_rows(N, (out["X_OUT"], "X_OUT", n), (out["LAM_OUT"], "LAM_OUT", m), (out["SCAL_OUT"], "SCAL_OUT", 8))
+        if N > 1 and out["SCAL_OUT"].stride(0) != 8:
+            raise TowrGpuError("SCAL_OUT: expected contiguous rows of 8")
+        _check_per_problem(out["RHO_OUT"], "RHO_OUT", N, self.device)
+        q.X_OUT, q.ldxo = out["X_OUT"].data_ptr(), out["X_OUT"].stride(0)
+        q.LAM_OUT, q.ldlo = out["LAM_OUT"].data_ptr(), out["LAM_OUT"].stride(0)
+        q.RHO_OUT, q.SCAL_OUT = out["RHO_OUT"].data_ptr(), out["SCAL_OUT"].data_ptr()
+        q.ISTATE_OUT = self._int_operand(out["ISTATE_OUT"], "ISTATE_OUT", 4 * N).value
+        q.ITERS_OUT = self._int_operand(out["ITERS_OUT"], "ITERS_OUT", N).value
+        opts = capi.SolveOpts(method=int(method), max_iters=int(max_iters), check_every=int(check_every), compact=1)
+        rep = capi.SolveReport()
+        self._check(self._lib.towr_gpu_alsolve_solve_queue_batch_device(
+            self._h, B, C.byref(opts), C.byref(params), None if stop is None else C.byref(stop), C.byref(c), C.byref(d),
+            C.byref(q), self._int_operand(LOG, "LOG", 8 + 2 * (B // 2)), C.byref(rep), self._stream(stream, st.X)))
+        del keep_g, keep_x
+        res = dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase),
+                   n_acceptable=rep.reserved[0], n_infeasible=rep.reserved[1])
+        res.update(out)
+        return res
 
     def set_products_chunk(self, k: int):
         """Problems per chunk of eval_products_batch_device's values scratch (0 = automatic)."""
