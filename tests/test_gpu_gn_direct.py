@@ -59,8 +59,9 @@ def _run(c, mu=MU, rows=None, stream=None, V=None, GR=None, RUN=None, run_stride
     W = _workspace(c, B if wrows is None else wrows)
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
+    XL, XU = (sel(c["XLd"]), sel(c["XUd"])) if "XLd" in c else (None, None)   # (explicit bounds: tests/test_gpu_sweep_chol.py)
     c["p"].gn_direct_direction_batch_device(gn_params(mu=mu), Vd, sel(c["LPd"] if LAMP is None else LAMP), GRd, D, SUM, W, rho=sel(c["RHOd"]),
-                                            X=sel(c["Xd"]), RUN=RUN, run_stride=run_stride, stream=stream)
+                                            X=sel(c["Xd"]), XL=XL, XU=XU, RUN=RUN, run_stride=run_stride, stream=stream)
     torch.cuda.synchronize()
     assert np.isnan(W.cpu().numpy()[:, c["info"]["ldw_min"]:]).all(), "the workspace's padding was written"
     return D, SUM
@@ -103,9 +104,13 @@ def test_direction_against_numpy(name, B, wrows):
 
 @pytest.mark.parametrize("name,B,wrows", CASES)
 def test_bits_and_isolation(name, B, wrows):
+    check_bits_and_isolation(_operands(name, B), wrows)
+
+
+def check_bits_and_isolation(c, wrows):
+    """On the operands c (this file's, or tests/test_gpu_sweep_chol.py's)."""
     import torch
-    c = _operands(name, B)
-    p, n, nnz = c["p"], c["n"], c["nnz"]
+    p, n, nnz, B = c["p"], c["n"], c["nnz"], c["B"]
     x = c["X"][0]
     v_ref = p.eval_jac_values(x)
     p.eval_g_keep_jac(x)
@@ -115,7 +120,7 @@ def test_bits_and_isolation(name, B, wrows):
     assert (S0[:, 5] == 1).all()
     D1, S1 = _run(c)
     assert _same_bits(D0, D1) and _same_bits(S0, S1), "run to run"
-    for wr in (1, B):
+    for wr in (1, 2, B):
         D1, S1 = _run(c, wrows=wr)
         assert _same_bits(D0, D1) and _same_bits(S0, S1), f"wrows = {wr}"
     order = list(range(B))[::-1]
@@ -159,9 +164,13 @@ def test_breakdown_and_nothing_to_solve(name, B, wrows):
     rounding noise of either sign, and the device stops at column 19 of the monoped's problem 0 where both float64
     references stop at 21; the columns are printed.) And GR = +-0 on every free column of problem 1 (mu = 1e-6): code 3,
     D == GR with the signs of the zeros, no factorisation."""
+    check_breakdown_and_nothing_to_solve(_operands(name, B), name, wrows)
+
+
+def check_breakdown_and_nothing_to_solve(c, name, wrows):
+    """On the operands c (this file's, or tests/test_gpu_sweep_chol.py's)."""
     import torch
-    c = _operands(name, B)
-    n, pos = c["n"], c["info"]["pos"]
+    n, pos, B = c["n"], c["info"]["pos"], c["B"]
     D0, S0 = _run(c, mu=0.0, wrows=wrows)
     Sh = S0.cpu().numpy()
     seen = 0

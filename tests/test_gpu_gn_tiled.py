@@ -59,8 +59,10 @@ def _run(c, mu=MU, rows=None, stream=None, V=None, GR=None, RUN=None, run_stride
     W = _nan(B if wrows is None else wrows, ldw + 3)
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
+    XL, XU = (sel(c["XLd"]), sel(c["XUd"])) if "XLd" in c else (None, None)   # (explicit bounds: tests/test_gpu_sweep_chol.py)
     c["p"].gn_tiled_direction_batch_device(gn_params(mu=mu), Vd, sel(c["LPd"] if LAMP is None else LAMP), GRd, D, SUM, W,
-                                           rho=sel(c["RHOd"]), X=sel(c["Xd"]), RUN=RUN, run_stride=run_stride, stream=stream)
+                                           rho=sel(c["RHOd"]), X=sel(c["Xd"]), XL=XL, XU=XU, RUN=RUN, run_stride=run_stride,
+                                           stream=stream)
     torch.cuda.synchronize()
     assert np.isnan(W.cpu().numpy()[:, ldw:]).all(), "the workspace's padding was written"
     return D, SUM
@@ -105,9 +107,13 @@ def test_direction_against_numpy(name, B, wrows):
 
 @pytest.mark.parametrize("name,B,wrows", CASES)
 def test_bits_and_isolation(name, B, wrows):
+    check_bits_and_isolation(_operands(name, B), wrows)
+
+
+def check_bits_and_isolation(c, wrows):
+    """On the operands c (this file's, or tests/test_gpu_sweep_chol.py's)."""
     import torch
-    c = _operands(name, B)
-    p, n, nnz = c["p"], c["n"], c["nnz"]
+    p, n, nnz, B = c["p"], c["n"], c["nnz"], c["B"]
     x = c["X"][0]
     v_ref = p.eval_jac_values(x)
     p.eval_g_keep_jac(x)
@@ -115,7 +121,7 @@ def test_bits_and_isolation(name, B, wrows):
     v = p.eval_jac_values_kept(x)
     assert np.array_equal(v.view(np.int64), v_ref.view(np.int64)), "the kept Jacobian was dropped"
     assert (S0[:, 5] == 1).all()
-    D1, S1 = _baseline(name, B, wrows)
+    D1, S1 = _run(c, wrows=wrows)
     assert _same_bits(D0, D1) and _same_bits(S0, S1), "run to run, and the case's wrows"
     for wr in (1, 2, B):
         D1, S1 = _run(c, wrows=wr)
@@ -159,9 +165,13 @@ def test_breakdown_and_nothing_to_solve(name, B, wrows):
     pivot exactly 0 — code 2, SUM[7] that column, D == GR, no other problem's bits change (the others' own breakdown
     columns at mu = 0 are rounding noise and are not asserted). And GR = +-0 on every free column of problem 1 (mu = 1e-6):
     code 3, D == GR with the signs of the zeros, no factorisation."""
+    check_breakdown_and_nothing_to_solve(_operands(name, B), wrows)
+
+
+def check_breakdown_and_nothing_to_solve(c, wrows):
+    """On the operands c (this file's, or tests/test_gpu_sweep_chol.py's)."""
     import torch
-    c = _operands(name, B)
-    n, pos = c["n"], c["info"]["pos"]
+    n, pos, B = c["n"], c["info"]["pos"], c["B"]
     D0, S0 = _run(c, mu=0.0, wrows=wrows)
     others = torch.tensor([b for b in range(B) if b != 1], device=_dev())
     LP0 = c["LPd"].clone()
@@ -178,7 +188,7 @@ def test_breakdown_and_nothing_to_solve(name, B, wrows):
     assert np.array_equal(lbfgs_ref.held_mask(c["X"][1], g0, c["lo"][1], c["up"][1]), held)
     GR0 = c["GRd"].clone()
     GR0[1, :n] = torch.from_numpy(g0).to(_dev())
-    D2, S2 = _baseline(name, B, wrows)
+    D2, S2 = _run(c, wrows=wrows)
     D3, S3 = _run(c, GR=GR0, wrows=wrows)
     s = S3[1].cpu().numpy()
     assert (s[0], s[1], s[2], s[4], s[5], s[6], s[7]) == (0.0, 0.0, 0.0, held.sum(), 3.0, 0.0, -1.0), s[:8]

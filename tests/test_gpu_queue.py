@@ -15,7 +15,7 @@ from tests import stop_ref as S
 from tests.gpu_helpers import _dev, _nan, _same_bits, _terrains, _vec
 from tests.test_gpu_alsolve import ALL, SOLVE_PAR, _start, _state
 from tests.test_gpu_lbfgs import _ints, _problem
-from tests.test_gpu_solve import _bytes, _row, _tiled
+from tests.test_gpu_solve import _bytes, _row, _tiled, method_iterate, method_operands
 from towr2025_amd import _capi as capi, alsolve_params, alsolve_stop_params, gn_params
 
 pytestmark = pytest.mark.gpu
@@ -322,35 +322,34 @@ def test_per_problem_everything():
     assert _same_bits(G0, G1) and _same_bits(V0, V1), "the handle's batch terrains changed"
 
 
-@pytest.mark.parametrize("method", [capi.SOLVE_LBFGS, capi.SOLVE_GN_PC])
+@pytest.mark.parametrize("method", [capi.SOLVE_LBFGS, capi.SOLVE_GN_PC, capi.SOLVE_GN, capi.SOLVE_GN_DIRECT])
 def test_methods_equal_their_iterate_entry(method):
     """monoped_procedural, N = 5 through B = 2, M = 8, K = 4: the outputs are the method's iterate entry's after 8 iterations
     on the 5 rows. With L-BFGS a slot's history rows are an earlier tenant's when a problem enters: the slots start with NaN
-    history rows and a HMETA that points into them, so a history that leaked would show."""
+    history rows and a HMETA that points into them, so a history that leaked would show. The operands beside the state are
+    tests/test_gpu_solve.py's method_operands: the direct method's W has one row for the two slots."""
     import torch
     p, lo, up, _ = _problem("monoped_procedural")
     N, B, n, m, mem, M, K = 5, 2, p.n, p.m, SOLVE_PAR["mem"], 8, 4
     par = alsolve_params(**SOLVE_PAR)
-    gn = gn_params(ncg=20, mu=1e-2, tol=1e-3)
     h0 = _start(p, lo, up, N, mem, 7700)
-    pc = method == capi.SOLVE_GN_PC
-    extra = lambda rows: dict(gn=gn, DC=_nan(rows, n + 3), GSUM=_nan(rows, 8 + 2), PC=_nan(rows, n + 3)) if pc else {}
     ref = _state(p, N, mem, h0)
     p.alsolve_init(par, ref)
-    if pc:
-        e = extra(N)
-        p.alsolve_gn_pc_iterate(par, ref, gn, e["DC"], e["GSUM"], PC=e["PC"], iters=M)
-    else:
-        p.alsolve_iterate(par, ref, iters=M)
+    method_iterate(p, method, par, ref, method_operands(p, method, N, 2), M)
     torch.cuda.synchronize()
     st = _state(p, B, mem)
     st.HMETA.fill_(3)                       # (a count and a head that point into the NaN history rows)
+    kw = method_operands(p, method, B, 1)
     res = p.alsolve_solve_queue(par, st, _vec(h0["X"]), LAM0=_vec(h0["LAM"]), method=method, max_iters=M, check_every=K,
-                                out=_outputs(N, n, m), **extra(B))
+                                out=_outputs(N, n, m), **kw)
     torch.cuda.synchronize()
     iters, ph = _assert_report(res, N, B, K)
     _assert_outputs(res, ref, N, n, m, f"method {method}")
     assert res["rounds"] == 6 or not (iters == M).all(), (iters, res["rounds"])
+    if "GSUM" in kw:
+        assert torch.isnan(kw["GSUM"][:, 6 if method == capi.SOLVE_GN else 8:]).all() and torch.isnan(kw["DC"][:, n:]).all(), "padding written"
+    if "W" in kw:
+        assert torch.isnan(kw["W"][:, p.gn_factor_info()["ldw_min"]:]).all(), "the workspace's padding was written"
 
 
 def test_with_a_stop_rule():

@@ -281,40 +281,73 @@ def test_short_solve_with_and_without_compaction():
     assert rc["problem_iters"] == int(sum(4 * -(-d // 4) for d in life)), (rc, life.tolist())
 
 
-@pytest.mark.parametrize("method", [capi.SOLVE_LBFGS, capi.SOLVE_GN_PC])
+def method_operands(p, method, rows, wrows):
+    """What a method's iterate entry takes beside the state, on `rows` problems, as keywords of alsolve_solve /
+    alsolve_solve_queue (NaN-filled, padded leading dimensions). TOWR_SOLVE_GN's GSUM row is 6 doubles at a leading
+    dimension of 7 in a tensor of one row more: the drivers exchange 48 bytes of it, and an exchange of 64, as for the other
+    methods, would reach into the next row. TOWR_SOLVE_GN_DIRECT's W has `wrows` rows, longer than the envelope."""
+    n = p.n
+    if method == capi.SOLVE_LBFGS:
+        return {}
+    kw = dict(gn=gn_params(ncg=20, mu=1e-2, tol=1e-3), DC=_nan(rows, n + 3))
+    kw["GSUM"] = _nan(rows + 1, 6 + 1)[:rows] if method == capi.SOLVE_GN else _nan(rows, 8 + 2)
+    if method == capi.SOLVE_GN_PC:
+        kw["PC"] = _nan(rows, n + 3)
+    if method == capi.SOLVE_GN_DIRECT:
+        kw["W"] = _nan(wrows, p.gn_factor_info()["ldw_min"] + 5)
+    return kw
+
+
+def method_iterate(p, method, par, st, kw, iters):
+    """`iters` iterations of the method's iterate entry on the operands of method_operands."""
+    if method == capi.SOLVE_LBFGS:
+        p.alsolve_iterate(par, st, iters=iters)
+    elif method == capi.SOLVE_GN:
+        p.alsolve_gn_iterate(par, st, kw["gn"], kw["DC"], kw["GSUM"], iters=iters)
+    elif method == capi.SOLVE_GN_PC:
+        p.alsolve_gn_pc_iterate(par, st, kw["gn"], kw["DC"], kw["GSUM"], PC=kw["PC"], iters=iters)
+    else:
+        assert method == capi.SOLVE_GN_DIRECT
+        p.alsolve_gn_direct_iterate(par, st, kw["gn"], kw["DC"], kw["GSUM"], kw["W"], iters=iters)
+
+
+@pytest.mark.parametrize("method", [capi.SOLVE_LBFGS, capi.SOLVE_GN_PC, capi.SOLVE_GN, capi.SOLVE_GN_DIRECT])
 def test_methods_equal_their_iterate_entry(method):
     """monoped_procedural, B = 3, row 1 pre-frozen, max_iters = 6 in rounds of 2: with and without compaction the
     persistent arrays of every problem, and every array of the problems active to the end, are the method's iterate entry's
-    after 6 iterations on the whole batch."""
+    after 6 iterations on the whole batch. The direct method's W has wrows = 2 < B."""
     import torch
     p, lo, up, _ = _problem("monoped_procedural")
     B, n, mem = 3, p.n, SOLVE_PAR["mem"]
     par = alsolve_params(**SOLVE_PAR)
-    gn = gn_params(ncg=20, mu=1e-2, tol=1e-3)
     h0 = _start(p, lo, up, B, mem, 7700)
-    pc = method == capi.SOLVE_GN_PC
+    gnm = method != capi.SOLVE_LBFGS
 
     def fresh():
         st = _state(p, B, mem, h0)
         p.alsolve_init(par, st)
         st.ISTATE.view(B, 4)[1, 0] = R.STALLED
-        return st, (_nan(B, n + 3) if pc else None), (_nan(B, 8 + 2) if pc else None), (_nan(B, n + 3) if pc else None)
+        return st, method_operands(p, method, B, 2)
 
-    ref, DCr, GSr, PCr = fresh()
-    if pc:
-        p.alsolve_gn_pc_iterate(par, ref, gn, DCr, GSr, PC=PCr, iters=6)
-    else:
-        p.alsolve_iterate(par, ref, iters=6)
+    ref, kr = fresh()
+    method_iterate(p, method, par, ref, kr, 6)
     torch.cuda.synchronize()
+    if gnm:
+        solved = kr["GSUM"][[0, 2], 5].tolist()
+        print(f"method {method}: the iterate entry's direction codes of rows 0 and 2: {solved}")
+        assert not np.isnan(solved).any(), "the iterate entry wrote no direction for an active row"
     for compact in (True, False):
-        st, DC, GS, PC = fresh()
-        rep = p.alsolve_solve(par, st, method=method, gn=gn if pc else None, DC=DC, GSUM=GS, PC=PC, max_iters=6, check_every=2,
-                              compact=compact)
+        st, kw = fresh()
+        rep = p.alsolve_solve(par, st, method=method, max_iters=6, check_every=2, compact=compact, **kw)
         assert (rep["rounds"], rep["iters_run"]) == (3, 6) and rep["problem_iters"] == (3 * 2 + 2 * 2 + 2 * 2 if compact else 18), rep
         assert rep["n_phase"][3] == 1 and rep["n_phase"][0] + rep["n_phase"][1] == 2, rep
-        extra = (("DC", DC, DCr), ("GSUM", GS, GSr)) if pc else ()
+        extra = (("DC", kw["DC"], kr["DC"]), ("GSUM", kw["GSUM"], kr["GSUM"])) if gnm else ()
         _assert_rows(st, ref, (0, 2), ALL, f"method {method} compact {compact}", extra=extra)
         _assert_rows(st, ref, (1,), PERSISTENT, f"method {method} compact {compact}")
+        if gnm:
+            assert torch.isnan(kw["GSUM"][:, 6 if method == capi.SOLVE_GN else 8:]).all() and torch.isnan(kw["DC"][:, n:]).all()
+        if "W" in kw:
+            assert torch.isnan(kw["W"][:, p.gn_factor_info()["ldw_min"]:]).all(), "the workspace's padding was written"
 
 
 def test_isolation():
