@@ -1118,6 +1118,58 @@ int towr_gpu_alsolve_solve_ex_batch_device(towr_gpu_handle h, int32_t B, const t
                                            double* GU, int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
                                            towr_solve_report_t* report, void* stream);
 
+/* ---- probing the trial lengths before the expensive iteration ---------------------------------------------------------- */
+/* A rejected trial of the loops above pays for a whole iteration (in the GN loops: a direction at the candidate) although
+ * the line search only looks at the merit f + phi. The probe stage tests up to `trials` lengths of the line search's own
+ * ladder with cheap evaluations (an f-only objective launch, a g-only evaluation and the residual kernel) and leaves the
+ * state where the sequential loop would stand after the rejections it found, so that the following iteration runs at a
+ * length already known to pass. The bases the loop visits are bit for bit those of the loop without probes.
+ * trials = T in 1..TOWR_PROBE_MAX (host memory, read at the call).                                                      */
+#define TOWR_PROBE_MAX 8
+typedef struct { int32_t trials, reserved; } towr_alsolve_probe_t;
+
+/* The probe stage alone, in front of an iteration. PSUM (DEVICE, ldps >= 8) is its per-problem summary. A problem whose
+ * phase word is not SEARCH gets PSUM[b][0] = 0 and not one other byte of it changes (XC and PSUM[b][1..7] included). For
+ * a SEARCH problem, with X, D, GR, LAM[b], RHO[b], M0 = SCAL[0] and the bounds as the iteration sees them:
+ *   lengths: a_0 = ALPHA[b], a_t = a_{t-1} * shrink (one rounded product each: the bits the line search's rejected branch
+ *     produces). v = the number of leading t in 0..T with a_t >= alpha_min (a NaN ends the run); t = 0 always counts.
+ *   probes, for t < min(v, T) in ascending order: XT = P(X - a_t D), towr_gpu_step_batch_device's expression;
+ *     MC_t = F(XT) + phi(XT; LAM[b], RHO[b]), one rounded addition of the objective kernel's f (its f-only launch, whose F
+ *     is the gradient launch's bit for bit) and the residual kernel's SUM[3] at a g-only evaluation: the bits the line
+ *     search computes at the same point; gs_t = sum_j GR_j (XT_j - X_j) on the line search's tree;
+ *     pass_t = gs_t <= 0 and MC_t <= M0 + c1*gs_t, the line search's test (a NaN anywhere makes it false).
+ *   choice: t* = the first passing t. If none passes: t* = T when a_T is valid (the next, untested length), else
+ *     t* = v - 1 (the last valid length, known to fail: the following line search takes its code 4 / 5 branch at exactly
+ *     the base and counters of the sequential loop).
+ *   writes: ALPHA[b] = a_{t*}; XC = P(X - a_{t*} D); ISTATE inner += t* (the outer update's inner >= max_inner sees the
+ *     sequential loop's number); PSUM[b] = {code, t*, lengths probed, a_{t*}, MC_{t*} (NaN when untested), gs_{t*}, 0, 0},
+ *     code 1: a probed length passed, 2: none passed and an untested length follows, 3: none passed and the last valid
+ *     length stays.
+ * The candidates, their g, lam+ and summaries live in handle scratch. Fixed-tree sums, decisions on broadcast scalars:
+ * problem b's outputs are a function of its own operands alone, for any B, position and stream. Batch terrains,
+ * per-problem bounds rows, the cross-stream scratch rule and the kept Jacobian as for
+ * towr_gpu_alsolve_iterate_batch_device. TOWR_ERR_INVALID before anything runs for: what that entry refuses, a NULL
+ * probe, trials outside 1..TOWR_PROBE_MAX, a NULL PSUM, ldps < 8. TOWR_ERR_UNSUPPORTED as for the L-BFGS kernels.         */
+int towr_gpu_alsolve_probe_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                        const towr_alsolve_probe_t* probe, const towr_alsolve_state_t* state,
+                                        const double* GL, const double* GU, int64_t ldgb, const double* XL,
+                                        const double* XU, int64_t ldxb, double* PSUM, int64_t ldps, void* stream);
+
+/* towr_gpu_alsolve_solve_ex_batch_device with the probe stage in front of every iteration of the method's iterate entry
+ * (bit-identical to towr_gpu_alsolve_probe_batch_device and that entry with iters = 1 in sequence), for every method and
+ * both compact values. PSUM is the last iteration's summary of the rows as they stood in that iteration, not state: it
+ * is not exchanged by the compaction. iters_run, max_iters and check_every count probed iterations. The stop rule still
+ * runs once per iteration: with acc_iters > 0 its run length counts PROBED ITERATIONS, not the sequential loop's trials,
+ * so an ACCEPTABLE stop may come after fewer trials' worth of iterations than without probes. probe == NULL:
+ * towr_gpu_alsolve_solve_ex_batch_device itself (PSUM and ldps are not read). TOWR_ERR_INVALID before anything runs for
+ * what that entry refuses and, with a probe, for trials outside 1..TOWR_PROBE_MAX, a NULL PSUM or ldps < 8.              */
+int towr_gpu_alsolve_solve_probe_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                              const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                              const towr_alsolve_probe_t* probe, const towr_alsolve_state_t* state,
+                                              const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb,
+                                              double* XL, double* XU, int64_t ldxb, double* PSUM, int64_t ldps,
+                                              int32_t* LOG, towr_solve_report_t* report, void* stream);
+
 /* ---- a queue of problems through the resident solve's slots: each leaves when it is done, the next takes its row ---- */
 /* The retire key of a batch: which rows leave their slots. ISTATE as in towr_alsolve_state_t (only the phase word
  * ISTATE[4 b] is read; NOT WRITTEN), AGE is int32_t[B] (the iterations a row's problem has run), KEY is int32_t[4*B]

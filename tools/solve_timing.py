@@ -24,7 +24,13 @@ loop, whose iterate entry has no rule; MAX_INNER overrides SOLVE_PAR's 200.
 QUEUE=1: towr_gpu_alsolve_solve_queue_batch_device (queue_run below): N starts (N_MONOPED default 16384, N default 2048
 for ANYmal) through B slots (B_MONOPED 4096, B 512) with K = the first of KS, beside N / B successive compact = 1 solves of B
 and one compact = 1 solve of all N (ALL_AT_ONCE=0 leaves it out); STOP, FEASIBLE and MAX_ITERS as above.
-usage: python tools/solve_timing.py [anymal|monoped|all|stopcost]"""
+PROBE=T: the probe stage (towr_gpu_alsolve_solve_probe_batch_device). Per K two more variants, alternated with
+the others: (s) compact = 1 with shrink = PROBE_SHRINK (default 0.5) and no probes, (p) the same with T probes; the frozen
+count of every variant is printed, so the gain of the finer ladder and of the probes can be told apart. ONLY=c,p runs only
+the variants with those letters (n, c, h, s, p, n1, c1). `probecost` / `probecost_monoped`: the stage's own cost, as
+`stopcost`: one round of STOPCOST_ITERS iterations on all B problems (B / B_MONOPED, default 4096), compact = 0,
+shrink = PROBE_SHRINK, with and without PROBE (default 4) probes, alternated, per iteration.
+usage: python tools/solve_timing.py [anymal|monoped|all|stopcost|probecost|probecost_monoped]"""
 import ctypes as C
 import os
 import statistics
@@ -47,6 +53,9 @@ SEED = int(os.environ.get("SEED", "900"))
 SOLVE_PAR = dict(mem=8, shrink=0.1, rho0=10.0, curv_eps=1e-14, max_inner=int(os.environ.get("MAX_INNER", "200")), alpha_min=1e-16)
 FEASIBLE = os.environ.get("FEASIBLE", "0") == "1"
 STOP = os.environ.get("STOP", "0") == "1"
+PROBE = int(os.environ.get("PROBE", "0"))
+PROBE_SHRINK = float(os.environ.get("PROBE_SHRINK", "0.5"))
+ONLY = [v for v in os.environ.get("ONLY", "").split(",") if v]
 
 
 def stop_params():
@@ -86,6 +95,13 @@ def run(title, p, B):
         torch.cuda.synchronize()
 
     stop = stop_params() if STOP else None
+    par_fine = alsolve_params(**{**SOLVE_PAR, "shrink": PROBE_SHRINK})
+    PSUM = torch.zeros((B, 8), dtype=torch.float64, device=dev)
+
+    def probed(K, T):   # (T = 0: the finer ladder alone)
+        return p.alsolve_solve(par_fine, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=MAX_ITERS,
+                               check_every=K, compact=True, LOG=LOG, stream=stream, stop=stop, probes=T or None,
+                               PSUM=PSUM if T else None)
 
     def driver(K, compact):
         return p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=MAX_ITERS,
@@ -112,8 +128,13 @@ def run(title, p, B):
                      (f"c  K={K:<2d} compact=1", "spread", lambda K=K: driver(K, True))]
         if not STOP:
             variants += [(f"h  K={K:<2d} hand loop", "spread", lambda K=K: hand(K))]
+        if PROBE:
+            variants += [(f"s  K={K:<2d} compact=1 shrink={PROBE_SHRINK:g}", "spread", lambda K=K: probed(K, 0)),
+                         (f"p  K={K:<2d} compact=1 shrink={PROBE_SHRINK:g} probes={PROBE}", "spread", lambda K=K: probed(K, PROBE))]
     variants += [(f"n1 K={KS[0]:<2d} compact=0, one start", "same", lambda: driver(KS[0], False)),
                  (f"c1 K={KS[0]:<2d} compact=1, one start", "same", lambda: driver(KS[0], True))]
+    if ONLY:
+        variants = [v for v in variants if v[0].split()[0] in ONLY]
     # warm-up: every variant once (the tables' upload, the scratch, the page-locked HEAD); the bits of X kept per variant
     bits, reports = {}, {}
     for name, which, fn in variants:
@@ -138,8 +159,11 @@ def run(title, p, B):
         t, r = times[name], reports[name]
         med[name] = statistics.median(t)
         print(f"  {name:32s} {med[name]:9.2f} ms  (min {min(t):.2f} max {max(t):.2f})  rounds {r['rounds']} iters_run {r['iters_run']} "
-              f"problem_iters {r['problem_iters']} phases 0..4,other {r['n_phase']}"
+              f"problem_iters {r['problem_iters']} frozen {B - r['n_phase'][0] - r['n_phase'][1]} of {B} "
+              f"phases 0..4,other {r['n_phase']}"
               + (f" acceptable {r['n_acceptable']} infeasible {r['n_infeasible']}" if STOP else ""), flush=True)
+    if ONLY:                                   # (the ratios below need every variant)
+        return
     for K in KS:
         nn, cc, hh = (f"{v}  K={K:<2d} {w}" for v, w in (("n", "compact=0"), ("c", "compact=1"), ("h", "hand loop")))
         if STOP:
@@ -151,7 +175,7 @@ def run(title, p, B):
               f"{reports[cc]['problem_iters'] / max(reports[nn]['problem_iters'], 1):.3f}; driver n / hand loop {med[nn] / med[hh]:.3f}; "
               f"X bit-equal c vs n: {torch.equal(bits[cc].view(torch.int64), bits[nn].view(torch.int64))}, n vs hand: "
               f"{torch.equal(bits[nn].view(torch.int64), bits[hh].view(torch.int64))}", flush=True)
-    n1, c1 = variants[-2][0], variants[-1][0]
+    n1, c1 = (f"{v} K={KS[0]:<2d} compact={k}, one start" for v, k in (("n1", 0), ("c1", 1)))
     print(f"  one start: time c1 / n1 {med[c1] / med[n1]:.3f}; X bit-equal: "
           f"{torch.equal(bits[c1].view(torch.int64), bits[n1].view(torch.int64))}", flush=True)
 
@@ -186,6 +210,39 @@ def stop_cost(p, B):
     print(f"stop rule's cost: anymal B={B}, one round of {iters} iterations, ms per iteration: without {a:.4f} "
           f"(min {min(times['without']):.4f} max {max(times['without']):.4f}), with {b:.4f} (min {min(times['with']):.4f} max "
           f"{max(times['with']):.4f}), difference {1e3 * (b - a):.1f} us", flush=True)
+
+
+def probe_cost(title, p, B):
+    """One round of `iters` iterations on the whole batch with and without the probe stage, alternated (stop_cost's shape)."""
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    n, mem, iters, T = p.n, SOLVE_PAR["mem"], int(os.environ.get("STOPCOST_ITERS", "20")), PROBE or 4
+    par, gn = alsolve_params(**{**SOLVE_PAR, "shrink": PROBE_SHRINK}), gn_params(mu=MU)
+    x0 = p.initial_x()
+    X0 = torch.from_numpy(np.stack([x0 + 0.05 * np.random.default_rng(SEED + b).standard_normal(n) for b in range(B)])).to(dev)
+    st = AlSolveState.allocate(p, B, mem)
+    DC, GS = torch.zeros_like(st.X), torch.zeros((B, 8), dtype=torch.float64, device=dev)
+    W = torch.empty((B, p.gn_tile_info()["ldw_min"]), dtype=torch.float64, device=dev)
+    LOG = torch.zeros(8 + 2 * B, dtype=torch.int32, device=dev)
+    PSUM = torch.zeros((B, 8), dtype=torch.float64, device=dev)
+    times = {"without": [], "with": []}
+    for r in range(ROUNDS + 1):               # (round 0: warm-up)
+        for name, probes in (("without", None), ("with", T)):
+            st.X.copy_(X0)
+            st.LAM.zero_()
+            p.alsolve_init(par, st, stream=stream)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=iters,
+                            check_every=iters, compact=False, LOG=LOG, stream=stream, probes=probes, PSUM=PSUM if probes else None)
+            torch.cuda.synchronize()
+            if r:
+                times[name].append(1e3 * (time.perf_counter() - t0) / iters)
+    a, b = statistics.median(times["without"]), statistics.median(times["with"])
+    print(f"probe stage's cost: {title} B={B} T={T} shrink={PROBE_SHRINK:g}, one round of {iters} iterations, ms per iteration: "
+          f"without {a:.4f} (min {min(times['without']):.4f} max {max(times['without']):.4f}), with {b:.4f} (min "
+          f"{min(times['with']):.4f} max {max(times['with']):.4f}), ratio {b / a:.3f}", flush=True)
 
 
 def queue_run(title, p, N, B, K):
@@ -306,6 +363,12 @@ if __name__ == "__main__":
         sys.exit(0)
     if which == "stopcost":
         stop_cost(anymal(), int(os.environ.get("B", "4096")))
+    if which == "probecost":
+        probe_cost("anymal_trot_feasible" if FEASIBLE else "anymal_trot", anymal(), int(os.environ.get("B", "4096")))
+    if which == "probecost_monoped":
+        f, vs, cs, goal, T = F.procedural_monoped()
+        vb = f.var_bounds_data(varsets=vs, init_mode=capi.INIT_PROCEDURAL, ee_goal=goal, total_time=T)
+        probe_cost("monoped_procedural", TowrGpuProblem(F.procedural_desc(), device=0, data=vb), int(os.environ.get("B_MONOPED", "4096")))
     if which in ("anymal", "all"):
         run("anymal_trot_feasible" if FEASIBLE else "anymal_trot", anymal(), int(os.environ.get("B", "1024")))
     if which in ("monoped", "all"):

@@ -107,6 +107,13 @@ class AlSolveStop(C.Structure):   # towr_alsolve_stop_t
                 ("infeas_keep", C.c_double), ("infeas_rho", C.c_double)]
 
 
+PROBE_MAX = 8   # TOWR_PROBE_MAX
+
+
+class AlSolveProbe(C.Structure):   # towr_alsolve_probe_t
+    _fields_ = [("trials", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GnParams(C.Structure):   # towr_gn_params_t
     _fields_ = [("ncg", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double), ("tol", C.c_double)]
 
@@ -324,6 +331,14 @@ SYMBOLS = {
                                                           C.POINTER(AlSolveStop), C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
                                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                           C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
+    "towr_gpu_alsolve_probe_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(AlSolveParams), C.POINTER(AlSolveProbe),
+                                                       C.POINTER(AlSolveStateC), C.c_void_p, C.c_void_p, C.c_int64,
+                                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "towr_gpu_alsolve_solve_probe_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(SolveOpts), C.POINTER(AlSolveParams),
+                                                             C.POINTER(AlSolveStop), C.POINTER(AlSolveProbe),
+                                                             C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
+                                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                             C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
     "towr_gpu_alsolve_retire_key_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                             C.c_void_p, C.c_void_p]),
     "towr_gpu_alsolve_move_rows_batch_device": (C.c_int, [_HANDLE, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

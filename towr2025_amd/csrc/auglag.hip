@@ -28,7 +28,7 @@ void towr_gpu_handle_s::AugLag::release() {
   for (void* p : d_jp) if (p) (void)hipFree(p);
   for (void* p : d_gf) if (p) (void)hipFree(p);
   for (void* p : d_gt) if (p) (void)hipFree(p);
-  void* rest[] = {d_pv, d_set_row0, d_blo, d_bup, d_rg, d_rl, d_set_col0, d_xlo, d_xup, d_sd, d_sf};
+  void* rest[] = {d_pv, d_set_row0, d_blo, d_bup, d_rg, d_rl, d_set_col0, d_xlo, d_xup, d_sd, d_sf, d_pr};
   for (void* p : rest) if (p) (void)hipFree(p);
   if (h_head) (void)hipHostFree(h_head);
 }
@@ -808,6 +808,47 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
   return rc;
 }
 
+// the probe stage's own arguments (towr_alsolve_probe_t and its summary)
+int probe_args(towr_gpu_handle h, const towr_alsolve_probe_t* probe, const double* PSUM, int64_t ldps) {
+  if (!probe) return fail(h, TOWR_ERR_INVALID, "null probe");
+  if (probe->trials < 1 || probe->trials > TOWR_PROBE_MAX) return fail(h, TOWR_ERR_INVALID, "probe: trials outside 1..TOWR_PROBE_MAX");
+  if (!PSUM) return fail(h, TOWR_ERR_INVALID, "probe: null PSUM");
+  if (ldps < 8) return fail(h, TOWR_ERR_INVALID, "probe: ldps smaller than 8");
+  return TOWR_OK;
+}
+
+// The probe stage on the caller's stream (inside fused(), after residual_ready and step_ready): T + 1 launches of the
+// probe kernel and, between two of them, f (the f-only objective launch), g (the g-only evaluation) and the residual
+// kernel at the candidates. The candidates, f, g, lam+ and the residual summaries of the whole batch live in handle
+// scratch (d_sd, d_sf, d_rg, d_rl, d_pr); the iteration behind the stage reuses d_rg with its own rows.
+int probe_stage(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, int T, const towr_alsolve_state_t& st, const double* GL,
+                const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb, double* PSUM, int64_t ldps,
+                const Batch& b) {
+  towr_gpu_handle_s::AugLag& al = h->al;
+  const int64_t ldn = ld16(h->L.n), ldr = ld16(h->L.m), ldq = ld16(4 + (int64_t)h->L.cons.size());
+  int rc = scratch_grow(h, &al.d_sd, &al.sd_cap, B, ldn);
+  if (rc == TOWR_OK) rc = scratch_grow(h, &al.d_sf, &al.sf_cap, B, 1);
+  if (rc == TOWR_OK) rc = scratch_grow(h, &al.d_rg, &al.rg_cap, B, ldr);
+  if (rc == TOWR_OK) rc = scratch_grow(h, &al.d_rl, &al.rl_cap, B, ldr);
+  if (rc == TOWR_OK) rc = scratch_grow(h, &al.d_pr, &al.pr_cap, B, ldq);
+  if (rc != TOWR_OK) return rc;
+  ProbeArgs a{st, XL, XU, ldxb, al.d_sd, ldn, al.d_sf, al.d_pr, ldq, PSUM, ldps, p.c1, p.shrink, p.alpha_min, h->L.n, 0, T, 0};
+  if (!a.XL) { a.XL = al.d_xlo; a.XU = al.d_xup; a.ldb = 0; }
+  ResArgs r{al.d_rg, ldr, GL, GU, ldgb, st.LAM, st.ldl, al.d_rl, ldr, al.d_pr, ldq};
+  r.rho = 1.0;
+  r.RHO = st.RHO;
+  for (int t = 0; t <= T && rc == TOWR_OK; ++t) {
+    a.t = t;
+    void* args[] = {&a};
+    HIPCHK(h, launch_kernel(alsolve_probe_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, b.s));
+    if (t == T) break;
+    rc = launch_cost(h, B, al.d_sd, ldn, al.d_sf, nullptr, 0, b.s, b.ter, b.per);
+    if (rc == TOWR_OK) rc = launch(h, B, al.d_sd, ldn, al.d_rg, ldr, nullptr, 0, 1, 0, b.s, b.ter, b.per, -1);
+    if (rc == TOWR_OK) rc = launch_residual(h, B, r, b.s);
+  }
+  return rc;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1122,14 +1163,18 @@ int towr_gpu_alsolve_init_batch_device(towr_gpu_handle h, int32_t B, const towr_
 // Per iteration what the six public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag
 // chunks with the per-problem RHO accumulated onto GRC (g in handle scratch), the line search, the outer update, the
 // direction of the problems whose flag bit 1 is set (RUN = the flags) and the step.
-// (ter: fused()'s, the solve driver's permuted terrains; stop: the stop rule between the line search and the outer update)
+// (ter: fused()'s, the solve driver's permuted terrains; stop: the stop rule between the line search and the outer update;
+// probe: the probe stage in front of every iteration, PSUM / ldps its summary)
 static int alsolve_lbfgs_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                                  const towr_alsolve_state_t* state, const double* GL, const double* GU, int64_t ldgb,
                                  const double* XL, const double* XU, int64_t ldxb, void* stream,
-                                 const towr_terrain_t* ter = nullptr, const towr_alsolve_stop_t* stop = nullptr) {
+                                 const towr_terrain_t* ter = nullptr, const towr_alsolve_stop_t* stop = nullptr,
+                                 const towr_alsolve_probe_t* probe = nullptr, double* PSUM = nullptr, int64_t ldps = 0) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (stop)
     if (int rc = alsolve_stop_params(h, stop)) return rc;
+  if (probe)
+    if (int rc = probe_args(h, probe, PSUM, ldps)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   const towr_alsolve_state_t& st = *state;
   ResArgs r{nullptr, 0, GL, GU, ldgb, st.LAM, st.ldl, st.LAMP, st.ldl, st.RSUM, st.ldrs};
@@ -1146,7 +1191,8 @@ static int alsolve_lbfgs_iterate(towr_gpu_handle h, int32_t B, int32_t iters, co
   return fused(h, B, stream, {products_ready, residual_ready, step_ready}, [&](const Batch& b) {
     int rc = TOWR_OK;
     for (int it = 0; it < iters && rc == TOWR_OK; ++it) {
-      rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
+      if (probe) rc = probe_stage(h, B, *params, probe->trials, st, GL, GU, ldgb, XL, XU, ldxb, PSUM, ldps, b);
+      if (rc == TOWR_OK) rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
       if (rc == TOWR_OK)
         rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b);
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
@@ -1157,6 +1203,19 @@ static int alsolve_lbfgs_iterate(towr_gpu_handle h, int32_t B, int32_t iters, co
     }
     return rc;
   }, ter);
+}
+
+int towr_gpu_alsolve_probe_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                        const towr_alsolve_probe_t* probe, const towr_alsolve_state_t* state, const double* GL,
+                                        const double* GU, int64_t ldgb, const double* XL, const double* XU, int64_t ldxb,
+                                        double* PSUM, int64_t ldps, void* stream) {
+  if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
+  if (int rc = probe_args(h, probe, PSUM, ldps)) return rc;
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  return fused(h, B, stream, {residual_ready, step_ready}, [&](const Batch& b) {
+    return probe_stage(h, B, *params, probe->trials, *state, GL, GU, ldgb, XL, XU, ldxb, PSUM, ldps, b);
+  });
 }
 
 int towr_gpu_alsolve_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
@@ -1220,16 +1279,19 @@ int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const to
 // Per iteration what the public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag chunks
 // with the per-problem RHO accumulated onto GRC and, per chunk, the GN direction at (XC, GRC) into DC on the values still
 // in handle scratch (RUN = the phases: frozen problems are skipped), the line search, the outer update, the select
-// (D <- DC or GR by the flags) and the step. (stop: as above)
+// (D <- DC or GR by the flags) and the step. (stop, probe: as above)
 static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                               const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC, double* GSUM,
                               int64_t ldgs, bool pc, int32_t precond, double* PC, const double* GL, const double* GU, int64_t ldgb,
                               const double* XL, const double* XU, int64_t ldxb, void* stream, const GnWorkspace* ws = nullptr,
                               const towr_terrain_t* ter = nullptr,   // (ter: fused()'s)
-                              const towr_alsolve_stop_t* stop = nullptr) {
+                              const towr_alsolve_stop_t* stop = nullptr,
+                              const towr_alsolve_probe_t* probe = nullptr, double* PSUM = nullptr, int64_t ldps = 0) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (stop)
     if (int rc = alsolve_stop_params(h, stop)) return rc;
+  if (probe)
+    if (int rc = probe_args(h, probe, PSUM, ldps)) return rc;
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   if (int rc = ws ? gn_direct_params(h, gn, DC, GSUM, ldgs, *ws) : gn_params(h, gn, DC, GSUM, ldgs)) return rc;
   const towr_alsolve_state_t& st = *state;
@@ -1277,7 +1339,8 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
   return fused(h, B, stream, {tiled ? gn_tiled_ready : ws ? gn_direct_ready : gn_ready, residual_ready, step_ready}, [&](const Batch& b) {
     int rc = TOWR_OK;
     for (int it = 0; it < iters && rc == TOWR_OK; ++it) {
-      rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
+      if (probe) rc = probe_stage(h, B, *params, probe->trials, st, GL, GU, ldgb, XL, XU, ldxb, PSUM, ldps, b);
+      if (rc == TOWR_OK) rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
       if (rc == TOWR_OK)
         rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b,
                            ws ? nullptr : &g, ws && !tiled ? &gd : nullptr, ws ? ws->wrows : 0, tiled ? &gt : nullptr);
@@ -1548,11 +1611,12 @@ static void solve_state_rows(const Layout& L, const towr_alsolve_params_t& par, 
   }
 }
 
-// both solve entries; stop NULL: the plain loop and the plain report
+// the three solve entries; stop NULL: the plain loop and the plain report; probe NULL: no probe stage (PSUM is not read)
 static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts, const towr_alsolve_params_t* params,
                          const towr_alsolve_stop_t* stop, const towr_alsolve_state_t* state, const towr_solve_dir_t* dir,
                          double* GL, double* GU, int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
-                         towr_solve_report_t* report, void* stream) {
+                         towr_solve_report_t* report, void* stream, const towr_alsolve_probe_t* probe = nullptr,
+                         double* PSUM = nullptr, int64_t ldps = 0) {
   if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
   if (!opts || !dir || !LOG || !report) return fail(h, TOWR_ERR_INVALID, "solve: null opts, dir, LOG or report");
   if (opts->method < TOWR_SOLVE_LBFGS || opts->method > TOWR_SOLVE_GN_TILED) return fail(h, TOWR_ERR_INVALID, "solve: method outside 0..4");
@@ -1564,11 +1628,11 @@ static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* 
   const GnWorkspace ws{dir->W, dir->ldw, dir->wrows, method == TOWR_SOLVE_GN_TILED};
   // `iters` iterations of the method's iterate entry on rows [0, Bc): its own checks and launches (iters = 0: the checks)
   auto iterate = [&](int Bc, int iters, const towr_terrain_t* ter) -> int {
-    if (!gn) return alsolve_lbfgs_iterate(h, Bc, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream, ter, stop);
+    if (!gn) return alsolve_lbfgs_iterate(h, Bc, iters, params, state, GL, GU, ldgb, XL, XU, ldxb, stream, ter, stop, probe, PSUM, ldps);
     const bool pc = method == TOWR_SOLVE_GN_PC;
     return alsolve_gn_iterate(h, Bc, iters, params, state, dir->gn, dir->DC, dir->GSUM, dir->ldgs, pc,
                               pc ? dir->precond : (int32_t)TOWR_GN_PC_NONE, pc ? dir->PC : nullptr, GL, GU, ldgb, XL, XU, ldxb, stream,
-                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter, stop);
+                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter, stop, probe, PSUM, ldps);
   };
   // the iterate entry's refusals, TOWR_ERR_NO_DEVICE and TOWR_ERR_UNSUPPORTED (it binds the handle); nothing is queued.
   // Its argument checks come first: with another code they have passed, and this entry's own follow before that code
@@ -1869,6 +1933,15 @@ int towr_gpu_alsolve_solve_ex_batch_device(towr_gpu_handle h, int32_t B, const t
                                            int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
                                            towr_solve_report_t* report, void* stream) {
   return alsolve_solve(h, B, opts, params, stop, state, dir, GL, GU, ldgb, XL, XU, ldxb, LOG, report, stream);
+}
+
+int towr_gpu_alsolve_solve_probe_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                              const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                              const towr_alsolve_probe_t* probe, const towr_alsolve_state_t* state,
+                                              const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb, double* XL,
+                                              double* XU, int64_t ldxb, double* PSUM, int64_t ldps, int32_t* LOG,
+                                              towr_solve_report_t* report, void* stream) {
+  return alsolve_solve(h, B, opts, params, stop, state, dir, GL, GU, ldgb, XL, XU, ldxb, LOG, report, stream, probe, PSUM, ldps);
 }
 
 }  // extern "C"

@@ -180,6 +180,10 @@ struct towr_gpu_handle_s {
     double *d_xlo = nullptr, *d_xup = nullptr;
     double *d_sd = nullptr, *d_sf = nullptr;
     int64_t sd_cap = 0, sf_cap = 0;
+    // The probe stage (towr_gpu_alsolve_probe_batch_device): the residual summaries of its candidates (the batch); the
+    // candidates themselves, their f, g and lam+ use d_sd, d_sf, d_rg and d_rl
+    double* d_pr = nullptr;
+    int64_t pr_cap = 0;
     // The solve driver (towr_gpu_alsolve_solve_batch_device): page-locked host memory for the partition's HEAD (8 ints),
     // made by the first solve
     int32_t* h_head = nullptr;

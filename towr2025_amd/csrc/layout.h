@@ -328,6 +328,21 @@ struct AlInitArgs {
   double rho0, eta0, omega0;
   int32_t n;
 };
+// The probe stage (towr_gpu_alsolve_probe_batch_device): launch t of T + 1, one block of kLbfgsBlock threads per problem.
+// Launch t folds the outcome of trial t - 1 (F and RS hold f and the residual summary at the candidate XT of that trial)
+// and, while the problem is undecided, writes the candidate of trial t into XT. XT, F and RS are handle scratch; PSUM
+// carries the problem's running outcome between the launches ([0] = 0: undecided, [5] = gs of the candidate in XT).
+struct ProbeArgs {
+  towr_alsolve_state_t st;
+  const double *XL, *XU; int64_t ldb;
+  double* XT; int64_t ldxt;
+  const double* F;
+  const double* RS; int64_t ldrs;
+  double* PSUM; int64_t ldps;
+  double c1, shrink, alpha_min;
+  int32_t n, t, T, reserved;
+};
+const void* alsolve_probe_kernel();
 const void* linesearch_kernel();
 const void* alsolve_outer_kernel();
 const void* alsolve_stop_kernel();

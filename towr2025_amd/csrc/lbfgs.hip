@@ -1,6 +1,6 @@
 // lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
 // and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device); and the kernels of the
-// resident AL loop built on them (the line search, the outer update, the stop rule, the state's initialisation; at the
+// resident AL loop built on them (the line search, the probe stage in front of it, the outer update, the stop rule, the state's initialisation; at the
 // end), with the two kernels of the compacting solve behind those (the partition plan and the row swap) and the two of
 // the queued solve (the retire key and the row move by index).
 //
@@ -260,6 +260,100 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_linesearch_kernel(LineSearch
   Lb[5] = v[2];
   Lb[6] = store ? 1.0 : 0.0;
   Lb[7] = take ? __longlong_as_double((long long)pg) : pg_old;
+}
+
+// The probe stage of the resident AL loop (towr_gpu.h, towr_gpu_alsolve_probe_batch_device): launch t of T + 1. Between
+// two launches the host side evaluates f and phi at the candidates in XT (an f-only objective launch, a g-only
+// evaluation, the residual kernel). Launch t, for a SEARCH problem that no earlier launch decided (PSUM[0] == 0):
+//   folds trial t - 1: MC = F + RS[3], the line search's test on it and on the gs that launch t - 1 left in PSUM[5];
+//   passed, or a_t is below alpha_min: the stage ends at a_{t-1} (code 1 / 3); else t == T: it ends at the untested a_T
+//     (code 2); else the candidate of trial t goes into XT and its gs into PSUM[5].
+// Ending writes XC = P(X - a D) with the step kernel's expression (the bits trial t* left in XT), gs on the line search's
+// tree (block_sums: the lane's partial in column order), ALPHA, inner and the summary. The lengths are recomputed from
+// ALPHA by t rounded products; every lane reads ALPHA, inner and PSUM before the sums' barriers, lane 0 writes them behind.
+// A problem that is not in SEARCH gets PSUM[0] = 0 and, in XT, a copy of X for the evaluations between the launches.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_probe_kernel(ProbeArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double s_part[1][kLbfgsWaves], s_bc[1];
+  const towr_alsolve_state_t& st = a.st;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int n = a.n, t = a.t;
+  int32_t* IS = st.ISTATE + 4 * b;
+  double* Pb = a.PSUM + b * a.ldps;
+  double* XTb = a.XT + b * a.ldxt;
+  const double* Xb = st.X + b * st.ldx;
+  if (IS[0] != kAlSearch) {   // (block-uniform: before any barrier)
+    if (t == 0) {
+#pragma unroll 4
+      for (int j = tid; j < n; j += kLbfgsBlock) XTb[j] = Xb[j];
+      if (tid == 0) Pb[0] = 0.0;
+    }
+    return;
+  }
+  if (t > 0 && Pb[0] != 0.0) return;   // decided by an earlier launch (every lane reads the same word; no launch writes it meanwhile)
+  const double gs_prev = t > 0 ? Pb[5] : 0.0;
+  const int inner = IS[2];
+  const double m0 = st.SCAL[b * st.ldsc];
+  double prev = 0.0, cur = st.ALPHA[b];   // a_{t-1}, a_t
+  for (int k = 0; k < t; ++k) {
+    prev = cur;
+    cur = cur * a.shrink;
+  }
+  const bool cur_ok = t == 0 || cur >= a.alpha_min;   // (a NaN: false; the lengths before it were valid, or t - 1 had ended the stage)
+  double mc = __longlong_as_double(0x7ff8000000000000ll);
+  bool pass = false;
+  if (t > 0) {
+    mc = a.F[b] + a.RS[b * a.ldrs + 3];
+    const double c1gs = a.c1 * gs_prev;
+    pass = gs_prev <= 0.0 && mc <= m0 + c1gs;   // (a NaN anywhere: false)
+  }
+  int code = 0, tstar = 0;
+  double al = cur;
+  if (pass || !cur_ok) {
+    code = pass ? 1 : 3;
+    tstar = t - 1;
+    al = prev;
+  } else if (t == a.T) {
+    code = 2;
+    tstar = t;
+    mc = __longlong_as_double(0x7ff8000000000000ll);
+  }
+  double* Ob = code ? st.XC + b * st.ldx : XTb;
+  const double* Db = st.D + b * st.ldx;
+  const double* Gb = st.GR + b * st.ldx;
+  const double* Lo = a.XL + b * a.ldb;
+  const double* Up = a.XU + b * a.ldb;
+  double v[1] = {0.0};   // sum gr s
+#pragma unroll 4
+  for (int j = tid; j < n; j += kLbfgsBlock) {
+    const double x = Xb[j], d = Db[j], l = Lo[j], u = Up[j], g = Gb[j];
+    const bool has_l = l > -kSideInf, has_u = u < kSideInf;
+    const double ad = al * d;
+    double xp = x - ad;   // (the comparisons drop a NaN: xp stays NaN)
+    if (has_l && xp < l) xp = l;
+    if (has_u && xp > u) xp = u;
+    Ob[j] = xp;
+    const double s = xp - x;
+    v[0] += g * s;
+  }
+  block_sums<1>(v, s_part, s_bc, tid);
+  if (tid != 0) return;
+  if (!code) {
+    Pb[0] = 0.0;
+    Pb[5] = v[0];
+    return;
+  }
+  st.ALPHA[b] = al;
+  IS[2] = inner + tstar;
+  Pb[0] = (double)code;
+  Pb[1] = (double)tstar;
+  Pb[2] = (double)(code == 2 ? t : tstar + 1);
+  Pb[3] = al;
+  Pb[4] = mc;
+  Pb[5] = v[0];
+  Pb[6] = 0.0;
+  Pb[7] = 0.0;
 }
 
 __global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_direction_kernel(LbfgsDirArgs a) {
@@ -699,6 +793,7 @@ const void* alsolve_move_rows_kernel() { return reinterpret_cast<const void*>(&t
 const void* gn_select_kernel() { return reinterpret_cast<const void*>(&towr_gn_select_kernel); }
 const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }
+const void* alsolve_probe_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_probe_kernel); }
 const void* linesearch_kernel() { return reinterpret_cast<const void*>(&towr_linesearch_kernel); }
 const void* alsolve_outer_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_outer_kernel); }
 const void* alsolve_stop_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_stop_kernel); }

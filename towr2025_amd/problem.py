@@ -684,6 +684,25 @@ class TowrGpuProblem:
         self._check(self._lib.towr_gpu_alsolve_iterate_batch_device(self._h, st.B, int(iters), C.byref(params), C.byref(c),
                                                                     gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
 
+    def _probe_operands(self, B, probes, PSUM):
+        """(towr_alsolve_probe_t, PSUM pointer, ldps) of a probe stage with `probes` trials."""
+        if PSUM is None:
+            raise TowrGpuError("PSUM: required with probes")
+        self._check_rows(B, (PSUM, "PSUM", 8))
+        return capi.AlSolveProbe(trials=int(probes)), PSUM.data_ptr(), PSUM.stride(0)
+
+    def alsolve_probe(self, params, st, probes, PSUM, GL=None, GU=None, XL=None, XU=None, stream=None):
+        """The probe stage in front of an iteration (towr_gpu.h, towr_gpu_alsolve_probe_batch_device): up to `probes`
+        lengths of the line search's ladder are tested with cheap evaluations (f only, g only, the residual kernel) and
+        every SEARCH problem's ALPHA, XC and inner counter are left where the sequential loop would stand after the
+        rejections found. PSUM (B, >= 8): code, t*, lengths probed, the length, its merit (NaN when untested), gs."""
+        c = self._alsolve_state(st, params)
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        pr, ps, ldps = self._probe_operands(st.B, probes, PSUM)
+        self._check(self._lib.towr_gpu_alsolve_probe_batch_device(self._h, st.B, C.byref(params), C.byref(pr), C.byref(c),
+                                                                  gl, gu, ldgb, xl, xu, ldxb, ps, ldps, self._stream(stream, st.X)))
+
     # -------------------------------------------------------------------- Gauss-Newton -------
     def gn_direction_batch_device(self, gn, V, LAMP, GR, D, SUM, rho=1.0, X=None, XL=None, XU=None, RUN=None, run_stride=1,
                                   stream=None):
@@ -952,7 +971,7 @@ class TowrGpuProblem:
 
     def alsolve_solve(self, params, st, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
                       precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, compact=True,
-                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None):
+                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None, probes=None, PSUM=None):
         """Run the resident loop to completion (towr_gpu.h, towr_gpu_alsolve_solve_batch_device): rounds of check_every
         iterations of the method's iterate entry (capi.SOLVE_*; gn, DC, GSUM, PC / precond, W / wrows as that entry
         takes them), the host looking at the phases once per round, until every problem is frozen or max_iters
@@ -962,7 +981,9 @@ class TowrGpuProblem:
         when None. Returns dict(rounds, iters_run, problem_iters, n_phase (6 counts: phases 0..4, other)). stop (an
         alsolve_stop_params()): the stop rule runs in every iteration (towr_gpu_alsolve_solve_ex_batch_device) and the
         dict also holds n_acceptable and n_infeasible, which n_phase[5] includes. ex: whether the call goes through the
-        _ex entry (default: when stop is given); ex=True with stop None passes stop == NULL to it."""
+        _ex entry (default: when stop is given); ex=True with stop None passes stop == NULL to it. probes (1..capi.PROBE_MAX)
+        with PSUM (B, >= 8): the probe stage runs in front of every iteration (towr_gpu_alsolve_solve_probe_batch_device;
+        iters_run then counts probed iterations); probes=0 calls that entry with probe == NULL, which is the _ex entry."""
         import torch
         c = self._alsolve_state(st, params)
         B = st.B
@@ -974,6 +995,16 @@ class TowrGpuProblem:
         opts = capi.SolveOpts(method=int(method), max_iters=int(max_iters), check_every=int(check_every), compact=int(bool(compact)))
         rep = capi.SolveReport()
         log = self._int_operand(LOG, "LOG", 8 + 2 * B)
+        if probes is not None:
+            pr, ps, ldps = self._probe_operands(B, probes, PSUM) if probes else (None, None, 0)
+            self._check(self._lib.towr_gpu_alsolve_solve_probe_batch_device(
+                self._h, B, C.byref(opts), C.byref(params), None if stop is None else C.byref(stop),
+                None if pr is None else C.byref(pr), C.byref(c), C.byref(d), gl, gu, ldgb, xl, xu, ldxb, ps, ldps,
+                log, C.byref(rep), self._stream(stream, st.X)))
+            out = dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase))
+            if stop is not None:
+                out.update(n_acceptable=rep.reserved[0], n_infeasible=rep.reserved[1])
+            return out
         if not (stop is not None if ex is None else ex):
             if stop is not None:
                 raise TowrGpuError("alsolve_solve: stop needs the _ex entry (ex=False was given)")
