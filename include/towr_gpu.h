@@ -1170,6 +1170,76 @@ int towr_gpu_alsolve_solve_probe_batch_device(towr_gpu_handle h, int32_t B, cons
                                               double* XL, double* XU, int64_t ldxb, double* PSUM, int64_t ldps,
                                               int32_t* LOG, towr_solve_report_t* report, void* stream);
 
+/* ---- deciding a trial before its Gauss-Newton direction: the lazy GN loop ------------------------------------------------ */
+/* The GN iterate entries compute the direction at the candidate XC of every problem that is not frozen, before the line
+ * search has looked at the candidate; after a rejected trial nobody reads the problem's DC or GSUM row. Everything the
+ * line search's accept test reads is on the device once the products chunk's residual kernel has run, so the verdict
+ * stage restates that test ahead of the direction and the direction runs only where a base will be accepted. The words
+ * 0 (run) and 2 (skip) make VERDICT a RUN mask with run_stride = 1 for all four direction entries.
+ *
+ * The verdict stage alone. Fields of `state` used: X, GR, XC, ldx, FC, SCAL, ISTATE, RSUM (ldsc, ldrs); of `params`: c1.
+ * VERDICT is DEVICE memory, int32_t[B]; NDIR is DEVICE memory, int32_t[B], or NULL. Per problem b, with the phase word
+ * ISTATE[4 b]:
+ *   RESTART: VERDICT[b] = 0 (the line search always takes a RESTART candidate);
+ *   SEARCH:  gs = sum_j GR_j (XC_j - X_j) on the line search's tree (the lane's partial in column order j = lane,
+ *            lane + 256, ..., then the block's fixed tree), mc = FC[b] + RSUM[b][3], m0 = SCAL[b][0],
+ *            take = gs <= 0 and mc <= m0 + c1 gs (a rounded product, then a rounded addition; a NaN anywhere makes it
+ *            false): the bits and the test of towr_gpu_linesearch_batch_device on the same operands;
+ *            VERDICT[b] = take ? 0 : 2;
+ *   any other word (frozen, or garbage): VERDICT[b] = 2.
+ * NDIR[b] += 1 when the verdict is 0. Nothing else is written: the line search behind the stage finds exactly what it
+ * finds without it. Problem b's outputs are a function of its own operands alone, for any B, position and stream.
+ * TOWR_ERR_INVALID before anything runs for: NULL params, state or VERDICT, an invalid params field, a NULL used field,
+ * ldx < n, ldsc < 8, ldrs < 4, B < 0. TOWR_ERR_UNSUPPORTED and TOWR_ERR_NO_DEVICE as for the line search.                */
+int towr_gpu_alsolve_verdict_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                          const towr_alsolve_state_t* state, int32_t* VERDICT, int32_t* NDIR, void* stream);
+
+/* The lazy loop's two arrays (the struct is host memory; the pointers are DEVICE memory, int32_t[B] each; NDIR may be
+ * NULL). NDIR is only ever incremented: the caller zeroes it.                                                          */
+typedef struct { int32_t* VERDICT; int32_t* NDIR; } towr_alsolve_lazy_t;
+
+/* `iters` iterations of the method's GN iterate entry (method: TOWR_SOLVE_GN, _GN_PC, _GN_DIRECT or _GN_TILED; `dir` as
+ * towr_gpu_alsolve_solve_batch_device takes it) with one change inside each products chunk: behind the chunk's J^T lam+
+ * product the verdict stage runs on the chunk's rows, and the chunk's direction runs with RUN = those rows of VERDICT,
+ * run_stride = 1, in place of RUN = ISTATE, 4. Everything else is launch for launch that entry.
+ *   After any number of iterations, for any B, batch position, products chunk, wrows and stream, every field of `state`
+ *   (X, GR, XC, GRC, D, LAM, LAMP, HS, HY, HMETA, ALPHA, RHO, FC, SCAL, ISTATE, RSUM, SSUM, USUM, LSUM; DSUM is not
+ *   written) is bit for bit what the method's iterate entry leaves: the select step reads DC only where the line search
+ *   accepted a base, and there the verdict was 0.
+ *   DC, GSUM and, with TOWR_GN_PC_JACOBI, PC (the rows the direction kernel writes): a row is that entry's bits in every
+ *   iteration where the problem's verdict was 0; in an iteration where it was 2 not one byte of the row is touched. After
+ *   a run a row therefore holds the direction of the last candidate that was taken.
+ *   After the iteration's line search VERDICT[b] == 0 exactly when LSUM[b][0] is 1 or 2, and 2 otherwise; flag bit 0 set
+ *   implies VERDICT[b] == 0. NDIR[b] grows by the number of iterations with verdict 0 and no longer changes once the
+ *   problem is frozen.
+ * TOWR_ERR_INVALID before anything runs for: what the method's iterate entry refuses, a NULL dir, TOWR_SOLVE_LBFGS or a
+ * method outside 0..4 (L-BFGS has no direction at the candidate), a NULL lazy or lazy->VERDICT. TOWR_ERR_UNSUPPORTED and
+ * TOWR_ERR_NO_DEVICE as for that entry.                                                                                */
+int towr_gpu_alsolve_gn_lazy_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, int32_t method,
+                                                  const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                                  const towr_solve_dir_t* dir, const towr_alsolve_lazy_t* lazy,
+                                                  const double* GL, const double* GU, int64_t ldgb, const double* XL,
+                                                  const double* XU, int64_t ldxb, void* stream);
+
+/* towr_gpu_alsolve_solve_probe_batch_device with the lazy iteration above in place of the method's iterate entry, for
+ * both compact values and with or without stop and probe, which behave as there. lazy == NULL: that entry itself, launch
+ * for launch. With a lazy: every array that entry's contract names — the persistent arrays, the candidate-side and
+ * summary rows other than DC and GSUM, and the probe's PSUM — holds that entry's bits (PSUM[b][0] == 1, a probed length
+ * passed, implies VERDICT[b] == 0 in that iteration); DC and GSUM rows follow the rule above. With compact = 1, NDIR
+ * joins the exchanged per-problem arrays (one int per row; with it the state, DC, GSUM, four bounds arrays and the
+ * terrains are 28 descriptors of TOWR_SWAP_MAX_ARRAYS) and is back in the caller's order at return; since it no longer
+ * changes once a problem is frozen it is equal under compact = 0 and 1. VERDICT is rewritten in every iteration and is
+ * not exchanged, like PSUM: it holds the last iteration's words for the rows as they stood then. TOWR_ERR_INVALID before
+ * anything runs for what that entry refuses and, with a lazy, for TOWR_SOLVE_LBFGS and a NULL lazy->VERDICT. The queue
+ * entry below takes neither probe nor lazy.                                                                            */
+int towr_gpu_alsolve_solve_lazy_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                             const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                             const towr_alsolve_probe_t* probe, const towr_alsolve_state_t* state,
+                                             const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb,
+                                             double* XL, double* XU, int64_t ldxb, double* PSUM, int64_t ldps,
+                                             int32_t* LOG, towr_solve_report_t* report,
+                                             const towr_alsolve_lazy_t* lazy, void* stream);
+
 /* ---- a queue of problems through the resident solve's slots: each leaves when it is done, the next takes its row ---- */
 /* The retire key of a batch: which rows leave their slots. ISTATE as in towr_alsolve_state_t (only the phase word
  * ISTATE[4 b] is read; NOT WRITTEN), AGE is int32_t[B] (the iterations a row's problem has run), KEY is int32_t[4*B]

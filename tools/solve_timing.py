@@ -30,6 +30,11 @@ count of every variant is printed, so the gain of the finer ladder and of the pr
 the variants with those letters (n, c, h, s, p, n1, c1). `probecost` / `probecost_monoped`: the stage's own cost, as
 `stopcost`: one round of STOPCOST_ITERS iterations on all B problems (B / B_MONOPED, default 4096), compact = 0,
 shrink = PROBE_SHRINK, with and without PROBE (default 4) probes, alternated, per iteration.
+LAZY=1: the lazy GN loop (towr_gpu_alsolve_solve_lazy_batch_device). Every compact = 1 variant (c, s, p) gets a
+twin (cl, sl, pl) that runs the same solve through the lazy entry, alternated with the others; printed per pair: the ratio
+of times and directions / problem_iters, the share of problem iterations whose direction was computed. The tool asserts
+that a twin's report and persistent arrays (X, GR, LAM, RHO, SCAL, ISTATE, HS, HY, HMETA, D, ALPHA) are bit-equal to its
+eager variant's.
 usage: python tools/solve_timing.py [anymal|monoped|all|stopcost|probecost|probecost_monoped]"""
 import ctypes as C
 import os
@@ -56,6 +61,8 @@ STOP = os.environ.get("STOP", "0") == "1"
 PROBE = int(os.environ.get("PROBE", "0"))
 PROBE_SHRINK = float(os.environ.get("PROBE_SHRINK", "0.5"))
 ONLY = [v for v in os.environ.get("ONLY", "").split(",") if v]
+LAZY = os.environ.get("LAZY", "0") == "1"
+PERSISTENT = ("X", "GR", "LAM", "RHO", "SCAL", "ISTATE", "HS", "HY", "HMETA", "D", "ALPHA")
 
 
 def stop_params():
@@ -91,6 +98,9 @@ def run(title, p, B):
     def restart(which):
         st.X.copy_(X0[which])
         st.LAM.zero_()
+        if LAZY:   # (the slots a solve does not write would keep the previous variant's pairs: compared below)
+            st.HS.zero_()
+            st.HY.zero_()
         p.alsolve_init(par, st, stream=stream)
         torch.cuda.synchronize()
 
@@ -98,14 +108,21 @@ def run(title, p, B):
     par_fine = alsolve_params(**{**SOLVE_PAR, "shrink": PROBE_SHRINK})
     PSUM = torch.zeros((B, 8), dtype=torch.float64, device=dev)
 
-    def probed(K, T):   # (T = 0: the finer ladder alone)
+    VERDICT, NDIR = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+
+    def lazy_kw(lazy):   # (NDIR counts from zero in every solve; the memset is inside the window)
+        if lazy:
+            NDIR.zero_()
+        return dict(lazy=True, VERDICT=VERDICT, NDIR=NDIR) if lazy else {}
+
+    def probed(K, T, lazy=False):   # (T = 0: the finer ladder alone)
         return p.alsolve_solve(par_fine, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=MAX_ITERS,
                                check_every=K, compact=True, LOG=LOG, stream=stream, stop=stop, probes=T or None,
-                               PSUM=PSUM if T else None)
+                               PSUM=PSUM if T else None, **lazy_kw(lazy))
 
-    def driver(K, compact):
+    def driver(K, compact, lazy=False):
         return p.alsolve_solve(par, st, method=capi.SOLVE_GN_TILED, gn=gn, DC=DC, GSUM=GS, W=W, wrows=B, max_iters=MAX_ITERS,
-                               check_every=K, compact=compact, LOG=LOG, stream=stream, stop=stop)
+                               check_every=K, compact=compact, LOG=LOG, stream=stream, stop=stop, **lazy_kw(lazy))
 
     def hand(K):
         phases = st.ISTATE.view(B, 4)[:, 0]
@@ -131,17 +148,25 @@ def run(title, p, B):
         if PROBE:
             variants += [(f"s  K={K:<2d} compact=1 shrink={PROBE_SHRINK:g}", "spread", lambda K=K: probed(K, 0)),
                          (f"p  K={K:<2d} compact=1 shrink={PROBE_SHRINK:g} probes={PROBE}", "spread", lambda K=K: probed(K, PROBE))]
+        if LAZY:
+            variants += [(f"cl K={K:<2d} compact=1 lazy", "spread", lambda K=K: driver(K, True, True))]
+            if PROBE:
+                variants += [(f"sl K={K:<2d} compact=1 shrink={PROBE_SHRINK:g} lazy", "spread", lambda K=K: probed(K, 0, True)),
+                             (f"pl K={K:<2d} compact=1 shrink={PROBE_SHRINK:g} probes={PROBE} lazy", "spread",
+                              lambda K=K: probed(K, PROBE, True))]
     variants += [(f"n1 K={KS[0]:<2d} compact=0, one start", "same", lambda: driver(KS[0], False)),
                  (f"c1 K={KS[0]:<2d} compact=1, one start", "same", lambda: driver(KS[0], True))]
     if ONLY:
         variants = [v for v in variants if v[0].split()[0] in ONLY]
     # warm-up: every variant once (the tables' upload, the scratch, the page-locked HEAD); the bits of X kept per variant
-    bits, reports = {}, {}
+    bits, reports, kept = {}, {}, {}
     for name, which, fn in variants:
         restart(which)
         reports[name] = fn()
         torch.cuda.synchronize()
         bits[name] = st.X.clone()
+        if LAZY:
+            kept[name] = {k: getattr(st, k).clone() for k in PERSISTENT}
     times = {name: [] for name, _, _ in variants}
     for _ in range(ROUNDS):
         for name, which, fn in variants:
@@ -162,6 +187,22 @@ def run(title, p, B):
               f"problem_iters {r['problem_iters']} frozen {B - r['n_phase'][0] - r['n_phase'][1]} of {B} "
               f"phases 0..4,other {r['n_phase']}"
               + (f" acceptable {r['n_acceptable']} infeasible {r['n_infeasible']}" if STOP else ""), flush=True)
+    if LAZY:
+        for K in KS:
+            for e in ("c", "s", "p"):
+                a = next((v for v in times if v.startswith(f"{e}  K={K:<2d} ")), None)
+                b = next((v for v in times if v.startswith(f"{e}l K={K:<2d} ")), None)
+                if a is None or b is None:
+                    continue
+                ra, rb = reports[a], dict(reports[b])
+                directions = rb.pop("directions")
+                assert ra == rb, f"{b}: the report differs from the eager variant's: {rb} against {ra}"
+                for k in PERSISTENT:
+                    x, y = kept[a][k], kept[b][k]
+                    same = torch.equal(x, y) if x.dtype == torch.int32 else torch.equal(x.view(torch.int64), y.view(torch.int64))
+                    assert same, f"{b}: {k} differs from the eager variant's"
+                print(f"  K={K}: time {e}l / {e} {med[b] / med[a]:.3f}; directions {directions} of problem_iters {rb['problem_iters']} = "
+                      f"{directions / max(rb['problem_iters'], 1):.3f}; persistent arrays and report bit-equal: True", flush=True)
     if ONLY:                                   # (the ratios below need every variant)
         return
     for K in KS:

@@ -114,6 +114,10 @@ class AlSolveProbe(C.Structure):   # towr_alsolve_probe_t
     _fields_ = [("trials", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AlSolveLazy(C.Structure):   # towr_alsolve_lazy_t (device pointers: int32[B] each; NDIR may be NULL)
+    _fields_ = [("VERDICT", C.c_void_p), ("NDIR", C.c_void_p)]
+
+
 class GnParams(C.Structure):   # towr_gn_params_t
     _fields_ = [("ncg", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double), ("tol", C.c_double)]
 
@@ -339,6 +343,18 @@ SYMBOLS = {
                                                              C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
                                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                              C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(SolveReport), C.c_void_p]),
+    "towr_gpu_alsolve_verdict_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(AlSolveParams), C.POINTER(AlSolveStateC),
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "towr_gpu_alsolve_gn_lazy_iterate_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlSolveParams),
+                                                                 C.POINTER(AlSolveStateC), C.POINTER(SolveDir), C.POINTER(AlSolveLazy),
+                                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                                 C.c_void_p]),
+    "towr_gpu_alsolve_solve_lazy_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.POINTER(SolveOpts), C.POINTER(AlSolveParams),
+                                                            C.POINTER(AlSolveStop), C.POINTER(AlSolveProbe),
+                                                            C.POINTER(AlSolveStateC), C.POINTER(SolveDir),
+                                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                            C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(SolveReport),
+                                                            C.POINTER(AlSolveLazy), C.c_void_p]),
     "towr_gpu_alsolve_retire_key_batch_device": (C.c_int, [_HANDLE, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                             C.c_void_p, C.c_void_p]),
     "towr_gpu_alsolve_move_rows_batch_device": (C.c_int, [_HANDLE, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

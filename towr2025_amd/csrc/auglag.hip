@@ -703,6 +703,18 @@ int launch_stop(towr_gpu_handle h, int B, const towr_alsolve_params_t& p, const 
   return TOWR_OK;
 }
 
+// the verdict stage on rows [c0, c0 + B) of the whole batch's operands in `whole` (n: the handle's)
+int launch_verdict(towr_gpu_handle h, int B, const VerdictArgs& whole, int c0, hipStream_t s) {
+  VerdictArgs a = whole;
+  a.X += (int64_t)c0 * a.ldx; a.GR += (int64_t)c0 * a.ldx; a.XC += (int64_t)c0 * a.ldx;
+  a.FC += c0; a.SCAL += (int64_t)c0 * a.ldsc; a.ISTATE += 4 * (int64_t)c0; a.RSUM += (int64_t)c0 * a.ldrs;
+  a.VERDICT += c0; a.NDIR = row_at(a.NDIR, c0, 1);
+  a.n = h->L.n;
+  void* args[] = {&a};
+  HIPCHK(h, launch_kernel(alsolve_verdict_kernel(), dim3((unsigned)B), dim3(kLbfgsBlock), args, 0, s));
+  return TOWR_OK;
+}
+
 // ---- fused calls ----------------------------------------------------------------------------------------------------
 // the stream and terrains of a fused call
 struct Batch {
@@ -741,10 +753,13 @@ int fused(towr_gpu_handle h, int B, void* stream, std::initializer_list<Ready> r
 // chunk launches with its rows of them. With gn (the resident GN loop): behind a chunk's product, while its values are
 // still in d_pv, the GN direction at (e.X, z.Out) with that lam+ and rho into the chunk's rows of gn->D / gn->SUM (of gn
 // the bounds, RUN, D, SUM and the CG parameters are used); with gd the direct direction in its place (of gd the bounds,
-// RUN, D, SUM, the workspace and mu); with gt the tiled direct direction, as gd.
+// RUN, D, SUM, the workspace and mu); with gt the tiled direct direction, as gd. With vd (the lazy GN loop; vd holds the
+// whole batch's operands): behind a chunk's product the verdict stage on the chunk's rows, and the chunk's direction runs
+// with RUN = those rows of vd->VERDICT, run_stride 1, in place of the caller's RUN.
 struct EvalStage { const double* X; int64_t ldx; double* G; int64_t ldg; };
 int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r, const JpArgs& z, const Batch& b,
-                  const GnArgs* gn = nullptr, const GnDirectArgs* gd = nullptr, int wrows = 0, const GnTiledArgs* gt = nullptr) {
+                  const GnArgs* gn = nullptr, const GnDirectArgs* gd = nullptr, int wrows = 0, const GnTiledArgs* gt = nullptr,
+                  const VerdictArgs* vd = nullptr) {
   towr_gpu_handle_s::AugLag& al = h->al;
   const int64_t ldv = ld16(h->L.nnz), ldr = ld16(h->L.m);
   const int C = chunk_plan(h, B);
@@ -764,6 +779,7 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
     if (rc == TOWR_OK) rc = launch_residual(h, cb, a, b.s);
     if (rc == TOWR_OK)
       rc = launch_product(h, true, cb, product(al.d_pv, ldv, a.LAMP, a.ldlp, z.Out + (int64_t)c0 * z.ldo, z.ldo, z.accumulate), b.s);
+    if (rc == TOWR_OK && vd) rc = launch_verdict(h, cb, *vd, c0, b.s);
     if (rc == TOWR_OK && gn) {
       GnArgs g = *gn;
       g.V = al.d_pv; g.ldv = ldv;
@@ -773,6 +789,7 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
       g.GR = z.Out + (int64_t)c0 * z.ldo; g.ldgr = z.ldo;
       g.XL = row_at(gn->XL, c0, gn->ldb); g.XU = row_at(gn->XU, c0, gn->ldb);
       g.RUN = row_at(gn->RUN, c0, gn->run_stride);
+      if (vd) { g.RUN = vd->VERDICT + c0; g.run_stride = 1; }
       g.D = gn->D + (int64_t)c0 * gn->ldd;
       g.SUM = gn->SUM + (int64_t)c0 * gn->lds;
       if (gn->PC) g.PC = gn->PC + (int64_t)c0 * gn->ldpc;
@@ -787,6 +804,7 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
       g.GR = z.Out + (int64_t)c0 * z.ldo; g.ldgr = z.ldo;
       g.XL = row_at(gd->XL, c0, gd->ldb); g.XU = row_at(gd->XU, c0, gd->ldb);
       g.RUN = row_at(gd->RUN, c0, gd->run_stride);
+      if (vd) { g.RUN = vd->VERDICT + c0; g.run_stride = 1; }
       g.D = gd->D + (int64_t)c0 * gd->ldd;
       g.SUM = gd->SUM + (int64_t)c0 * gd->lds;
       rc = launch_gn_direct(h, cb, g, wrows, b.s);
@@ -800,6 +818,7 @@ int auglag_chunks(towr_gpu_handle h, int B, const EvalStage& e, const ResArgs& r
       g.GR = z.Out + (int64_t)c0 * z.ldo; g.ldgr = z.ldo;
       g.XL = row_at(gt->XL, c0, gt->ldb); g.XU = row_at(gt->XU, c0, gt->ldb);
       g.RUN = row_at(gt->RUN, c0, gt->run_stride);
+      if (vd) { g.RUN = vd->VERDICT + c0; g.run_stride = 1; }
       g.D = gt->D + (int64_t)c0 * gt->ldd;
       g.SUM = gt->SUM + (int64_t)c0 * gt->lds;
       rc = launch_gn_tiled(h, cb, g, wrows, b.s);
@@ -1279,19 +1298,22 @@ int towr_gpu_gn_direction_pc_batch_device(towr_gpu_handle h, int32_t B, const to
 // Per iteration what the public calls launch, on the caller's stream: the cost launch at XC (FC, GRC), the auglag chunks
 // with the per-problem RHO accumulated onto GRC and, per chunk, the GN direction at (XC, GRC) into DC on the values still
 // in handle scratch (RUN = the phases: frozen problems are skipped), the line search, the outer update, the select
-// (D <- DC or GR by the flags) and the step. (stop, probe: as above)
+// (D <- DC or GR by the flags) and the step. (stop, probe: as above; lazy: the verdict stage in every chunk, whose words
+// are the direction's RUN)
 static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const towr_alsolve_params_t* params,
                               const towr_alsolve_state_t* state, const towr_gn_params_t* gn, double* DC, double* GSUM,
                               int64_t ldgs, bool pc, int32_t precond, double* PC, const double* GL, const double* GU, int64_t ldgb,
                               const double* XL, const double* XU, int64_t ldxb, void* stream, const GnWorkspace* ws = nullptr,
                               const towr_terrain_t* ter = nullptr,   // (ter: fused()'s)
                               const towr_alsolve_stop_t* stop = nullptr,
-                              const towr_alsolve_probe_t* probe = nullptr, double* PSUM = nullptr, int64_t ldps = 0) {
+                              const towr_alsolve_probe_t* probe = nullptr, double* PSUM = nullptr, int64_t ldps = 0,
+                              const towr_alsolve_lazy_t* lazy = nullptr) {
   if (int rc = alsolve_args(h, B, params, state, GL, GU, ldgb, XL, XU, ldxb)) return rc;
   if (stop)
     if (int rc = alsolve_stop_params(h, stop)) return rc;
   if (probe)
     if (int rc = probe_args(h, probe, PSUM, ldps)) return rc;
+  if (lazy && !lazy->VERDICT) return fail(h, TOWR_ERR_INVALID, "lazy: null VERDICT");
   if (iters < 0) return fail(h, TOWR_ERR_INVALID, "iters is negative");
   if (int rc = ws ? gn_direct_params(h, gn, DC, GSUM, ldgs, *ws) : gn_params(h, gn, DC, GSUM, ldgs)) return rc;
   const towr_alsolve_state_t& st = *state;
@@ -1332,6 +1354,8 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
   if (ws) { gt.W = ws->W; gt.ldw = ws->ldw; }
   const bool tiled = ws && ws->tiled;
   const StepArgs step{st.X, st.ldx, st.D, st.ldx, st.ALPHA, 0.0, XL, XU, ldxb, st.XC, st.ldx, st.SSUM, st.ldss};
+  VerdictArgs vd{st.X, st.GR, st.XC, st.ldx, st.FC, st.SCAL, st.ldsc, st.ISTATE, st.RSUM, st.ldrs};
+  if (lazy) { vd.VERDICT = lazy->VERDICT; vd.NDIR = lazy->NDIR; vd.c1 = params->c1; }
   if (int rc = bind(h)) return rc;
   if (int rc = lbfgs_fits(h)) return rc;
   if (int rc = tiled ? gn_tiled_fits(h) : ws ? gn_direct_fits(h) : gn_fits(h)) return rc;
@@ -1343,7 +1367,8 @@ static int alsolve_gn_iterate(towr_gpu_handle h, int32_t B, int32_t iters, const
       if (rc == TOWR_OK) rc = launch_cost(h, B, st.XC, st.ldx, st.FC, st.GRC, st.ldx, b.s, b.ter, b.per);
       if (rc == TOWR_OK)
         rc = auglag_chunks(h, B, EvalStage{st.XC, st.ldx, nullptr, 0}, r, product(nullptr, 0, nullptr, 0, st.GRC, st.ldx, 1), b,
-                           ws ? nullptr : &g, ws && !tiled ? &gd : nullptr, ws ? ws->wrows : 0, tiled ? &gt : nullptr);
+                           ws ? nullptr : &g, ws && !tiled ? &gd : nullptr, ws ? ws->wrows : 0, tiled ? &gt : nullptr,
+                           lazy ? &vd : nullptr);
       if (rc == TOWR_OK) rc = launch_linesearch(h, B, *params, st, XL, XU, ldxb, b.s);
       if (rc == TOWR_OK && stop) rc = launch_stop(h, B, *params, *stop, st, b.s);
       if (rc == TOWR_OK) rc = launch_outer(h, B, *params, st, b.s);
@@ -1470,6 +1495,43 @@ int towr_gpu_alsolve_gn_tiled_iterate_batch_device(towr_gpu_handle h, int32_t B,
   const GnWorkspace ws{W, ldw, wrows, true};
   return alsolve_gn_iterate(h, B, iters, params, state, gn, DC, GSUM, ldgs, false, TOWR_GN_PC_NONE, nullptr, GL, GU, ldgb, XL, XU,
                             ldxb, stream, &ws);
+}
+
+// ---- the lazy GN loop: the line search's verdict ahead of the direction (lbfgs.hip) -------------------------------------
+int towr_gpu_alsolve_verdict_batch_device(towr_gpu_handle h, int32_t B, const towr_alsolve_params_t* params,
+                                          const towr_alsolve_state_t* state, int32_t* VERDICT, int32_t* NDIR, void* stream) {
+  if (!h || B < 0) return fail(h, TOWR_ERR_INVALID, "bad argument (B < 0)");
+  if (int rc = alsolve_params(h, params)) return rc;
+  if (!state) return fail(h, TOWR_ERR_INVALID, "null state");
+  if (!VERDICT) return fail(h, TOWR_ERR_INVALID, "verdict: null VERDICT");
+  const towr_alsolve_state_t& st = *state;   // (of the state only what the test reads)
+  if (!st.X || !st.GR || !st.XC) return fail(h, TOWR_ERR_INVALID, "state: null X, GR or XC");
+  if (!st.FC || !st.SCAL || !st.ISTATE || !st.RSUM) return fail(h, TOWR_ERR_INVALID, "state: null FC, SCAL, ISTATE or RSUM");
+  if (st.ldx < h->L.n) return fail(h, TOWR_ERR_INVALID, "state: ldx smaller than n");
+  if (st.ldsc < 8) return fail(h, TOWR_ERR_INVALID, "state: ldsc smaller than 8");
+  if (st.ldrs < 4) return fail(h, TOWR_ERR_INVALID, "state: ldrs smaller than 4");
+  if (int rc = bind(h)) return rc;
+  if (int rc = lbfgs_fits(h)) return rc;
+  if (B == 0) return TOWR_OK;
+  VerdictArgs a{st.X, st.GR, st.XC, st.ldx, st.FC, st.SCAL, st.ldsc, st.ISTATE, st.RSUM, st.ldrs, VERDICT, NDIR, params->c1};
+  return launch_verdict(h, B, a, 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+int towr_gpu_alsolve_gn_lazy_iterate_batch_device(towr_gpu_handle h, int32_t B, int32_t iters, int32_t method,
+                                                  const towr_alsolve_params_t* params, const towr_alsolve_state_t* state,
+                                                  const towr_solve_dir_t* dir, const towr_alsolve_lazy_t* lazy, const double* GL,
+                                                  const double* GU, int64_t ldgb, const double* XL, const double* XU,
+                                                  int64_t ldxb, void* stream) {
+  if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
+  if (!dir) return fail(h, TOWR_ERR_INVALID, "lazy: null dir");
+  if (method < TOWR_SOLVE_GN || method > TOWR_SOLVE_GN_TILED)
+    return fail(h, TOWR_ERR_INVALID, "lazy: method outside TOWR_SOLVE_GN..TOWR_SOLVE_GN_TILED (L-BFGS has no direction at the candidate)");
+  if (!lazy) return fail(h, TOWR_ERR_INVALID, "null lazy");
+  const bool pc = method == TOWR_SOLVE_GN_PC;
+  const GnWorkspace ws{dir->W, dir->ldw, dir->wrows, method == TOWR_SOLVE_GN_TILED};
+  return alsolve_gn_iterate(h, B, iters, params, state, dir->gn, dir->DC, dir->GSUM, dir->ldgs, pc,
+                            pc ? dir->precond : (int32_t)TOWR_GN_PC_NONE, pc ? dir->PC : nullptr, GL, GU, ldgb, XL, XU, ldxb, stream,
+                            method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, nullptr, nullptr, nullptr, nullptr, 0, lazy);
 }
 
 // ---- a solve to completion: rounds of the resident loop, frozen problems compacted out (lbfgs.hip) ---------------------
@@ -1611,15 +1673,17 @@ static void solve_state_rows(const Layout& L, const towr_alsolve_params_t& par, 
   }
 }
 
-// the three solve entries; stop NULL: the plain loop and the plain report; probe NULL: no probe stage (PSUM is not read)
+// the four solve entries; stop NULL: the plain loop and the plain report; probe NULL: no probe stage (PSUM is not read);
+// lazy NULL: the method's iterate entry as it is, else the lazy GN iteration (NDIR among the exchanged rows)
 static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts, const towr_alsolve_params_t* params,
                          const towr_alsolve_stop_t* stop, const towr_alsolve_state_t* state, const towr_solve_dir_t* dir,
                          double* GL, double* GU, int64_t ldgb, double* XL, double* XU, int64_t ldxb, int32_t* LOG,
                          towr_solve_report_t* report, void* stream, const towr_alsolve_probe_t* probe = nullptr,
-                         double* PSUM = nullptr, int64_t ldps = 0) {
+                         double* PSUM = nullptr, int64_t ldps = 0, const towr_alsolve_lazy_t* lazy = nullptr) {
   if (!h) return fail(h, TOWR_ERR_INVALID, "null handle");
   if (!opts || !dir || !LOG || !report) return fail(h, TOWR_ERR_INVALID, "solve: null opts, dir, LOG or report");
   if (opts->method < TOWR_SOLVE_LBFGS || opts->method > TOWR_SOLVE_GN_TILED) return fail(h, TOWR_ERR_INVALID, "solve: method outside 0..4");
+  if (lazy && opts->method == TOWR_SOLVE_LBFGS) return fail(h, TOWR_ERR_INVALID, "solve: lazy needs a GN method (L-BFGS has no direction at the candidate)");
   if (opts->max_iters < 0) return fail(h, TOWR_ERR_INVALID, "solve: max_iters is negative");
   if (opts->check_every < 1) return fail(h, TOWR_ERR_INVALID, "solve: check_every must be >= 1");
   if (opts->compact != 0 && opts->compact != 1) return fail(h, TOWR_ERR_INVALID, "solve: compact outside {0, 1}");
@@ -1632,7 +1696,7 @@ static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* 
     const bool pc = method == TOWR_SOLVE_GN_PC;
     return alsolve_gn_iterate(h, Bc, iters, params, state, dir->gn, dir->DC, dir->GSUM, dir->ldgs, pc,
                               pc ? dir->precond : (int32_t)TOWR_GN_PC_NONE, pc ? dir->PC : nullptr, GL, GU, ldgb, XL, XU, ldxb, stream,
-                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter, stop, probe, PSUM, ldps);
+                              method >= TOWR_SOLVE_GN_DIRECT ? &ws : nullptr, ter, stop, probe, PSUM, ldps, lazy);
   };
   // the iterate entry's refusals, TOWR_ERR_NO_DEVICE and TOWR_ERR_UNSUPPORTED (it binds the handle); nothing is queued.
   // Its argument checks come first: with another code they have passed, and this entry's own follow before that code
@@ -1650,6 +1714,7 @@ static int alsolve_solve(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* 
     if (row_bytes > 0) rows[nr++] = towr_rows_t{base, ld_bytes, row_bytes};
   };
   solve_state_rows(L, *params, st, *dir, method, add);
+  if (lazy && lazy->NDIR) add(lazy->NDIR, 4, 4);   // (VERDICT is rewritten by every iteration: not exchanged)
   if (GL && ldgb > 0) for (double* p : {GL, GU}) add(p, 8 * ldgb, 8 * (int64_t)L.m);
   if (XL && ldxb > 0) for (double* p : {XL, XU}) add(p, 8 * ldxb, 8 * (int64_t)L.n);
   if (int rc = swap_rows_args(h, nr, rows)) return rc;
@@ -1942,6 +2007,16 @@ int towr_gpu_alsolve_solve_probe_batch_device(towr_gpu_handle h, int32_t B, cons
                                               double* XU, int64_t ldxb, double* PSUM, int64_t ldps, int32_t* LOG,
                                               towr_solve_report_t* report, void* stream) {
   return alsolve_solve(h, B, opts, params, stop, state, dir, GL, GU, ldgb, XL, XU, ldxb, LOG, report, stream, probe, PSUM, ldps);
+}
+
+int towr_gpu_alsolve_solve_lazy_batch_device(towr_gpu_handle h, int32_t B, const towr_solve_opts_t* opts,
+                                             const towr_alsolve_params_t* params, const towr_alsolve_stop_t* stop,
+                                             const towr_alsolve_probe_t* probe, const towr_alsolve_state_t* state,
+                                             const towr_solve_dir_t* dir, double* GL, double* GU, int64_t ldgb, double* XL,
+                                             double* XU, int64_t ldxb, double* PSUM, int64_t ldps, int32_t* LOG,
+                                             towr_solve_report_t* report, const towr_alsolve_lazy_t* lazy, void* stream) {
+  return alsolve_solve(h, B, opts, params, stop, state, dir, GL, GU, ldgb, XL, XU, ldxb, LOG, report, stream, probe, PSUM, ldps,
+                       lazy);
 }
 
 }  // extern "C"

@@ -343,6 +343,21 @@ struct ProbeArgs {
   int32_t n, t, T, reserved;
 };
 const void* alsolve_probe_kernel();
+// The verdict stage (towr_gpu_alsolve_verdict_batch_device): the line search's accept test ahead of the direction, one
+// block of kLbfgsBlock threads per problem. Of the state only what the test reads; VERDICT takes 0 (a base will be
+// accepted) or 2, NDIR (may be NULL) counts the zeros. A products chunk launches with its rows of every pointer.
+struct VerdictArgs {
+  const double *X, *GR, *XC; int64_t ldx;
+  const double* FC;
+  const double* SCAL; int64_t ldsc;
+  const int32_t* ISTATE;
+  const double* RSUM; int64_t ldrs;
+  int32_t* VERDICT;
+  int32_t* NDIR;
+  double c1;
+  int32_t n, reserved;
+};
+const void* alsolve_verdict_kernel();
 const void* linesearch_kernel();
 const void* alsolve_outer_kernel();
 const void* alsolve_stop_kernel();

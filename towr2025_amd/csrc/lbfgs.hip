@@ -1,8 +1,8 @@
 // lbfgs.hip — the batched L-BFGS kernels: the per-problem ring of (s, y) pairs (towr_gpu_lbfgs_update_batch_device)
 // and the two-loop recursion on the free columns (towr_gpu_lbfgs_direction_batch_device); and the kernels of the
-// resident AL loop built on them (the line search, the probe stage in front of it, the outer update, the stop rule, the state's initialisation; at the
-// end), with the two kernels of the compacting solve behind those (the partition plan and the row swap) and the two of
-// the queued solve (the retire key and the row move by index).
+// resident AL loop built on them (the line search, the probe stage in front of it, the verdict stage of the lazy GN loop,
+// the outer update, the stop rule, the state's initialisation; at the end), with the two kernels of the compacting
+// solve behind those (the partition plan and the row swap) and the two of the queued solve (the retire key and the row move by index).
 //
 // The shape of resid.hip and step.hip. One block of kLbfgsBlock threads per problem. Lane l takes columns l,
 // l + kLbfgsBlock, ... in ascending order in every pass, so a column belongs to one lane for the whole kernel: the
@@ -354,6 +354,45 @@ __global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_probe_kernel(ProbeAr
   Pb[5] = v[0];
   Pb[6] = 0.0;
   Pb[7] = 0.0;
+}
+
+// The verdict stage of the lazy GN loop (towr_gpu.h, towr_gpu_alsolve_verdict_batch_device): the line search's accept
+// test restated ahead of the direction, on the operands the line search will find (the stage writes none of them).
+// RESTART: 0 (the line search always takes a RESTART candidate); SEARCH: gs = sum GR (XC - X) on the tree of the line
+// search's v[3] (block_sums: the lane's partial in column order), mc = FC + RSUM[3], the test on the broadcast sum; any
+// other word: 2. The words are a RUN mask for the direction kernels (run_stride 1). The phase is read by every lane at
+// entry; lane 0 writes VERDICT and counts the zeros in NDIR behind the sums' barriers.
+__global__ void __launch_bounds__(kLbfgsBlock) towr_alsolve_verdict_kernel(VerdictArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double s_part[1][kLbfgsWaves], s_bc[1];
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int n = a.n;
+  const int phase = a.ISTATE[4 * b];
+  int word = 2;
+  if (phase == kAlRestart) {
+    word = 0;
+  } else if (phase == kAlSearch) {   // (block-uniform: every lane reaches the sums' barriers)
+    const double* Xb = a.X + b * a.ldx;
+    const double* Gb = a.GR + b * a.ldx;
+    const double* XCb = a.XC + b * a.ldx;
+    const double mc = a.FC[b] + a.RSUM[b * a.ldrs + 3];
+    const double m0 = a.SCAL[b * a.ldsc];
+    double v[1] = {0.0};   // sum gr s
+#pragma unroll 4
+    for (int j = tid; j < n; j += kLbfgsBlock) {
+      const double g = Gb[j];
+      const double s = XCb[j] - Xb[j];
+      v[0] += g * s;
+    }
+    block_sums<1>(v, s_part, s_bc, tid);
+    const double c1gs = a.c1 * v[0];
+    const bool take = v[0] <= 0.0 && mc <= m0 + c1gs;   // (a NaN anywhere: false)
+    word = take ? 0 : 2;
+  }
+  if (tid != 0) return;
+  a.VERDICT[b] = word;
+  if (word == 0 && a.NDIR) a.NDIR[b] = a.NDIR[b] + 1;
 }
 
 __global__ void __launch_bounds__(kLbfgsBlock) towr_lbfgs_direction_kernel(LbfgsDirArgs a) {
@@ -794,6 +833,7 @@ const void* gn_select_kernel() { return reinterpret_cast<const void*>(&towr_gn_s
 const void* lbfgs_update_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_update_kernel); }
 const void* lbfgs_direction_kernel() { return reinterpret_cast<const void*>(&towr_lbfgs_direction_kernel); }
 const void* alsolve_probe_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_probe_kernel); }
+const void* alsolve_verdict_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_verdict_kernel); }
 const void* linesearch_kernel() { return reinterpret_cast<const void*>(&towr_linesearch_kernel); }
 const void* alsolve_outer_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_outer_kernel); }
 const void* alsolve_stop_kernel() { return reinterpret_cast<const void*>(&towr_alsolve_stop_kernel); }

@@ -890,6 +890,39 @@ class TowrGpuProblem:
             self._h, st.B, int(iters), C.byref(params), C.byref(c), C.byref(gn), C.c_void_p(DC.data_ptr()), *_opt(GSUM),
             wp, ldw, wr, gl, gu, ldgb, xl, xu, ldxb, self._stream(stream, st.X)))
 
+    # -------------------------------------------------------------------- the lazy GN loop ----
+    def _lazy_operands(self, B, VERDICT, NDIR):
+        """towr_alsolve_lazy_t of VERDICT (int32, >= B) and NDIR (int32, >= B, or None)."""
+        if VERDICT is None:
+            raise TowrGpuError("VERDICT: required")
+        return capi.AlSolveLazy(VERDICT=self._int_operand(VERDICT, "VERDICT", B).value,
+                                NDIR=None if NDIR is None else self._int_operand(NDIR, "NDIR", B).value)
+
+    def alsolve_verdict(self, params, st, VERDICT, NDIR=None, stream=None):
+        """The line search's accept test ahead of it (towr_gpu.h, towr_gpu_alsolve_verdict_batch_device), on st.X, GR, XC,
+        FC, SCAL, ISTATE and RSUM as the line search will find them: VERDICT[b] (int32) = 0 where a base will be accepted
+        (RESTART, or a SEARCH candidate that passes) and 2 otherwise (frozen rows included); NDIR[b] (int32, optional)
+        += 1 on a 0. Nothing else is written."""
+        c = self._alsolve_state(st, params)
+        lz = self._lazy_operands(st.B, VERDICT, NDIR)
+        self._check(self._lib.towr_gpu_alsolve_verdict_batch_device(self._h, st.B, C.byref(params), C.byref(c), lz.VERDICT, lz.NDIR,
+                                                                    self._stream(stream, st.X)))
+
+    def alsolve_gn_lazy_iterate(self, params, st, method, gn, DC, GSUM, VERDICT, NDIR=None, PC=None, precond=capi.GN_PC_JACOBI,
+                                W=None, wrows=None, iters=1, GL=None, GU=None, XL=None, XU=None, stream=None):
+        """`iters` iterations of the GN method's iterate entry (capi.SOLVE_GN, _GN_PC, _GN_DIRECT, _GN_TILED; gn, DC, GSUM,
+        PC / precond, W / wrows as that entry takes them) with alsolve_verdict ahead of every direction, which then runs
+        only where VERDICT is 0 (towr_gpu.h, towr_gpu_alsolve_gn_lazy_iterate_batch_device). The state is bit for bit that
+        entry's; a DC / GSUM / PC row is written only in an iteration whose candidate the line search takes."""
+        c = self._alsolve_state(st, params)
+        d = self._solve_dir(st, method, gn, DC, GSUM, PC, precond, W, wrows)
+        lz = self._lazy_operands(st.B, VERDICT, NDIR)
+        gl, gu, ldgb = self._bounds_operands(st.B, GL, GU)
+        xl, xu, ldxb = self._var_bounds_operands(st.B, XL, XU)
+        self._check(self._lib.towr_gpu_alsolve_gn_lazy_iterate_batch_device(
+            self._h, st.B, int(iters), int(method), C.byref(params), C.byref(c), C.byref(d), C.byref(lz), gl, gu, ldgb,
+            xl, xu, ldxb, self._stream(stream, st.X)))
+
     # -------------------------------------------------------------------- solve to completion -
     def _int_operand(self, t, what, count):
         import torch
@@ -971,7 +1004,8 @@ class TowrGpuProblem:
 
     def alsolve_solve(self, params, st, method=capi.SOLVE_GN_TILED, gn=None, DC=None, GSUM=None, PC=None,
                       precond=capi.GN_PC_JACOBI, W=None, wrows=None, max_iters=100, check_every=4, compact=True,
-                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None, probes=None, PSUM=None):
+                      GL=None, GU=None, XL=None, XU=None, LOG=None, stream=None, stop=None, ex=None, probes=None, PSUM=None,
+                      lazy=False, VERDICT=None, NDIR=None):
         """Run the resident loop to completion (towr_gpu.h, towr_gpu_alsolve_solve_batch_device): rounds of check_every
         iterations of the method's iterate entry (capi.SOLVE_*; gn, DC, GSUM, PC / precond, W / wrows as that entry
         takes them), the host looking at the phases once per round, until every problem is frozen or max_iters
@@ -983,7 +1017,11 @@ class TowrGpuProblem:
         dict also holds n_acceptable and n_infeasible, which n_phase[5] includes. ex: whether the call goes through the
         _ex entry (default: when stop is given); ex=True with stop None passes stop == NULL to it. probes (1..capi.PROBE_MAX)
         with PSUM (B, >= 8): the probe stage runs in front of every iteration (towr_gpu_alsolve_solve_probe_batch_device;
-        iters_run then counts probed iterations); probes=0 calls that entry with probe == NULL, which is the _ex entry."""
+        iters_run then counts probed iterations); probes=0 calls that entry with probe == NULL, which is the _ex entry.
+        lazy (a GN method): the solve runs through towr_gpu_alsolve_solve_lazy_batch_device, where every direction waits
+        for alsolve_verdict and runs only for a candidate the line search takes, with stop and probes as above; VERDICT
+        and NDIR (int32, B each) are allocated (NDIR zeroed) when None, and the dict also holds directions =
+        int(NDIR.sum()), the directions computed, beside problem_iters."""
         import torch
         c = self._alsolve_state(st, params)
         B = st.B
@@ -995,6 +1033,22 @@ class TowrGpuProblem:
         opts = capi.SolveOpts(method=int(method), max_iters=int(max_iters), check_every=int(check_every), compact=int(bool(compact)))
         rep = capi.SolveReport()
         log = self._int_operand(LOG, "LOG", 8 + 2 * B)
+        if lazy:
+            if VERDICT is None:
+                VERDICT = torch.zeros(B, dtype=torch.int32, device=st.X.device)
+            if NDIR is None:
+                NDIR = torch.zeros(B, dtype=torch.int32, device=st.X.device)
+            lz = self._lazy_operands(B, VERDICT, NDIR)
+            pr, ps, ldps = self._probe_operands(B, probes, PSUM) if probes else (None, None, 0)
+            self._check(self._lib.towr_gpu_alsolve_solve_lazy_batch_device(
+                self._h, B, C.byref(opts), C.byref(params), None if stop is None else C.byref(stop),
+                None if pr is None else C.byref(pr), C.byref(c), C.byref(d), gl, gu, ldgb, xl, xu, ldxb, ps, ldps,
+                log, C.byref(rep), C.byref(lz), self._stream(stream, st.X)))
+            out = dict(rounds=rep.rounds, iters_run=rep.iters_run, problem_iters=rep.problem_iters, n_phase=list(rep.n_phase),
+                       directions=int(NDIR.sum()))
+            if stop is not None:
+                out.update(n_acceptable=rep.reserved[0], n_infeasible=rep.reserved[1])
+            return out
         if probes is not None:
             pr, ps, ldps = self._probe_operands(B, probes, PSUM) if probes else (None, None, 0)
             self._check(self._lib.towr_gpu_alsolve_solve_probe_batch_device(
